@@ -16,7 +16,12 @@ N GPUs  ``--gpus N``: N chains, one per GPU, MC3 layout (config 3; weak scaling)
         RCCL.  Launched by ``torch.distributed.run`` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) - or by this script
         itself: without WORLD_SIZE it starts the N rank processes before anything touches a GPU and relays rank 0's line.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5|0] [--only] [--no-cpu-baseline]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5|0] [--only] [--no-cpu-baseline] [--dump-outputs DIR]
+
+``--dump-outputs DIR``: after the timed steps, what a caller of ``MCMC.run_steps`` holds for the measured chain (rank 0's) is written
+as ``DIR/<name>.npy`` in float64 - the weight matrices, the chain's scalars and the predictions on the training rows (a fixed, seeded
+sample of rows when they would pass 32 MB).  The inputs are seeded, so two builds given the same arguments can be compared array
+for array.
 """
 import argparse
 import csv
@@ -44,7 +49,32 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--only", action="store_true", help="the named config alone: without the other single-GPU configurations that the "
                                                          "default run (config 2) adds under other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the measured chain's weights, scalars and predictions as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_PREDICTION_BYTES = 32 << 20        # above this the predictions are dumped for a fixed, seeded sample of rows
+
+
+def dump_outputs(out_dir, bnn, mcmc):
+    """What the timed path hands its caller after the last timed step: the chain's weights (``bnn._w_layers``), its scalars and the
+    predictions of the accepted weights on the training rows (``mcmc._y``), as float64 .npy files (together well under 64 MB)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"weights_%d" % i: w for i, w in enumerate(bnn._w_layers)}
+    arrays["chain_scalars"] = [mcmc._logLik, mcmc._logPrior, mcmc._logPost, mcmc._acceptance_rate, mcmc._current_iteration]
+    if len(np.atleast_1d(bnn._error_prm)):
+        arrays["error_prm"] = np.atleast_1d(bnn._error_prm)
+    y = np.asarray(mcmc._y, dtype=np.float64)
+    if y.nbytes > DUMP_PREDICTION_BYTES:
+        n_keep = DUMP_PREDICTION_BYTES // max(1, y.nbytes // len(y))
+        rows = np.sort(np.random.default_rng(0).choice(len(y), n_keep, replace=False))
+        arrays["prediction_rows"] = rows
+        y = y[rows]
+    arrays["predictions"] = y
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -200,6 +230,8 @@ def main():
     advance(args.steps)
     sync()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bnn, mcmc)
     per_rank = None
     if comm is not None:
         # the slowest rank's clock prices the job; every rank's own clock, rate and acceptance go into the line beside it, so that

@@ -1,5 +1,5 @@
 """Seeded synthetic inputs shared by the golden-vector generator
-(``make_golden.py``, runs only where /root/reference exists) and the tests
+(``make_golden.py``, runs only beside an upstream np_bnn checkout) and the tests
 (run anywhere).  Inputs are regenerated from seeds so the committed ``.npz``
 fixtures only need to hold the reference's *outputs*.
 """

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Generate the golden vectors in tests/golden/*.npz from the REFERENCE.
 
-Runs only in the build container, where the upstream repository is mounted at
-/root/reference (np_bnn 0.1.23, imported unmodified; nothing of it is copied
-into this repository -- only its numeric outputs on seeded synthetic inputs
-are stored).  Usage:  python tests/golden/make_golden.py
+Runs only beside a checkout of the upstream repository (np_bnn 0.1.23,
+imported unmodified; nothing of it is copied into this repository -- only its
+numeric outputs on seeded synthetic inputs are stored).  Usage:
+    NPBNN_UPSTREAM_DIR=<np_bnn checkout> python tests/golden/make_golden.py
 
 Groups:
   G1 grid.npz        forward / categorical likelihood / accuracy statistics
@@ -30,7 +30,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-sys.path.insert(0, "/root/reference")
+UPSTREAM = os.environ.get("NPBNN_UPSTREAM_DIR")
+if not UPSTREAM:
+    sys.exit("NPBNN_UPSTREAM_DIR: set it to a checkout of the upstream np_bnn repository (0.1.23)")
+sys.path.insert(0, UPSTREAM)
 
 import cases  # noqa: E402
 import np_bnn as bn  # noqa: E402  (the reference)

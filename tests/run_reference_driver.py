@@ -1,6 +1,6 @@
 """Run one of the REFERENCE's own driver scripts, unchanged, against this package (CPU; test infrastructure).
 
-    python tests/run_reference_driver.py /root/reference/bnn_classify.py
+    python tests/run_reference_driver.py <np_bnn checkout>/bnn_classify.py
 
 ``np_bnn`` is made to resolve to ``npbnn_amd`` before the script is executed from where it lies (nothing of it is copied); the
 device is absent here, so the package's device seams are served by the float64 oracle: the sampler's backend
