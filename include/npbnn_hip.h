@@ -45,7 +45,8 @@ enum {
     NPBNN_E_NOMEM = -4,
     NPBNN_E_COMM = -5,      /* RCCL failure                           */
     NPBNN_E_RANGE = -6,     /* value outside the fp16-split range      */
-    NPBNN_E_SYNC = -7       /* a device-side wait of NPBNN_SCHED_OVERLAP2 timed out */
+    NPBNN_E_SYNC = -7,      /* a device-side wait of NPBNN_SCHED_OVERLAP2 timed out */
+    NPBNN_E_INTERNAL = -8   /* the library's own plan and its buffers disagree (a bug: the launch is refused) */
 };
 
 /* activation kinds — ActFun.activate selection, np_bnn/BNN_lib.py:50-87 */

@@ -32,6 +32,7 @@ INFO_WIDE = 10
 INFO_F16_MOVED_COLUMNS, INFO_F16_MAX_MOVE = 11, 12
 E_RANGE = -6
 E_SYNC = -7
+E_INTERNAL = -8
 
 LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libnpbnn_hip.so")

@@ -94,6 +94,13 @@ int upload_matrix(npbnn_ctx* ctx, const T* X, int64_t n_rows, int32_t F, int whi
         }
         HIP_TRY(ctx, hipMemcpy(d.X + r0 * d.Fp, stage.data(), nr * d.Fp * sizeof(float), hipMemcpyHostToDevice));
     }
+    // A net built on another training matrix is built again, as npbnn_set_arch would build it on this one: the choice of path reads
+    // the row count (wide_needed) and the fp16-split positions of the chain's proposals carry the old matrix's column scales
+    // (d_w2scale).  Float32 layout first, as npbnn_set_arch; plan_launch moves to fp16-split when it applies.
+    if (which == 0 && ctx->arch_set) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return rebuild_net(ctx, false);
+    }
     return NPBNN_OK;
 }
 

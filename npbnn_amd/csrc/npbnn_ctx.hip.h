@@ -217,9 +217,13 @@ struct npbnn_ctx {
     bool wide = false;
     int wide_option = 0;           // NPBNN_OPT_WIDE: 0 when the resident path cannot hold the network, 1 always
     WideMeta wmeta{};
+    // Sizes: d_wide_cand and d_wide_cs by the network alone (wide_build); d_prep_terms by the widest proposal (prep_cap, chain_prepare);
+    // the fp16-split copy Dataset::X16w by its own table (built by wide_plan, freed with the table); d_wide_act by the largest table a plan
+    // was made for (wide_plan: rows x widest layer, and npbnn_wide_slice_room for the K-slices), which wide_forward checks every launch against.
     float* d_wide_cand = nullptr;  // candidate image of a device chain (the committed image with the pending proposal patched in)
     float* d_wide_act[3] = {nullptr, nullptr, nullptr};   // hidden activations [rows][16 * tiles], ping-pong between layers; [2]: the K-slices' sums
-    size_t wide_act_cap = 0;       // floats each
+    size_t wide_act_cap = 0;       // floats each of [0], [1]
+    size_t wide_slice_cap = 0;     // floats of [2] (npbnn_wide_slice_room of the largest demand met; wide_forward checks every launch against it)
     double* d_prep_terms = nullptr;       // [kMaxCand][M] prior terms of the pending candidates' entries (ChainParams::prep_terms)
     size_t prep_cap = 0;
     WideCandState* d_wide_cs = nullptr;   // what the candidate image's last patch covered (wide proposals: wide_cand_sync)

@@ -24,6 +24,8 @@
 #include "numpy/random/bitgen.h"
 #include "numpy/random/distributions.h"
 
+#include "npbnn_wide_plan.h"
+
 #define NPBNN_HOST_MAX_LAYERS 8
 
 /* ---------------------------------------------------------------------------------------------
@@ -676,4 +678,11 @@ int npbnn_host_predraw_state(uint64_t* gen, int64_t first_iteration, int64_t mcm
     gen[2] = (uint64_t)(g.inc >> 64); gen[3] = (uint64_t)g.inc;
     gen[4] = (uint64_t)g.has_uint32; gen[5] = (uint64_t)g.uinteger;
     return rc;
+}
+
+/* The floats of the K-slice buffer a pass of the weight-streamed path over a table of n_rows rows needs (npbnn_wide_plan.h: the rule
+ * the HIP library sizes that buffer by), exported for the CPU tests of that rule. */
+long long npbnn_host_wide_slice_room(int n_layers, const int32_t* out_dim, int in_dim, int64_t n_rows, int n_cu) {
+    if (n_layers < 1 || n_layers > NPBNN_HOST_MAX_LAYERS || !out_dim || in_dim < 1 || n_rows < 1 || n_cu < 1) return -1;
+    return npbnn_wide_slice_room(n_layers, out_dim, in_dim, n_rows, n_cu);
 }

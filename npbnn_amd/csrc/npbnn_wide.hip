@@ -4,6 +4,7 @@
 // (MatrixMultiplicationD, np_bnn/BNN_lib.py:154-162; default n_nodes = [50, 5] on any number of features, np_bnn/BNN_env.py:20).
 #define NPBNN_KERNELS_WIDE
 #include "npbnn_ctx.hip.h"
+#include "npbnn_wide_plan.h"
 
 namespace npbnn_api {
 
@@ -31,26 +32,18 @@ GemmCfg g_cfg[6] = {
     {wide_gemm_kernel<2, 2, 4, 1, true, 1, 3>, wide_gemm_kernel<2, 2, 4, 1, false, 1, 3>, wide_gemm_kernel<2, 2, 4, 1, true, 2, 3>, wide_gemm_kernel<2, 2, 4, 1, false, 2, 3>, wide_gemm_kernel<2, 2, 4, 1, true, 3, 3>, wide_gemm_kernel<2, 2, 4, 1, false, 3, 3>, 8, 2, 256, 5, 3, 1},      // 128 x 32 : 20 KiB
     {wide_gemm_kernel<4, 4, 4, 4, true>, wide_gemm_kernel<4, 4, 4, 4, false>, nullptr, nullptr, nullptr, nullptr, 16, 16, 1024, 4, 2, 4},   // 256 x 256 on 16 waves (experiment: NPBNN_WIDE_CFG=5)
 };
-// the tiling of a layer: by its width; tables of few rows take the 128-row blocks (more workgroups)
-GemmCfg& cfg_for(int mt, int n_row_tiles, int n_cu) {
-    if (const char* e = getenv("NPBNN_WIDE_CFG")) { const int v = atoi(e); if (v >= 0 && v < 6) return g_cfg[v]; }
-    if (mt > 8) return g_cfg[0];
-    if (mt > 4) return g_cfg[1];
-    const bool few_rows = (n_row_tiles + 15) / 16 < n_cu / 2;
-    if (mt > 2) return few_rows ? g_cfg[3] : g_cfg[2];
-    return g_cfg[4];
+// the tiling of a layer and the K-slices of its product: npbnn_wide_plan.h (the rule the slice buffer is sized by - wide_plan)
+static_assert(kWideMaxSlices == NPBNN_WIDE_MAX_SLICES, "npbnn_wide_plan.h caps the K-slices as wide_gemm_kernel does");
+static_assert(sizeof(g_cfg) / sizeof(g_cfg[0]) == NPBNN_WIDE_N_CFG, "npbnn_wide_plan.h describes every tiling");
+GemmCfg& cfg_for(int mt, int n_row_tiles, int n_cu) { return g_cfg[npbnn_wide_cfg_index(mt, n_row_tiles, n_cu)]; }
+
+int slices_for(const GemmCfg& cf, int n_row_tiles, int mt, int units, int n_cu) {
+    return npbnn_wide_slices((int)(&cf - g_cfg), n_row_tiles, mt, units, n_cu);
 }
 
-// K-slices of a layer's product: while the blocks of the output do not fill the chip and a slice keeps a contraction worth its prologue
-int slices_for(const GemmCfg& cf, int n_row_tiles, int mt, int units, int n_cu) {
-    const int n_rb = (n_row_tiles + cf.xt - 1) / cf.xt, n_cb = (mt + cf.wt - 1) / cf.wt;
-    int n_sl = 1;
-    if (const char* e = getenv("NPBNN_WIDE_SLICES")) n_sl = atoi(e);
-    else while (n_sl < kWideMaxSlices && n_rb * n_cb * (n_sl + 1) <= n_cu && units / (n_sl + 1) >= 8) ++n_sl;
-    if (n_sl > kWideMaxSlices) n_sl = kWideMaxSlices;
-    if (n_sl > units) n_sl = units;
-    if (n_sl < 1) n_sl = 1;
-    return n_sl;
+// floats of the K-slices' sums a pass over `d` needs (npbnn_wide_plan.h)
+long long slice_room(const npbnn_ctx* ctx, const Dataset& d) {
+    return npbnn_wide_slice_room(ctx->arch.n_layers, ctx->arch.out_dim, ctx->arch.in_dim, d.n_rows, ctx->n_cu);
 }
 
 // the narrow layers from layer `l` on as wide_tail_layers takes them, or false when they are not narrow (or too large for `lds_budget` bytes)
@@ -179,6 +172,8 @@ bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
     bool fusable = a->n_layers >= 2 && a->out_dim[a->n_layers - 1] <= 128 && !lik_needs_row_scratch(a->lik_kind) &&
                    (a->lik_kind == NPBNN_LIK_CATEGORICAL || (a->lik_kind == NPBNN_LIK_GAUSS && a->n_targets <= kFuseTargets));
     for (int l = 1; l < a->n_layers; ++l) fusable = fusable && a->out_dim[l] <= 128;
+    // (the row count of the training matrix: npbnn_set_data rebuilds the net on a new one, so the path does not depend on whether
+    // the architecture or the data came first)
     if (!getenv("NPBNN_WIDE_MIN_WAVES") && fusable && a->out_dim[0] <= 32 && ctx->ds[0].X != nullptr && ctx->ds[0].n_rows >= 65536 && w < 8) w = 8;
     return resident_lds_bytes(ctx, a, f16, w) > ctx->lds_limit;
 }
@@ -188,12 +183,17 @@ void wide_free(npbnn_ctx* ctx) {
     for (int i = 0; i < 3; ++i)
         if (ctx->d_wide_act[i]) { (void)hipFree(ctx->d_wide_act[i]); ctx->d_wide_act[i] = nullptr; }
     ctx->wide_act_cap = 0;
+    ctx->wide_slice_cap = 0;
     if (ctx->d_wide_cs) { (void)hipFree(ctx->d_wide_cs); ctx->d_wide_cs = nullptr; }
     if (ctx->d_prep_terms) { (void)hipFree(ctx->d_prep_terms); ctx->d_prep_terms = nullptr; ctx->prep_cap = 0; }
 }
 
 // image layout, device images, packed weight -> image position map (called by rebuild_net after build_net has filled ctx->net)
 int wide_build(npbnn_ctx* ctx, bool f16) {
+    for (int i = 0; i < NPBNN_WIDE_N_CFG; ++i)      // (the slice buffer is sized by npbnn_wide_plan.h's copy of the tilings' blocks)
+        if (g_cfg[i].xt != npbnn_wide_cfg_xt[i] || g_cfg[i].wt != npbnn_wide_cfg_wt[i])
+            return fail(ctx, NPBNN_E_INTERNAL, "weight-streamed tiling %d: npbnn_wide_plan.h says %d x %d tiles, the launch table %d x %d (internal error)", i,
+                        npbnn_wide_cfg_xt[i], npbnn_wide_cfg_wt[i], g_cfg[i].xt, g_cfg[i].wt);
     const npbnn_arch& a = ctx->arch;
     WideMeta m{};
     m.n_layers = a.n_layers;
@@ -278,19 +278,23 @@ int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand) {
     int max_ld = 16;
     for (int l = 0; l < m.n_layers; ++l)
         if (16 * m.L[l].mt > max_ld) max_ld = 16 * m.L[l].mt;
+    // Both buffers grow to the demand of the table at hand and never shrink: a smaller table is cut into MORE K-slices (fewer row
+    // blocks to fill the chip with) and may take another tiling, so the slice buffer has a capacity of its own, not rows x slices of
+    // whichever table came first.
     const size_t need = (size_t)d.n_tiles * 16 * (size_t)max_ld;
     if (need > ctx->wide_act_cap) {
-        for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < 2; ++i)
             if (ctx->d_wide_act[i]) { (void)hipFree(ctx->d_wide_act[i]); ctx->d_wide_act[i] = nullptr; }
         ctx->wide_act_cap = 0;
         for (int i = 0; i < 2; ++i) HIP_TRY(ctx, hipMalloc(&ctx->d_wide_act[i], need * sizeof(float)));
-        int max_sl = 1;           // the K-slices' sums of a layer: room for the most any layer of this network is cut into on this table
-        for (int l = 0; l < m.n_layers; ++l) {
-            const int sl = slices_for(cfg_for(m.L[l].mt, d.n_tiles, ctx->n_cu), d.n_tiles, m.L[l].mt, m.L[l].units, ctx->n_cu);
-            if (sl > max_sl) max_sl = sl;
-        }
-        if (max_sl > 1) HIP_TRY(ctx, hipMalloc(&ctx->d_wide_act[2], need * sizeof(float) * max_sl));
         ctx->wide_act_cap = need;
+    }
+    const size_t room = (size_t)slice_room(ctx, d);      // the K-slices' sums: the most any layer writes on this table
+    if (room > ctx->wide_slice_cap) {
+        if (ctx->d_wide_act[2]) { (void)hipFree(ctx->d_wide_act[2]); ctx->d_wide_act[2] = nullptr; }
+        ctx->wide_slice_cap = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->d_wide_act[2], room * sizeof(float)));
+        ctx->wide_slice_cap = room;
     }
     if (m.L[0].f16 && !d.X16w) {        // the fp16-split copy in piece order
         Dataset* home = &d;
@@ -368,6 +372,9 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
                 t.out = ctx->d_wide_act[l & 1];
                 t.ldo = 16 * m.L[m.n_layers - 1].mt;
                 t.pass = pass;
+                if ((size_t)d.n_tiles * 16 * t.ldo > ctx->wide_act_cap)
+                    return fail(ctx, NPBNN_E_INTERNAL, "weight-streamed path: the tail on %lld rows needs %lld floats, the buffer holds %zu (internal error: planned for another table)",
+                                (long long)d.n_rows, (long long)d.n_tiles * 16 * t.ldo, ctx->wide_act_cap);
                 if (!tail_attr) {
                     HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(wide_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024 + 1024));
                     tail_attr = true;
@@ -439,11 +446,14 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
             attr = true;
         }
         const int n_rb = (d.n_tiles + cf.xt - 1) / cf.xt, n_cb = (L.mt + cf.wt - 1) / cf.wt;
-        int n_sl = slices_for(cf, d.n_tiles, L.mt, L.units, ctx->n_cu);
-        if (n_sl > 1 && !ctx->d_wide_act[2]) n_sl = 1;
+        const int n_sl = slices_for(cf, d.n_tiles, L.mt, L.units, ctx->n_cu);
         float* const layer_out = ctx->d_wide_act[l & 1];
         g.k_slices = n_sl;
         g.slice_stride = (long long)d.n_tiles * 16 * g.ldo;
+        // (what wide_plan sized for this table: a plan made for another table is an error here, not a write past the buffers)
+        if ((size_t)g.slice_stride > ctx->wide_act_cap || (n_sl > 1 && (size_t)g.slice_stride * n_sl > ctx->wide_slice_cap))
+            return fail(ctx, NPBNN_E_INTERNAL, "weight-streamed path: layer %d on %lld rows needs %lld floats x %d K-slices, the buffers hold %zu / %zu "
+                        "(internal error: planned for another table)", l, (long long)d.n_rows, g.slice_stride, n_sl, ctx->wide_act_cap, ctx->wide_slice_cap);
         if (n_sl > 1) g.out = ctx->d_wide_act[2];
         const int grid = (n_rb + 7) / 8 * 8 * n_cb * n_sl;
         hipLaunchKernelGGL(fn, dim3(grid), dim3(cf.threads), lds, st, g);
