@@ -180,7 +180,7 @@ enum { NPBNN_L0_AUTO = 0, NPBNN_L0_F32 = 1, NPBNN_L0_F16 = 2 };
 enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 3, NPBNN_INFO_FAST_TAILS = 4,
        NPBNN_INFO_TURN_NS_OVERLAPPED = 5, NPBNN_INFO_TURN_NS_BETWEEN = 6, NPBNN_INFO_MAX_CANDIDATES = 7,
        NPBNN_INFO_IT_NS_OVERLAPPED = 8, NPBNN_INFO_IT_NS_BETWEEN = 9, NPBNN_INFO_WIDE = 10,
-       NPBNN_INFO_F16_MOVED_COLUMNS = 11, NPBNN_INFO_F16_MAX_MOVE = 12 };
+       NPBNN_INFO_F16_MOVED_COLUMNS = 11, NPBNN_INFO_F16_MAX_MOVE = 12, NPBNN_INFO_PDP_ROUTE = 13 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -208,6 +208,18 @@ int npbnn_predict(npbnn_ctx* ctx, const double* W_packed, const double* act_prm,
  * :504-597, get_posterior_est :715-748), which copies and re-reads the feature matrix once per posterior sample. */
 int npbnn_predict_sets(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which, int apply_out_fn,
                        double* out_y);
+
+/* Partial dependence: replaces the loop over grid points and stored samples of get_pdp (np_bnn/BNN_pdp.py).  For each of n_grid
+ * points the focal columns (focal[n_focal]) read as grid[g][0..n_focal-1], then the columns col_override gives (in_dim entries,
+ * NaN = none: data_transform_obj, which applies after the grid values and so wins on a focal column) read as that constant.
+ * out_mean [n_grid][n_rows][out_dim]: per grid point and row, the prediction averaged over the n_sets stored weight vectors
+ * (W_sets and act_prm_sets as in npbnn_predict_sets).  NPBNN_INFO_PDP_ROUTE tells which route served the last call:
+ *   1  grid-batched kernel (networks on the LDS-resident path with narrow layers): one read of X per group of sets computes layer 0
+ *      with the focal columns at 0; each grid point adds its shift sum_f grid[g][f] * W0[:, f] and runs the later layers;
+ *   2  one pass of the evaluation kernels per (grid point, set), the grid values folded into layer 0's bias like col_override.
+ * Sums over the sets run in a fixed order (deterministic results).  NPBNN_PDP_PER_GRID=1 (environment) forces route 2. */
+int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, const int32_t* focal, int32_t n_focal,
+                      const double* grid, int32_t n_grid, const double* col_override, int which, int apply_out_fn, double* out_mean);
 
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events

@@ -30,6 +30,7 @@ INFO_L0_F16, INFO_WAVES_PER_BLOCK, INFO_N_CU, INFO_FAST_TAILS, INFO_TURN_NS_OVER
 INFO_IT_NS_OVERLAPPED, INFO_IT_NS_BETWEEN = 8, 9
 INFO_WIDE = 10
 INFO_F16_MOVED_COLUMNS, INFO_F16_MAX_MOVE = 11, 12
+INFO_PDP_ROUTE = 13
 E_RANGE = -6
 E_SYNC = -7
 E_INTERNAL = -8
@@ -132,6 +133,8 @@ SIGNATURES = {
                              C.POINTER(C.c_int64)]),
     "npbnn_predict": (C.c_int, [_P, _DP, _DP, _DP, C.c_int, C.c_int, _DP]),
     "npbnn_predict_sets": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, _DP]),
+    "npbnn_predict_pdp": (C.c_int, [_P, _DP, _DP, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _DP, C.c_int32, _DP, C.c_int,
+                                    C.c_int, _DP]),
     "npbnn_time_eval": (C.c_int, [_P, _DP, C.c_int, _DP, _DP]),
     "npbnn_time_pass": (C.c_int, [_P, _DP, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
     "npbnn_time_wide": (C.c_int, [_P, _DP, C.c_int, _DP, _DP, C.POINTER(C.c_int)]),

@@ -274,6 +274,25 @@ class HipContext:
                                                1 if apply_out_fn else 0, capi.dptr(out)))
         return out
 
+    def predict_pdp(self, weight_sets, focal, grid, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
+        """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
+        prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]
+        and then the columns ``col_override`` gives (NaN = none) to its constants.  NPBNN_INFO_PDP_ROUTE: the route taken."""
+        packed = capi.as_f64(np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel()
+                                       for w in weight_sets]))
+        n_sets = packed.shape[0]
+        ap = None
+        if act_prm_sets is not None and self.arch.n_layers > 1:
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        cols = np.ascontiguousarray(focal, dtype=np.int32).ravel()
+        g = capi.as_f64(np.asarray(grid, dtype=np.float64).reshape(-1, len(cols)))
+        co = None if col_override is None else capi.as_f64(np.asarray(col_override, dtype=np.float64).ravel())
+        out = np.empty((g.shape[0], self.n_rows[which], self.n_out), dtype=np.float64)
+        self._chk(self._lib.npbnn_predict_pdp(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets,
+                                              cols.ctypes.data_as(C.POINTER(C.c_int32)), len(cols), capi.dptr(g), g.shape[0],
+                                              capi.dptr(co), which, 1 if apply_out_fn else 0, capi.dptr(out)))
+        return out
+
     def time_eval(self, weights, iters=20):
         w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights)
         a, b = C.c_double(0), C.c_double(0)

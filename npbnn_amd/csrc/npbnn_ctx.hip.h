@@ -210,6 +210,7 @@ struct npbnn_ctx {
     hipStream_t stream_e[2] = {nullptr, nullptr};
     bool sync_failed = false;      // a wait timed out once: the schedule stays off for this context
     int debug_sync_skip = -1;      // npbnn_debug_sync_skip_ (diagnostics, not part of the ABI)
+    int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     npbnn_ctx* data_owner = nullptr;
     int n_borrowers = 0;
     bool zombie = false;
