@@ -2,6 +2,7 @@
 // functions each entry point replaces).  Host-side orchestration only: device buffers, launches,
 // the HIP stream of the chain.  No torch, no BLAS library, no CPU fallback for the numerics.
 #include <algorithm>
+#include <memory>
 #define NPBNN_KERNELS_MAIN
 #include "npbnn_ctx.hip.h"
 
@@ -22,9 +23,6 @@ int fail(npbnn_ctx* ctx, int code, const char* fmt, ...) {
 
 void free_dataset(Dataset& d) {
     if (d.X && !d.borrowed) (void)hipFree(d.X);
-    if (d.labels) (void)hipFree(d.labels);
-    if (d.targets) (void)hipFree(d.targets);
-    if (d.inst_w) (void)hipFree(d.inst_w);
     if (d.X16 && !d.borrowed) (void)hipFree(d.X16);
     if (d.X16w && !d.x16w_borrowed) (void)hipFree(d.X16w);
     d = Dataset();
@@ -292,21 +290,19 @@ eval_fn_t pick_kernel(const NetMeta& net, int n_cand) {
 // error is from its bounds - max(error / (2^-17 x mean |entry|), error / (2^-12 x typical |entry|)); <= 1 passes, 0 for an exact column.
 static int column_quality(npbnn_ctx* ctx, const Dataset& d, std::vector<double>* badness) {
     const int Fq = d.Fp;
-    unsigned* d_err = nullptr;
-    unsigned long long* d_sum = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d_err, (size_t)Fq * sizeof(unsigned)));
-    HIP_TRY(ctx, hipMalloc(&d_sum, (size_t)Fq * 3 * sizeof(unsigned long long)));
+    DevBuf<unsigned> d_err;
+    DevBuf<unsigned long long> d_sum;
+    if (int rc = d_err.reserve(ctx, (size_t)Fq)) return rc;
+    if (int rc = d_sum.reserve(ctx, (size_t)Fq * 3)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_err, 0, (size_t)Fq * sizeof(unsigned), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, (size_t)Fq * 3 * sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(split_quality_kernel, dim3((Fq + 255) / 256, (unsigned)((d.n_rows + 1023) / 1024)), dim3(256), 0, ctx->stream,
-                       (const float*)d.X, (long long)d.n_rows, d.Fp, (const float*)ctx->d_xscale, d_err, d_sum, d_sum + Fq, d_sum + 2 * (size_t)Fq);
+                       (const float*)d.X, (long long)d.n_rows, d.Fp, (const float*)ctx->d_xscale, d_err.get(), d_sum.get(), d_sum + Fq, d_sum + 2 * (size_t)Fq);
     std::vector<unsigned> h_err((size_t)Fq);
     std::vector<unsigned long long> h_sum((size_t)Fq * 3);
     HIP_TRY(ctx, hipMemcpyAsync(h_err.data(), d_err, h_err.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h_sum.data(), d_sum, h_sum.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_err);
-    (void)hipFree(d_sum);
     badness->assign((size_t)d.F, 0.0);
     for (int c = 0; c < d.F; ++c) {
         float e;
@@ -328,8 +324,8 @@ int ensure_scales(npbnn_ctx* ctx) {
     if (!tr.X) return fail(ctx, NPBNN_E_STATE, "the fp16-split path needs the training matrix first");
     if (ctx->d_xscale && ctx->scale_F == tr.F) return NPBNN_OK;
     const int Fp16 = round_up(tr.F, 32);
-    unsigned* d_max = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d_max, (size_t)Fp16 * sizeof(unsigned)));
+    DevBuf<unsigned> d_max;
+    if (int rc = d_max.reserve(ctx, (size_t)Fp16)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_max, 0, (size_t)Fp16 * sizeof(unsigned), ctx->stream));
     const int row_blocks = (int)((tr.n_rows + 1023) / 1024);
     hipLaunchKernelGGL(col_absmax_kernel, dim3((tr.Fp + 255) / 256, row_blocks), dim3(256), 0, ctx->stream, tr.X,
@@ -357,7 +353,7 @@ int ensure_scales(npbnn_ctx* ctx) {
     if (tr.f16_state == 0 && !getenv("NPBNN_F16_NO_SHIFT")) {
         std::vector<double> ratio;
         int rcq = column_quality(ctx, tr, &ratio);
-        if (rcq) { (void)hipFree(d_max); return rcq; }
+        if (rcq) return rcq;
         std::vector<int> shift((size_t)Fp16, 0);
         for (int c = 0; c < tr.F; ++c) {
             if (!(ratio[(size_t)c] > 1.0)) continue;
@@ -368,16 +364,14 @@ int ensure_scales(npbnn_ctx* ctx) {
             if (k > ctx->f16_max_shift) ctx->f16_max_shift = k;
         }
         if (ctx->f16_shifted_cols > 0) {
-            int* d_shift = nullptr;
-            HIP_TRY(ctx, hipMalloc(&d_shift, (size_t)Fp16 * sizeof(int)));
+            DevBuf<int> d_shift;
+            if (int rc = d_shift.reserve(ctx, (size_t)Fp16)) return rc;
             HIP_TRY(ctx, hipMemcpy(d_shift, shift.data(), (size_t)Fp16 * sizeof(int), hipMemcpyHostToDevice));
             hipLaunchKernelGGL(col_scale_kernel, dim3((Fp16 + 255) / 256), dim3(256), 0, ctx->stream, d_max, Fp16, ctx->d_xscale,
                                ctx->d_wscale, (const int*)d_shift);
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(d_shift);
         }
     }
-    (void)hipFree(d_max);
     return NPBNN_OK;
 }
 
@@ -399,7 +393,7 @@ int ensure_x16(npbnn_ctx* ctx, int which, int* usable) {
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), ctx->stream));
         const long long items = (long long)n_pad * (d.Fp16 / 8);
         hipLaunchKernelGGL(split_x_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, d.X, (long long)n_pad, d.Fp,
-                           d.Fp16, ctx->d_xscale, d.X16, reinterpret_cast<unsigned*>(ctx->d_overflow));
+                           d.Fp16, ctx->d_xscale, d.X16, reinterpret_cast<unsigned*>(ctx->d_overflow.get()));
         unsigned bits = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&bits, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -529,13 +523,7 @@ int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32, int wa
 }
 
 int ensure_work_buffers(npbnn_ctx* ctx, int n_waves) {
-    if (n_waves > ctx->partial_waves) {
-        if (ctx->d_partials) (void)hipFree(ctx->d_partials);
-        ctx->d_partials = nullptr;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_partials, (size_t)2 * kMaxCand * n_waves * kPartialStride * sizeof(double)));   // two pass parities
-        ctx->partial_waves = n_waves;
-    }
-    return NPBNN_OK;
+    return ctx->d_partials.reserve(ctx, (size_t)2 * kMaxCand * n_waves * kPartialStride);   // two pass parities
 }
 
 int stage_weights(npbnn_ctx* ctx, const double* W, const double* act_prm, const double* col_override) {
@@ -581,11 +569,10 @@ int push_chain_params(npbnn_ctx* ctx, const ChainParams& c) {
 
 // diagnostics (NPBNN_EVAL_STAMPS): what the evaluating workgroups of the last launch (or, in a persistent launch, of its last pass)
 // stamped - [grid][8] phases of wave 0, [grid][16] tile-loop ends per wave, [grid][8] prologue points (NPBNN_EXP_PROLOGUE_STAMPS builds).
-// first_wg: workgroups before it do not evaluate (the step workgroup of the flag-ordered schedules).  Frees the buffer.
-void report_eval_stamps(unsigned long long* d_stamps, int grid, int wpb, int first_wg) {
+// first_wg: workgroups before it do not evaluate (the step workgroup of the flag-ordered schedules).
+void report_eval_stamps(const DevBuf<unsigned long long>& stamps, int grid, int wpb, int first_wg) {
     std::vector<unsigned long long> hs((size_t)grid * 32);
-    (void)hipMemcpy(hs.data(), d_stamps, hs.size() * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_stamps);
+    (void)hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost);
     const int nwg = grid - first_wg;
     if (nwg < 1) return;
     if (getenv("NPBNN_EVAL_STAMPS") && atoi(getenv("NPBNN_EVAL_STAMPS")) >= 2) {
@@ -692,9 +679,9 @@ int check_dataset_for_lik(npbnn_ctx* ctx, const Dataset& d, int lik) {
 int rebuild_net(npbnn_ctx* ctx, bool f16) {
     int rc = build_net(ctx, &ctx->arch, f16);
     if (rc) return rc;
-    if (ctx->d_image) { (void)hipFree(ctx->d_image); ctx->d_image = nullptr; }
-    if (ctx->d_w2img) { (void)hipFree(ctx->d_w2img); ctx->d_w2img = nullptr; }
-    if (ctx->d_w2scale) { (void)hipFree(ctx->d_w2scale); ctx->d_w2scale = nullptr; }
+    ctx->d_image.reset();
+    ctx->d_w2img.reset();
+    ctx->d_w2scale.reset();
     if (ctx->wide) return wide_build(ctx, f16);
     wide_free(ctx);
     size_t lds = 0;
@@ -702,7 +689,7 @@ int rebuild_net(npbnn_ctx* ctx, bool f16) {
         return fail(ctx, NPBNN_E_ARG, "network too large: weight image of %d KiB does not fit the %zu KiB LDS of a CU",
                     ctx->net.image_floats * 4 / 1024, ctx->lds_limit / 1024);
     // (room for kMaxCand independent images: npbnn_predict_sets stages that many weight sets per pass)
-    HIP_TRY(ctx, hipMalloc(&ctx->d_image, (size_t)kMaxCand * ctx->net.image_floats * sizeof(float)));
+    if (int rc2 = ctx->d_image.reserve(ctx, (size_t)kMaxCand * ctx->net.image_floats)) return rc2;
     HIP_TRY(ctx, hipMemset(ctx->d_image, 0, (size_t)kMaxCand * ctx->net.image_floats * sizeof(float)));
     // where each packed weight lives in the image (bias column -> bias slot, else its MFMA fragment slot)
     std::vector<int> map((size_t)ctx->n_weights);
@@ -753,10 +740,10 @@ int rebuild_net(npbnn_ctx* ctx, bool f16) {
                 map[wi] = pos;
             }
     }
-    HIP_TRY(ctx, hipMalloc(&ctx->d_w2img, map.size() * sizeof(int)));
+    if (int rc2 = ctx->d_w2img.reserve(ctx, map.size())) return rc2;
     HIP_TRY(ctx, hipMemcpy(ctx->d_w2img, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
     if (f16) {
-        HIP_TRY(ctx, hipMalloc(&ctx->d_w2scale, scale.size() * sizeof(float)));
+        if (int rc2 = ctx->d_w2scale.reserve(ctx, scale.size())) return rc2;
         HIP_TRY(ctx, hipMemcpy(ctx->d_w2scale, scale.data(), scale.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return NPBNN_OK;
@@ -779,15 +766,9 @@ int launch_plain_eval(npbnn_ctx* ctx, const LaunchPlan& lp, int which) {
 
 // confusion counts: device and pinned host buffers for n_classes x n_classes
 int ensure_conf(npbnn_ctx* ctx, int n_classes) {
-    unsigned need = (unsigned)(n_classes < kResidentMaxWidth ? kResidentMaxWidth : n_classes);
-    if (need <= ctx->conf_cap) return NPBNN_OK;
-    if (ctx->d_conf) { (void)hipFree(ctx->d_conf); ctx->d_conf = nullptr; }
-    if (ctx->h_conf) { (void)hipHostFree(ctx->h_conf); ctx->h_conf = nullptr; }
-    ctx->conf_cap = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->d_conf, (size_t)need * need * sizeof(unsigned)));
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_conf, (size_t)need * need * sizeof(unsigned)));
-    ctx->conf_cap = need;
-    return NPBNN_OK;
+    const size_t need = (size_t)(n_classes < kResidentMaxWidth ? kResidentMaxWidth : n_classes);
+    if (int rc = ctx->d_conf.reserve(ctx, need * need)) return rc;
+    return ctx->h_conf.reserve(ctx, need * need);
 }
 
 void launch_finalize(npbnn_ctx* ctx) {
@@ -799,45 +780,13 @@ void launch_finalize(npbnn_ctx* ctx) {
 extern "C" void npbnn_set_global_error_(const char* msg) { g_last_error = msg ? msg : ""; }
 
 namespace npbnn_api {
+// the buffers go with the context (their destructors, the device current), its streams and events after them (npbnn_ctx_streams)
 void destroy_ctx(npbnn_ctx* c) {
     (void)hipSetDevice(c->device);
-    wide_free(c);
     free_dataset(c->ds[0]);
     free_dataset(c->ds[1]);
-    if (c->d_classw) (void)hipFree(c->d_classw);
-    if (c->d_wraw) (void)hipFree(c->d_wraw);
-    if (c->d_colov) (void)hipFree(c->d_colov);
     if (c->d_xscale) (void)hipFree(c->d_xscale);
     if (c->d_wscale) (void)hipFree(c->d_wscale);
-    if (c->d_overflow) (void)hipFree(c->d_overflow);
-    if (c->d_eparams) (void)hipFree(c->d_eparams);       // (d_fparams / d_cparams live in the same allocation)
-    if (c->d_xbuf) (void)hipFree(c->d_xbuf);
-    if (c->h_xbuf) (void)hipHostFree(c->h_xbuf);
-    if (c->ev_x) (void)hipEventDestroy(c->ev_x);
-    for (int i = 0; i < 2; ++i) {
-        if (c->stream_e[i]) (void)hipStreamDestroy(c->stream_e[i]);
-    }
-    if (c->h_params) (void)hipHostFree(c->h_params);
-    if (c->d_gparams) (void)hipFree(c->d_gparams);
-    if (c->h_gparams) (void)hipHostFree(c->h_gparams);
-    if (c->d_w2scale) (void)hipFree(c->d_w2scale);
-    if (c->d_image) (void)hipFree(c->d_image);
-    if (c->d_w2img) (void)hipFree(c->d_w2img);
-    if (c->d_partials) (void)hipFree(c->d_partials);
-    if (c->d_conf) (void)hipFree(c->d_conf);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_y) (void)hipFree(c->d_y);
-    if (c->h_w) (void)hipHostFree(c->h_w);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->h_conf) (void)hipHostFree(c->h_conf);
-    void* chain_bufs[] = {c->d_spec, c->d_spec_pv, c->d_spec_touch, c->d_spec_part, c->d_res, c->d_pv, c->d_mask, c->d_idx, c->d_pos, c->d_pscale, c->d_smult, c->d_hast, c->d_pscale_w, c->d_slopes, c->d_sidx, c->d_sdelta, c->d_shard_recv, c->d_shard_part};
-    for (void* b : chain_bufs)
-        if (b) (void)hipFree(b);
-    if (c->h_res) (void)hipHostFree(c->h_res);
-    if (c->h_shard) (void)hipHostFree(c->h_shard);
-    if (c->ev[0]) (void)hipEventDestroy(c->ev[0]);
-    if (c->ev[1]) (void)hipEventDestroy(c->ev[1]);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 }  // namespace npbnn_api
@@ -871,32 +820,24 @@ int npbnn_create(int device_id, npbnn_ctx** out) {
     HIP_TRY(nullptr, hipGetDeviceProperties(&prop, device_id));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(nullptr, NPBNN_E_ARG, "device %d is %s; this library is built for gfx950 (MI355X) only", device_id, prop.gcnArchName);
-    npbnn_ctx* c = new npbnn_ctx();
+    std::unique_ptr<npbnn_ctx> c(new npbnn_ctx());          // (a failure part-way frees what was made)
     c->device = device_id;
     c->n_cu = prop.multiProcessorCount;
     c->lds_limit = 160 * 1024;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&c->d_conf, (size_t)kResidentMaxWidth * kResidentMaxWidth * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&c->d_out, sizeof(npbnn_eval_out));
-    if (e == hipSuccess) e = hipMalloc(&c->d_overflow, sizeof(int));
+    HIP_TRY(nullptr, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIP_TRY(nullptr, hipEventCreate(&c->ev[0]));
+    HIP_TRY(nullptr, hipEventCreate(&c->ev[1]));
     // the kernels' parameter blocks: ONE device allocation laid out like its page-locked staging twin, so that a chain batch sends
     // all of them in one copy
-    if (e == hipSuccess) e = hipMalloc(&c->d_eparams, sizeof(EvalParams) + sizeof(FinalizeParams) + sizeof(ChainParams));
-    if (e == hipSuccess) {
-        c->d_fparams = reinterpret_cast<FinalizeParams*>(reinterpret_cast<char*>(c->d_eparams) + sizeof(EvalParams));
-        c->d_cparams = reinterpret_cast<ChainParams*>(reinterpret_cast<char*>(c->d_eparams) + sizeof(EvalParams) + sizeof(FinalizeParams));
-    }
-    if (e == hipSuccess) e = hipHostMalloc(&c->h_params, sizeof(EvalParams) + sizeof(FinalizeParams) + sizeof(ChainParams));
-    if (e == hipSuccess) e = hipHostMalloc(&c->h_out, sizeof(npbnn_eval_out));
-    if (e == hipSuccess) e = hipHostMalloc(&c->h_conf, (size_t)kResidentMaxWidth * kResidentMaxWidth * sizeof(unsigned));
-    if (e == hipSuccess) c->conf_cap = kResidentMaxWidth;
-    if (e == hipSuccess) e = hipEventCreate(&c->ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&c->ev[1]);
-    if (e != hipSuccess) {
-        npbnn_destroy(c);
-        return fail(nullptr, NPBNN_E_HIP, "context setup failed: %s", hipGetErrorString(e));
-    }
-    *out = c;
+    const size_t params_bytes = sizeof(EvalParams) + sizeof(FinalizeParams) + sizeof(ChainParams);
+    int rc;
+    if ((rc = ensure_conf(c.get(), kResidentMaxWidth)) || (rc = c->d_out.reserve(nullptr, 1)) || (rc = c->d_overflow.reserve(nullptr, 1)) ||
+        (rc = c->d_params.reserve(nullptr, params_bytes)) || (rc = c->h_params.reserve(nullptr, params_bytes)) || (rc = c->h_out.reserve(nullptr, 1)))
+        return rc;
+    c->d_eparams = reinterpret_cast<EvalParams*>(c->d_params.get());
+    c->d_fparams = reinterpret_cast<FinalizeParams*>(c->d_params + sizeof(EvalParams));
+    c->d_cparams = reinterpret_cast<ChainParams*>(c->d_params + sizeof(EvalParams) + sizeof(FinalizeParams));
+    *out = c.release();
     return NPBNN_OK;
 }
 
@@ -973,7 +914,8 @@ int npbnn_set_labels_i64(npbnn_ctx* ctx, const int64_t* y, int64_t n_rows, int w
         tmp[i] = (int)y[i];
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!d.labels) HIP_TRY(ctx, hipMalloc(&d.labels, n_pad * sizeof(int)));
+    rc = d.labels.reserve(ctx, n_pad);
+    if (rc) return rc;
     HIP_TRY(ctx, hipMemcpy(d.labels, tmp.data(), n_pad * sizeof(int), hipMemcpyHostToDevice));
     return NPBNN_OK;
 }
@@ -987,8 +929,9 @@ int npbnn_set_targets_f64(npbnn_ctx* ctx, const double* Y, int64_t n_rows, int32
     std::vector<float> tmp(n_pad * k, 0.0f);
     for (size_t i = 0; i < (size_t)n_rows * k; ++i) tmp[i] = (float)Y[i];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (d.targets && d.k != k) { (void)hipFree(d.targets); d.targets = nullptr; }
-    if (!d.targets) HIP_TRY(ctx, hipMalloc(&d.targets, n_pad * k * sizeof(float)));
+    if (d.k != k) d.targets.reset();
+    rc = d.targets.reserve(ctx, n_pad * k);
+    if (rc) return rc;
     d.k = k;
     HIP_TRY(ctx, hipMemcpy(d.targets, tmp.data(), n_pad * k * sizeof(float), hipMemcpyHostToDevice));
     return NPBNN_OK;
@@ -1004,15 +947,15 @@ int npbnn_set_row_weights(npbnn_ctx* ctx, const double* instance_w, int64_t n_ro
         const size_t n_pad = (size_t)d.n_tiles * 16;
         std::vector<float> tmp(n_pad, 0.0f);
         for (int64_t i = 0; i < n_rows; ++i) tmp[i] = (float)instance_w[i];
-        if (!d.inst_w) HIP_TRY(ctx, hipMalloc(&d.inst_w, n_pad * sizeof(float)));
+        rc = d.inst_w.reserve(ctx, n_pad);
+        if (rc) return rc;
         HIP_TRY(ctx, hipMemcpy(d.inst_w, tmp.data(), n_pad * sizeof(float), hipMemcpyHostToDevice));
-    } else if (d.inst_w) {
-        (void)hipFree(d.inst_w);
-        d.inst_w = nullptr;
+    } else {
+        d.inst_w.reset();
     }
     if (class_w) {
         if (n_classes < 1 || n_classes > NPBNN_MAX_WIDTH) return fail(ctx, NPBNN_E_ARG, "set_row_weights: n_classes=%d", n_classes);
-        if (!ctx->d_classw) HIP_TRY(ctx, hipMalloc(&ctx->d_classw, NPBNN_MAX_WIDTH * sizeof(double)));
+        if (int rc = ctx->d_classw.reserve(ctx, NPBNN_MAX_WIDTH)) return rc;
         HIP_TRY(ctx, hipMemcpy(ctx->d_classw, class_w, (size_t)n_classes * sizeof(double), hipMemcpyHostToDevice));
         ctx->n_classw = n_classes;
     } else {
@@ -1036,15 +979,16 @@ int npbnn_set_arch(npbnn_ctx* ctx, const npbnn_arch* arch) {
         ctx->arch = previous;
         return rc;
     }
-    if (ctx->d_wraw) { (void)hipFree(ctx->d_wraw); ctx->d_wraw = nullptr; }
-    if (ctx->d_colov) { (void)hipFree(ctx->d_colov); ctx->d_colov = nullptr; }
-    if (ctx->h_w) { (void)hipHostFree(ctx->h_w); ctx->h_w = nullptr; }
-    if (ctx->d_wcur) { (void)hipFree(ctx->d_wcur); ctx->d_wcur = nullptr; }
-    if (ctx->d_mask) { (void)hipFree(ctx->d_mask); ctx->d_mask = nullptr; }
-    if (ctx->d_pscale_w) { (void)hipFree(ctx->d_pscale_w); ctx->d_pscale_w = nullptr; }
-    HIP_TRY(ctx, hipMalloc(&ctx->d_wraw, (size_t)kMaxCand * ctx->n_weights * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_colov, (size_t)arch->in_dim * sizeof(double)));
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_w, ((size_t)ctx->n_weights + arch->in_dim) * sizeof(double)));
+    // buffers sized by the number of weights (or inputs); the device chain's result block is laid out again by its next batch
+    ctx->d_wraw.reset();
+    ctx->d_colov.reset();
+    ctx->h_w.reset();
+    ctx->d_mask.reset();
+    ctx->d_pscale_w.reset();
+    ctx->res_nw = 0;
+    if ((rc = ctx->d_wraw.reserve(ctx, (size_t)kMaxCand * ctx->n_weights))) return rc;
+    if ((rc = ctx->d_colov.reserve(ctx, (size_t)arch->in_dim))) return rc;
+    if ((rc = ctx->h_w.reserve(ctx, (size_t)ctx->n_weights + arch->in_dim))) return rc;
     ctx->arch_set = true;
     return NPBNN_OK;
 }
@@ -1245,13 +1189,7 @@ int npbnn_predict(npbnn_ctx* ctx, const double* W_packed, const double* act_prm,
     if (rc) return rc;
     rc = stage_weights(ctx, W_packed, act_prm, col_override);
     if (rc) return rc;
-    if (n_el > ctx->d_y_cap) {
-        if (ctx->d_y) (void)hipFree(ctx->d_y);
-        ctx->d_y = nullptr;
-        ctx->d_y_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_y, n_el * sizeof(float)));
-        ctx->d_y_cap = n_el;
-    }
+    if ((rc = ctx->d_y.reserve(ctx, n_el))) return rc;
     EvalParams p = make_params(ctx, d);
     p.labels = nullptr;
     p.targets = nullptr;
@@ -1289,13 +1227,7 @@ int npbnn_predict_sets(npbnn_ctx* ctx, const double* W_sets, const double* act_p
     const int n_act = ctx->net.n_layers - 1;
     const size_t per_set = (size_t)d.n_rows * C;
     const size_t wn = (size_t)ctx->n_weights;
-    if (kMaxCand * per_set > ctx->d_y_cap) {
-        if (ctx->d_y) (void)hipFree(ctx->d_y);
-        ctx->d_y = nullptr;
-        ctx->d_y_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_y, kMaxCand * per_set * sizeof(float)));
-        ctx->d_y_cap = kMaxCand * per_set;
-    }
+    if ((rc = ctx->d_y.reserve(ctx, kMaxCand * per_set))) return rc;
     std::vector<float> tmp(kMaxCand * per_set);
     std::vector<double> wstage(kMaxCand * wn);
     int s0 = 0;
@@ -1398,9 +1330,9 @@ int npbnn_time_pass(npbnn_ctx* ctx, const double* W_packed, int n_candidates, in
     p.pos = nullptr;
     p.pscale = nullptr;
     p.M = 0;
-    unsigned long long* d_stamps = nullptr;
+    DevBuf<unsigned long long> d_stamps;
     if (getenv("NPBNN_EVAL_STAMPS")) {      // diagnostics: per-phase wall-clock stamps of the last launch
-        HIP_TRY(ctx, hipMalloc(&d_stamps, (size_t)lp.grid * 32 * sizeof(unsigned long long)));     // [grid][8] wave 0 + [grid][16] per wave + [grid][8] prologue
+        if ((rc = d_stamps.reserve(ctx, (size_t)lp.grid * 32))) return rc;     // [grid][8] wave 0 + [grid][16] per wave + [grid][8] prologue
         HIP_TRY(ctx, hipMemset(d_stamps, 0, (size_t)lp.grid * 32 * sizeof(unsigned long long)));
         p.stamps = d_stamps;
     }

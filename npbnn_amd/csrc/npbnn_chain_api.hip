@@ -38,8 +38,8 @@ struct ChainBatch {
     bool make_cands = false;                   // weight-streamed path: the candidates are made between step and pass (ChainParams::prep_terms)
     size_t wb = 0;
     int launch = 0;                            // launches enqueued so far (overlapped schedule: the pass parity follows it)
-    unsigned long long* d_stamps = nullptr;    // diagnostics
-    unsigned long long* d_estamps = nullptr;   // diagnostics (NPBNN_EVAL_STAMPS: the evaluating workgroups' phases, last pass of the batch)
+    DevBuf<unsigned long long> d_stamps;       // diagnostics
+    DevBuf<unsigned long long> d_estamps;      // diagnostics (NPBNN_EVAL_STAMPS: the evaluating workgroups' phases, last pass of the batch)
     double tw0 = 0.0, tw1 = 0.0;
 };
 
@@ -242,14 +242,12 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
         size_t kc = (size_t)K > ctx->res_k ? (size_t)K : ctx->res_k;
         if (kc < kChainMinCapacity) kc = kChainMinCapacity;
         const ResLayout L = res_layout(kc, wb);
-        if (ctx->d_res) (void)hipFree(ctx->d_res);
-        if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-        if (ctx->d_mask) (void)hipFree(ctx->d_mask);        // sized by the number of weights as well
-        ctx->d_mask = nullptr;
-        ctx->d_res = nullptr; ctx->h_res = nullptr; ctx->res_cap = 0; ctx->res_k = 0; ctx->res_nw = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_res, L.total));
-        HIP_TRY(ctx, hipHostMalloc(&ctx->h_res, L.total));
-        ctx->res_cap = L.total; ctx->res_k = kc; ctx->res_nw = (size_t)ctx->n_weights;
+        ctx->d_res.reset();
+        ctx->h_res.reset();
+        ctx->d_mask.reset();        // sized by the number of weights as well
+        ctx->res_k = 0; ctx->res_nw = 0;
+        if ((rc = ctx->d_res.reserve(ctx, L.total)) || (rc = ctx->h_res.reserve(ctx, L.total))) return rc;
+        ctx->res_k = kc; ctx->res_nw = (size_t)ctx->n_weights;
         char* b = ctx->d_res;
         ctx->d_chain = reinterpret_cast<ChainDev*>(b);
         ctx->d_chain_ovf = reinterpret_cast<int*>(b + 448);
@@ -262,54 +260,32 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
     }
     const ResLayout RL = res_layout(ctx->res_k, wb);
     static_assert(sizeof(ChainDev) <= 448, "ChainDev must fit its slot of the result block");
-    if (mask_packed && !ctx->d_mask) HIP_TRY(ctx, hipMalloc(&ctx->d_mask, wb));
-    if ((size_t)M > ctx->pv_cap) {
-        if (ctx->d_pv) (void)hipFree(ctx->d_pv);
-        ctx->d_pv = nullptr; ctx->pv_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_pv, (size_t)2 * kMaxCand * M * sizeof(double)));
-        ctx->pv_cap = (size_t)M;
-    }
+    if (mask_packed && (rc = ctx->d_mask.reserve(ctx, (size_t)ctx->n_weights))) return rc;
+    if ((rc = ctx->d_pv.reserve(ctx, (size_t)2 * kMaxCand * M))) return rc;
     const bool spec = pserial;             // (every condition was checked where the schedule was fixed)
     if (spec) lp.fn = lp.fn_spec;          // (the builds that carry spec_rounds)      // prepare the next pass ahead for every outcome
     if (spec) {
-        if (!ctx->d_spec) HIP_TRY(ctx, hipMalloc(&ctx->d_spec, sizeof(SpecState)));
-        if ((size_t)M > ctx->spec_pv_cap) {
-            if (ctx->d_spec_pv) (void)hipFree(ctx->d_spec_pv);
-            ctx->d_spec_pv = nullptr; ctx->spec_pv_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_spec_pv, (size_t)3 * kSpecOutcomes * kMaxCand * M * sizeof(double)));
-            ctx->spec_pv_cap = (size_t)M;
-        }
-        if ((size_t)ctx->n_weights > ctx->spec_touch_cap) {
-            if (ctx->d_spec_touch) (void)hipFree(ctx->d_spec_touch);
-            ctx->d_spec_touch = nullptr; ctx->spec_touch_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_spec_touch, (size_t)kMaxCand * ctx->n_weights * 4 * sizeof(unsigned)));
-            ctx->spec_touch_cap = (size_t)ctx->n_weights;
-            ctx->spec_gen = 0xf0000000u;         // (forces the clearing below)
-        }
-        const size_t part_bytes = (size_t)2 * kMaxCand * kPartialStride * kSpecPartSlots * 2 * sizeof(unsigned long long);
-        if (!ctx->d_spec_part) {
-            HIP_TRY(ctx, hipMalloc(&ctx->d_spec_part, part_bytes));
-            ctx->spec_gen = 0xf0000000u;         // (cleared below)
-        }
+        bool touch_new = false, part_new = false;
+        if ((rc = ctx->d_spec.reserve(ctx, 1)) || (rc = ctx->d_spec_pv.reserve(ctx, (size_t)3 * kSpecOutcomes * kMaxCand * M)) ||
+            (rc = ctx->d_spec_touch.reserve(ctx, (size_t)kMaxCand * ctx->n_weights * 4, 0, &touch_new)) ||
+            (rc = ctx->d_spec_part.reserve(ctx, (size_t)2 * kMaxCand * kPartialStride * kSpecPartSlots * 2, 0, &part_new)))
+            return rc;
+        if (touch_new || part_new) ctx->spec_gen = 0xf0000000u;         // (forces the clearing below)
         if (ctx->spec_gen + (unsigned)K + 8u >= 0xf0000000u) {   // the batch's pass tags (one per pass, at most K + 1 passes) could repeat
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_spec_touch, 0, (size_t)kMaxCand * ctx->spec_touch_cap * 4 * sizeof(unsigned), ctx->stream));
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_spec_part, 0, part_bytes, ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_spec_touch, 0, ctx->d_spec_touch.size() * sizeof(unsigned), ctx->stream));
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_spec_part, 0, ctx->d_spec_part.size() * sizeof(unsigned long long), ctx->stream));
             ctx->spec_gen = 0;
         }
     }
     const size_t need = (size_t)K * M;
-    if (need > ctx->draw_cap) {
+    {   // room for K x M draws, and when it grows, for at least kChainMinCapacity iterations of M
         const size_t cap = need > (size_t)kChainMinCapacity * M ? need : (size_t)kChainMinCapacity * M;
-        if (ctx->d_idx) (void)hipFree(ctx->d_idx);          // (d_delta lives behind it)
-        if (ctx->d_pos) (void)hipFree(ctx->d_pos);
-        if (ctx->d_pscale) (void)hipFree(ctx->d_pscale);
-        ctx->d_idx = nullptr; ctx->d_delta = nullptr; ctx->d_pos = nullptr; ctx->d_pscale = nullptr; ctx->draw_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_idx, cap * (sizeof(int) + sizeof(double)) + 512));     // (indices, then the deviates: see below)
-        HIP_TRY(ctx, hipMalloc(&ctx->d_pos, cap * sizeof(int)));
-        HIP_TRY(ctx, hipMalloc(&ctx->d_pscale, cap * sizeof(float)));
-        ctx->draw_cap = cap;
+        const auto idx_ints = [](size_t n) { return (n * (sizeof(int) + sizeof(double)) + 512) / sizeof(int); };   // (indices, then the deviates: see below)
+        if ((rc = ctx->d_idx.reserve(ctx, idx_ints(need), idx_ints(cap))) || (rc = ctx->d_pos.reserve(ctx, need, cap)) ||
+            (rc = ctx->d_pscale.reserve(ctx, need, cap)))
+            return rc;
     }
-    ctx->d_delta = reinterpret_cast<double*>(reinterpret_cast<char*>(ctx->d_idx) + ((size_t)K * M * sizeof(int) + 255) / 256 * 256);
+    ctx->d_delta = reinterpret_cast<double*>(reinterpret_cast<char*>(ctx->d_idx.get()) + ((size_t)K * M * sizeof(int) + 255) / 256 * 256);
     hipStream_t st = ctx->stream;
     double t_stage = wall_us();
     stage_mark(ctx, "(host set-up so far)", &t_stage);
@@ -372,15 +348,9 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
         if (!cfg->sigma_mult || !cfg->hastings || lik != NPBNN_LIK_GAUSS)
             return fail(ctx, NPBNN_E_ARG, "chain_run: sigma_mult and hastings go together, with the Gaussian likelihood");
         const int kt = ctx->net.k_targets;
-        if ((size_t)K > ctx->smult_cap) {
-            if (ctx->d_smult) (void)hipFree(ctx->d_smult);
-            if (ctx->d_hast) (void)hipFree(ctx->d_hast);
-            ctx->d_smult = nullptr; ctx->d_hast = nullptr; ctx->smult_cap = 0;
-            const size_t cap = (size_t)K > kChainMinCapacity ? (size_t)K : kChainMinCapacity;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_smult, cap * NPBNN_MAX_TARGETS * sizeof(double)));
-            HIP_TRY(ctx, hipMalloc(&ctx->d_hast, cap * sizeof(double)));
-            ctx->smult_cap = cap;
-        }
+        const size_t cap = (size_t)K > kChainMinCapacity ? (size_t)K : kChainMinCapacity;
+        if ((rc = ctx->d_smult.reserve(ctx, (size_t)K * NPBNN_MAX_TARGETS, cap * NPBNN_MAX_TARGETS)) || (rc = ctx->d_hast.reserve(ctx, (size_t)K, cap)))
+            return rc;
         for (size_t i = 0; i < (size_t)K * kt; ++i)
             if (!(cfg->sigma_mult[i] > 0.0)) return fail(ctx, NPBNN_E_ARG, "chain_run: sigma_mult[%zu] is not positive", i);
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_smult, cfg->sigma_mult, (size_t)K * kt * sizeof(double), hipMemcpyHostToDevice, st));
@@ -402,13 +372,7 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
     c.prep_terms = nullptr;
     B->make_cands = false;
     if (lp.wide && !c.cand_image && seg_len == 0 && !cfg->slope_idx && !getenv("NPBNN_WIDE_STEP_MAKES")) {
-        const size_t need_terms = (size_t)kMaxCand * M;
-        if (need_terms > ctx->prep_cap) {
-            if (ctx->d_prep_terms) (void)hipFree(ctx->d_prep_terms);
-            ctx->d_prep_terms = nullptr; ctx->prep_cap = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_prep_terms, need_terms * sizeof(double)));
-            ctx->prep_cap = need_terms;
-        }
+        if ((rc = ctx->d_prep_terms.reserve(ctx, (size_t)kMaxCand * M))) return rc;
         c.prep_terms = ctx->d_prep_terms;
         B->make_cands = true;
     }
@@ -430,9 +394,8 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
         ctx->spec_gen += (unsigned)K + 8u;             // (a pass decides at least one iteration)
     }
     c.overflow = ctx->d_chain_ovf;
-    B->d_stamps = nullptr;
     if (getenv("NPBNN_STEP_STAMPS")) {      // diagnostics: per-phase wall-clock stamps of the step kernel
-        HIP_TRY(ctx, hipMalloc(&B->d_stamps, 1024 * 8 * sizeof(unsigned long long)));
+        if ((rc = B->d_stamps.reserve(ctx, 1024 * 8))) return rc;
         HIP_TRY(ctx, hipMemset(B->d_stamps, 0, 1024 * 8 * sizeof(unsigned long long)));
     }
     c.stamps = B->d_stamps;
@@ -455,7 +418,7 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
     if (cfg->prior_scale_w && cfg->prior_kind != NPBNN_PRIOR_UNIFORM) {
         for (int i = 0; i < ctx->n_weights; ++i)
             if (!(cfg->prior_scale_w[i] > 0.0)) return fail(ctx, NPBNN_E_ARG, "chain_run: prior_scale_w[%d] is not positive", i);
-        if (!ctx->d_pscale_w) HIP_TRY(ctx, hipMalloc(&ctx->d_pscale_w, wb));
+        if ((rc = ctx->d_pscale_w.reserve(ctx, (size_t)ctx->n_weights))) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pscale_w, cfg->prior_scale_w, wb, hipMemcpyHostToDevice, st));
         c.prior_scale_w = ctx->d_pscale_w;
     }
@@ -473,16 +436,9 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
         if (seg_len > 0 || group_blocks > 0) return fail(ctx, NPBNN_E_ARG, "chain_run: trainable slopes run in plain batches only");
         for (int t = 0; t < K; ++t)
             if (cfg->slope_idx[t] < 0 || cfg->slope_idx[t] >= cfg->n_slopes) return fail(ctx, NPBNN_E_ARG, "chain_run: slope_idx[%d] out of range", t);
-        if ((size_t)K > ctx->slope_cap) {
-            if (ctx->d_sidx) (void)hipFree(ctx->d_sidx);
-            if (ctx->d_sdelta) (void)hipFree(ctx->d_sdelta);
-            ctx->d_sidx = nullptr; ctx->d_sdelta = nullptr; ctx->slope_cap = 0;
-            const size_t cap = (size_t)K > kChainMinCapacity ? (size_t)K : kChainMinCapacity;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_sidx, cap * sizeof(int)));
-            HIP_TRY(ctx, hipMalloc(&ctx->d_sdelta, cap * sizeof(double)));
-            ctx->slope_cap = cap;
-        }
-        if (!ctx->d_slopes) HIP_TRY(ctx, hipMalloc(&ctx->d_slopes, sizeof(SlopeState)));
+        const size_t cap = (size_t)K > kChainMinCapacity ? (size_t)K : kChainMinCapacity;
+        if ((rc = ctx->d_sidx.reserve(ctx, (size_t)K, cap)) || (rc = ctx->d_sdelta.reserve(ctx, (size_t)K, cap)) || (rc = ctx->d_slopes.reserve(ctx, 1)))
+            return rc;
         SlopeState init_s{};
         for (int l = 0; l < cfg->n_slopes; ++l) init_s.cur[l] = cfg->cur_slopes[l];
         // (pageable sources: the copies are staged by the runtime before the calls return)
@@ -508,7 +464,7 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
     p.use_classw = ctx->n_classw > 0 ? 1 : 0;
     p.has_pass = 1;
     if (getenv("NPBNN_EVAL_STAMPS") && group_blocks == 0) {
-        HIP_TRY(ctx, hipMalloc(&B->d_estamps, (size_t)(lp.grid + 1) * 32 * sizeof(unsigned long long)));
+        if ((rc = B->d_estamps.reserve(ctx, (size_t)(lp.grid + 1) * 32))) return rc;
         HIP_TRY(ctx, hipMemset(B->d_estamps, 0, (size_t)(lp.grid + 1) * 32 * sizeof(unsigned long long)));
         p.stamps = B->d_estamps;
     }
@@ -655,15 +611,13 @@ int chain_enqueue(npbnn_ctx* ctx, ChainBatch& B, int n) {
 // after the result block has come back (h_res): hand the first k_take iterations' outcome to the caller
 int chain_finish(npbnn_ctx* ctx, ChainBatch& B, const npbnn_chain_cfg* cfg, double* W_inout, uint8_t* out_accepted, double* out_loglik_prop,
                  double* out_logprior_prop, npbnn_chain_result* result, int k_take, bool exchange_run = false) {
-    const ChainDev fin = *reinterpret_cast<const ChainDev*>(ctx->h_res);
+    const ChainDev fin = *reinterpret_cast<const ChainDev*>(ctx->h_res.get());
     if (fin.n_passes + fin.n_void > 0 && k_take > 0) ctx->its_per_pass = (double)k_take / (fin.n_passes + fin.n_void);
     ctx->last_schedule = B.schedule;
     if (k_take > 0) ctx->accept_rate = (double)fin.n_accepted / k_take;
     if (B.d_stamps) {
         std::vector<unsigned long long> hs(1024 * 8);
         (void)hipMemcpy(hs.data(), B.d_stamps, hs.size() * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(B.d_stamps);
-        B.d_stamps = nullptr;
         double acc[8] = {0};
         int n = 0;
         for (int r = 1; r < 1024; ++r) {
@@ -698,10 +652,7 @@ int chain_finish(npbnn_ctx* ctx, ChainBatch& B, const npbnn_chain_cfg* cfg, doub
             if (m) fprintf(stderr, "[npbnn step stamps] step start -> next step start %.2f us, of which between steps %.2f us (mean of %d)\n", period / m, idle / m, m);
         }
     }
-    if (B.d_estamps) {
-        report_eval_stamps(B.d_estamps, B.lp.grid + (B.overlap ? 1 : 0), B.lp.wpb, (B.sync || B.persist) ? 1 : 0);
-        B.d_estamps = nullptr;
-    }
+    if (B.d_estamps) report_eval_stamps(B.d_estamps, B.lp.grid + (B.overlap ? 1 : 0), B.lp.wpb, (B.sync || B.persist) ? 1 : 0);
     const int flags = *reinterpret_cast<const int*>(ctx->h_res + 448);
     if (flags & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "chain_run: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is");
     if (flags & kFlagBadIndex) return fail(ctx, NPBNN_E_ARG, "chain_run: a weight index of the batch is outside 0 .. %d (the entry was ignored)", ctx->n_weights - 1);
@@ -750,7 +701,7 @@ int npbnn_chain_run(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, double* W_inout,
     if (rc) return rc;
     hipStream_t st = ctx->stream;
     int t_done = 0, n_rounds = 0;
-    const ChainDev* now = reinterpret_cast<const ChainDev*>(ctx->h_res);
+    const ChainDev* now = reinterpret_cast<const ChainDev*>(ctx->h_res.get());
     while (t_done < K) {       // launch the least number of passes that can finish, look at the counter, repeat if short
         ++n_rounds;
         const double ta = timing ? wall_us() : 0.0;
@@ -773,7 +724,7 @@ int npbnn_chain_run(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, double* W_inout,
         if (timing) {
             const double tc = wall_us();
             fprintf(stderr, "[npbnn chain timing]   round %d: %d launches enqueued in %.0f us, waited %.0f us, t=%d of %d\n", n_rounds, n_launch, tb - ta,
-                    tc - tb, reinterpret_cast<const ChainDev*>(ctx->h_res)->t, K);
+                    tc - tb, reinterpret_cast<const ChainDev*>(ctx->h_res.get())->t, K);
         }
         if (now->aborted) {         // a device-side wait of the flag-ordered schedule timed out: nothing was decided after it
             ctx->sync_failed = true;
@@ -880,10 +831,7 @@ int npbnn_chains_run_batched(npbnn_chain_job* jobs, int32_t n_jobs, int32_t K) {
         HIP_TRY(c, hipEventRecord(c->ev_x, c->stream));
         HIP_TRY(ctx0, hipStreamWaitEvent(st, c->ev_x, 0));
     }
-    if (!ctx0->d_gparams) {
-        HIP_TRY(ctx0, hipMalloc(&ctx0->d_gparams, sizeof(EvalParams)));
-        HIP_TRY(ctx0, hipHostMalloc(&ctx0->h_gparams, sizeof(EvalParams)));
-    }
+    if ((rc = ctx0->d_gparams.reserve(ctx0, 1)) || (rc = ctx0->h_gparams.reserve(ctx0, 1))) return rc;
     {
         EvalParams g = make_params(ctx0, d0);
         g.partials = nullptr;
@@ -931,7 +879,7 @@ int npbnn_chains_run_batched(npbnn_chain_job* jobs, int32_t n_jobs, int32_t K) {
         }
         HIP_TRY(ctx0, hipStreamSynchronize(st));
         for (int q = 0; q < n_jobs; ++q) {
-            const ChainDev* now = reinterpret_cast<const ChainDev*>(jobs[q].ctx->h_res);
+            const ChainDev* now = reinterpret_cast<const ChainDev*>(jobs[q].ctx->h_res.get());
             if (now->t < t_done[q]) return fail(jobs[q].ctx, NPBNN_E_STATE, "chains_run_batched: chain %d went backwards (t=%d)", q, now->t);
             t_done[q] = now->t;
         }
@@ -997,15 +945,9 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
         L.cold = L.rec + (q == 0 ? up256(rec_bytes) : 0);
         L.total = L.cold + (jobs[q].out_cold_w ? up256((size_t)n_seg * ctx->n_weights * sizeof(double)) : 0);
         static_assert(sizeof(ExchangeParams) <= 256, "ExchangeParams must fit its slot");
-        if (L.total > ctx->xbuf_cap) {
-            if (ctx->d_xbuf) (void)hipFree(ctx->d_xbuf);
-            if (ctx->h_xbuf) (void)hipHostFree(ctx->h_xbuf);
-            ctx->d_xbuf = nullptr; ctx->h_xbuf = nullptr; ctx->xbuf_cap = 0;
-            const size_t cap = L.total + L.total / 2;
-            HIP_TRY(ctx, hipMalloc(&ctx->d_xbuf, cap));
-            HIP_TRY(ctx, hipHostMalloc(&ctx->h_xbuf, cap));
-            ctx->xbuf_cap = cap;
-        }
+        int rc = ctx->d_xbuf.reserve(ctx, L.total, L.total + L.total / 2);
+        if (!rc) rc = ctx->h_xbuf.reserve(ctx, L.total, L.total + L.total / 2);
+        if (rc) return rc;
         if (!ctx->ev_x) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_x, hipEventDisableTiming));
         return NPBNN_OK;
     };
@@ -1093,7 +1035,7 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
             // synchronisation, no stream events.
             xs[q] = B[q].sync ? ctx->stream_e[(B[q].launch - 1) & 1] : ctx->stream;
             hipLaunchKernelGGL(exchange_pack_kernel, dim3(1), dim3(64), 0, xs[q], (const ChainParams*)ctx->d_cparams,
-                               (const ExchangeParams*)ctx->d_xbuf, s);
+                               (const ExchangeParams*)ctx->d_xbuf.get(), s);
             if (q > 0) {
                 HIP_TRY(ctx, hipEventRecord(ctx->ev_x, ctx->stream));
                 HIP_TRY(ctx0, hipStreamWaitEvent(ctx0->stream, ctx->ev_x, 0));
@@ -1115,7 +1057,7 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
         for (int q = 0; q < n_jobs; ++q) {
             npbnn_ctx* ctx = jobs[q].ctx;
             hipLaunchKernelGGL(exchange_apply_kernel, dim3(1), dim3(1024), 0, xs[q], (const ChainParams*)ctx->d_cparams,
-                               (const ExchangeParams*)ctx->d_xbuf, s, B[q].launch, B[q].overlap ? 1 : 0);
+                               (const ExchangeParams*)ctx->d_xbuf.get(), s, B[q].launch, B[q].overlap ? 1 : 0);
             if (B[q].sync && s + 1 < n_seg)
                 hipLaunchKernelGGL(sync_gate_exchanged_kernel, dim3(1), dim3(64), 0, ctx->stream_e[B[q].launch & 1], ctx->d_chain, s + 1);
         }
@@ -1144,7 +1086,7 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
     }
     int seg_done = -1;
     for (int q = 0; q < n_jobs; ++q) {
-        const ChainDev* fin = reinterpret_cast<const ChainDev*>(jobs[q].ctx->h_res);
+        const ChainDev* fin = reinterpret_cast<const ChainDev*>(jobs[q].ctx->h_res.get());
         if (fin->aborted) jobs[q].ctx->sync_failed = true;     // (the chain stopped at a valid state; the records show it as short)
         if (seg_done < 0) seg_done = fin->seg_idx;
         if (fin->seg_idx != seg_done) return fail(ctx0, NPBNN_E_STATE, "chains_run_exchange: chains disagree on the exchanges done (%d, %d)", seg_done, fin->seg_idx);
@@ -1153,7 +1095,7 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
     for (int q = 0; q < n_jobs; ++q) {
         const npbnn_chain_job& J = jobs[q];
         npbnn_ctx* ctx = J.ctx;
-        const ChainDev* fin = reinterpret_cast<const ChainDev*>(ctx->h_res);
+        const ChainDev* fin = reinterpret_cast<const ChainDev*>(ctx->h_res.get());
         int rc = chain_finish(ctx, B[q], J.cfg, J.W_inout, J.out_accepted, J.out_loglik_prop, J.out_logprior_prop, J.result, fin->t, true);
         if (rc) return rc;
         if (J.out_state) memcpy(J.out_state, ctx->h_xbuf + XL[q].state, (size_t)n_seg * NPBNN_XSTATE_DOUBLES * sizeof(double));
@@ -1193,14 +1135,15 @@ int npbnn_set_row_shard(npbnn_ctx* ctx, npbnn_comm* comm, npbnn_gather_fn gather
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const size_t rec = (size_t)kMaxCand * kPartialStride;
-    if (ctx->d_shard_recv) { (void)hipFree(ctx->d_shard_recv); ctx->d_shard_recv = nullptr; }
-    if (ctx->d_shard_part) { (void)hipFree(ctx->d_shard_part); ctx->d_shard_part = nullptr; }
-    if (ctx->h_shard) { (void)hipHostFree(ctx->h_shard); ctx->h_shard = nullptr; }
-    HIP_TRY(ctx, hipMalloc(&ctx->d_shard_recv, rec * n_ranks * sizeof(double)));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_shard_part, rec * n_ranks * sizeof(double)));
+    ctx->d_shard_recv.reset();
+    ctx->d_shard_part.reset();
+    ctx->h_shard.reset();
+    int rc = ctx->d_shard_recv.reserve(ctx, rec * n_ranks);
+    if (!rc) rc = ctx->d_shard_part.reserve(ctx, rec * n_ranks);
+    if (rc) return rc;
     HIP_TRY(ctx, hipMemset(ctx->d_shard_recv, 0, rec * n_ranks * sizeof(double)));       // (values not in use stay zero)
     HIP_TRY(ctx, hipMemset(ctx->d_shard_part, 0, rec * n_ranks * sizeof(double)));
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_shard, rec * (n_ranks + 1) * sizeof(double)));
+    if ((rc = ctx->h_shard.reserve(ctx, rec * (n_ranks + 1)))) return rc;
     memset(ctx->h_shard, 0, rec * (n_ranks + 1) * sizeof(double));
     ctx->shard_n = n_ranks;
     ctx->shard_rank = rank;

@@ -14,6 +14,7 @@
 #include <string>
 #include <thread>
 
+#include "npbnn_buf.hip.h"
 #include "npbnn_hip.h"
 
 extern "C" void npbnn_set_global_error_(const char* msg);
@@ -22,9 +23,7 @@ struct npbnn_comm {
     int device = 0, rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;
     hipStream_t stream = nullptr;
-    void* d_send = nullptr;
-    void* d_recv = nullptr;
-    size_t cap_send = 0, cap_recv = 0;
+    npbnn_api::DevBuf<char> d_send, d_recv;
     bool dead = false;          // aborted after a failure in the middle of an exchange run: every later call fails at once
 };
 
@@ -52,19 +51,8 @@ int cfail(int code, const char* fmt, ...) {
     } while (0)
 
 int ensure(npbnn_comm* c, size_t send_bytes, size_t recv_bytes) {
-    if (send_bytes > c->cap_send) {
-        if (c->d_send) (void)hipFree(c->d_send);
-        c->d_send = nullptr;
-        C_HIP(hipMalloc(&c->d_send, send_bytes));
-        c->cap_send = send_bytes;
-    }
-    if (recv_bytes > c->cap_recv) {
-        if (c->d_recv) (void)hipFree(c->d_recv);
-        c->d_recv = nullptr;
-        C_HIP(hipMalloc(&c->d_recv, recv_bytes));
-        c->cap_recv = recv_bytes;
-    }
-    return NPBNN_OK;
+    if (int rc = c->d_send.reserve(nullptr, send_bytes)) return rc;
+    return c->d_recv.reserve(nullptr, recv_bytes);
 }
 
 // A collective whose peer has died never completes, and hipStreamSynchronize on it never returns.  Every host-side wait on a stream
@@ -252,8 +240,8 @@ void npbnn_comm_destroy(npbnn_comm* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->comm) (void)ncclCommDestroy(c->comm);
-    if (c->d_send) (void)hipFree(c->d_send);
-    if (c->d_recv) (void)hipFree(c->d_recv);
+    c->d_send.reset();
+    c->d_recv.reset();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }

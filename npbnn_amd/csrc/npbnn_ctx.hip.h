@@ -10,13 +10,17 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <set>
 #include <string>
 #include <vector>
 
+#include "npbnn_buf.hip.h"
 #include "npbnn_hip.h"
 #include "npbnn_kernels.hip.h"
 
 using namespace npbnn;
+using npbnn_api::DevBuf;
+using npbnn_api::PinnedBuf;
 
 // the evaluation-kernel instantiations live in npbnn_eval_inst_*.hip (compiled in parallel)
 namespace npbnn {
@@ -68,9 +72,9 @@ namespace npbnn_api {
 
 struct Dataset {
     float* X = nullptr;
-    int* labels = nullptr;
-    float* targets = nullptr;
-    float* inst_w = nullptr;
+    DevBuf<int> labels;
+    DevBuf<float> targets;
+    DevBuf<float> inst_w;
     int64_t n_rows = 0;
     int n_tiles = 0;
     int F = 0, Fp = 0, k = 0;
@@ -88,14 +92,30 @@ struct Dataset {
 }  // namespace npbnn_api
 using npbnn_api::Dataset;
 
-struct npbnn_ctx {
+// The streams and events of a context.  A base of npbnn_ctx: they are destroyed after every buffer the context owns.
+struct npbnn_ctx_streams {
+    hipStream_t stream = nullptr;
+    hipStream_t stream_e[2] = {nullptr, nullptr};   // flag-ordered overlapped chain schedule: the launches alternate between these two
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipEvent_t ev_x = nullptr;
+    npbnn_ctx_streams() = default;
+    npbnn_ctx_streams(const npbnn_ctx_streams&) = delete;
+    npbnn_ctx_streams& operator=(const npbnn_ctx_streams&) = delete;
+    ~npbnn_ctx_streams() {
+        for (hipEvent_t e : {ev_x, ev[0], ev[1]})
+            if (e) (void)hipEventDestroy(e);
+        for (hipStream_t s : {stream_e[0], stream_e[1], stream})
+            if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+struct npbnn_ctx : npbnn_ctx_streams {
     int device = 0;
     int n_cu = 256;
     size_t lds_limit = 160 * 1024;
-    hipStream_t stream = nullptr;
     std::string err;
     Dataset ds[2];
-    double* d_classw = nullptr;
+    DevBuf<double> d_classw;
     int n_classw = 0;
     bool arch_set = false;
     npbnn_arch arch{};
@@ -105,10 +125,9 @@ struct npbnn_ctx {
     int l0_option = 0;             // NPBNN_L0_AUTO / _F32 / _F16
     int fast_option = 1;           // NPBNN_OPT_FAST_TAILS
     int slopes_option = 0;         // NPBNN_OPT_TRAINABLE_SLOPES: the image holds a slot per hidden layer for the activation slope
-    SlopeState* d_slopes = nullptr; // trainable slopes of the device chain (npbnn_chain_cfg.slope_idx ...)
-    int* d_sidx = nullptr;          // [slope_cap] pre-drawn slope entries ...
-    double* d_sdelta = nullptr;     // ... and steps
-    size_t slope_cap = 0;
+    DevBuf<SlopeState> d_slopes;    // trainable slopes of the device chain (npbnn_chain_cfg.slope_idx ...)
+    DevBuf<int> d_sidx;             // pre-drawn slope entries ...
+    DevBuf<double> d_sdelta;        // ... and steps
     bool batch_slopes = false;      // the batch in flight carries slopes (chain_finish reads them back)
     int persist_option = 1;        // NPBNN_OPT_PERSISTENT
     const void* attr_fn = nullptr; // kernel whose dynamic-LDS limit was raised last, and to what
@@ -121,36 +140,35 @@ struct npbnn_ctx {
     int f16_shifted_cols = 0;      // columns whose scale was moved up (heavy tails: ensure_scales) and the largest such move (powers of two)
     int f16_max_shift = 0;
     int scale_F = 0;
-    int* d_overflow = nullptr;
-    // parameter blocks of the kernels: device copies (kernels take a pointer) + pinned host staging
-    EvalParams* d_eparams = nullptr;
-    FinalizeParams* d_fparams = nullptr;
-    ChainParams* d_cparams = nullptr;
-    char* h_params = nullptr;      // pinned: EvalParams | FinalizeParams | ChainParams
-    float* d_w2scale = nullptr;
+    DevBuf<int> d_overflow;
+    // parameter blocks of the kernels: device copies (kernels take a pointer) + pinned host staging, both laid out
+    // EvalParams | FinalizeParams | ChainParams
+    DevBuf<char> d_params;
+    EvalParams* d_eparams = nullptr;       // (view into d_params)
+    FinalizeParams* d_fparams = nullptr;   // (view into d_params)
+    ChainParams* d_cparams = nullptr;      // (view into d_params)
+    PinnedBuf<char> h_params;
+    DevBuf<float> d_w2scale;
     // device work buffers
-    double* d_wraw = nullptr;      // packed float64 weights
-    double* d_colov = nullptr;     // column override (in_dim doubles)
-    float* d_image = nullptr;      // float32 fragment image
-    int* d_w2img = nullptr;        // packed-weight index -> image float index
-    double* d_partials = nullptr;
-    int partial_waves = 0;
-    unsigned* d_conf = nullptr;    // NPBNN_MAX_WIDTH^2
-    npbnn_eval_out* d_out = nullptr;
-    float* d_y = nullptr;
-    size_t d_y_cap = 0;
+    DevBuf<double> d_wraw;         // packed float64 weights
+    DevBuf<double> d_colov;        // column override (in_dim doubles)
+    DevBuf<float> d_image;         // float32 fragment image
+    DevBuf<int> d_w2img;           // packed-weight index -> image float index
+    DevBuf<double> d_partials;
+    DevBuf<unsigned> d_conf;       // [classes][classes], classes >= kResidentMaxWidth (ensure_conf)
+    DevBuf<npbnn_eval_out> d_out;
+    DevBuf<float> d_y;
     // pinned host staging
-    double* h_w = nullptr;
-    size_t h_w_cap = 0;
-    npbnn_eval_out* h_out = nullptr;
-    unsigned* h_conf = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    PinnedBuf<double> h_w;
+    PinnedBuf<npbnn_eval_out> h_out;
+    PinnedBuf<unsigned> h_conf;
     // device-resident chain.  d_res / h_res: one block [ChainDev | overflow flag | W_cur | accepted | logLik' | logPrior'] so that a
-    // single copy brings the whole outcome of a batch to the (pinned) host side; d_chain, d_wcur, d_acc, d_llp, d_lpp point into it
-    char* d_res = nullptr;
-    char* h_res = nullptr;
-    size_t res_cap = 0, res_k = 0, res_nw = 0;
-    int* d_chain_ovf = nullptr;
+    // single copy brings the whole outcome of a batch to the (pinned) host side; d_chain ... d_lpp point into it.  res_k, res_nw:
+    // the iterations and weights it is laid out for (0: lay it out again)
+    DevBuf<char> d_res;
+    PinnedBuf<char> h_res;
+    size_t res_k = 0, res_nw = 0;
+    int* d_chain_ovf = nullptr;    // (view into d_res)
     int last_schedule = 0;         // schedule of the previous batch
     int turn_batches[2][2] = {{0, 0}, {0, 0}};   // [form][batch-size class] batches run since that form was last measured in that class (kTurnReprobeBatches)
     double turn_us[2] = {0.0, 0.0}; // measured time of a launch turn (pass, decided or void) of the persistent forms: overlapped, decision between passes
@@ -160,16 +178,13 @@ struct npbnn_ctx {
                                     // cost per batch differs, so what wins in dispatches of 100 need not win in sub-batches of 512
     double its_per_pass = 0.0;     // iterations a launch decided on average in the previous batch (0: unknown)
     double accept_rate = -1.0;     // acceptance rate of the previous batch (< 0: unknown)
-    double* d_wcur = nullptr;
-    double* d_pv = nullptr;        // [kMaxCand][M] proposed values of the candidates in flight
-    size_t pv_cap = 0;
+    double* d_wcur = nullptr;      // (view into d_res)
+    DevBuf<double> d_pv;           // [2][kMaxCand][M] proposed values of the candidates in flight
     // NPBNN_SCHED_PERSIST_SERIAL (spec_round): outcome-speculative preparation
-    SpecState* d_spec = nullptr;
-    double* d_spec_pv = nullptr;   // [3][kSpecOutcomes][kMaxCand][M]
-    size_t spec_pv_cap = 0;        // M capacity
-    unsigned* d_spec_touch = nullptr;   // [kMaxCand][n_weights][4] touch tables: pass tag (cleared before it could repeat), -, value
-    size_t spec_touch_cap = 0;     // weights capacity
-    unsigned long long* d_spec_part = nullptr;   // [2][kMaxCand][kPartialStride][256][2] the workgroups' sums of a pass as tagged word pairs (npbnn_chain.hip.h, SpecPart)
+    DevBuf<SpecState> d_spec;
+    DevBuf<double> d_spec_pv;      // [3][kSpecOutcomes][kMaxCand][M]
+    DevBuf<unsigned> d_spec_touch; // [kMaxCand][n_weights][4] touch tables: pass tag (cleared before it could repeat), -, value
+    DevBuf<unsigned long long> d_spec_part;   // [2][kMaxCand][kPartialStride][256][2] the workgroups' sums of a pass as tagged word pairs (npbnn_chain.hip.h, SpecPart)
     unsigned spec_gen = 0;         // pass tags handed out so far
     // rows split over the ranks of a communicator (npbnn_set_row_shard): the records of partial sums are gathered before every step
     int shard_n = 0, shard_rank = 0;
@@ -177,37 +192,30 @@ struct npbnn_ctx {
     npbnn_comm* shard_comm = nullptr;
     npbnn_gather_fn shard_gather = nullptr;
     void* shard_user = nullptr;
-    double* d_shard_recv = nullptr;   // [shard_n][kMaxCand][kPartialStride]: this rank's record at its own place, the peers' after the gather
-    double* d_shard_part = nullptr;   // [kMaxCand][kPartialStride][shard_n]: the same in the layout the step kernel sums
-    double* h_shard = nullptr;        // pinned, as d_shard_recv (host-staged gather)
-    double* d_mask = nullptr;
-    ChainDev* d_chain = nullptr;
-    int* d_idx = nullptr;
-    double* d_delta = nullptr;
-    int* d_pos = nullptr;
-    float* d_pscale = nullptr;
-    size_t draw_cap = 0;        // K*M capacity of d_idx / d_delta
-    int* d_cnt = nullptr;
-    double* d_logu = nullptr;
-    unsigned char* d_acc = nullptr;
-    double* d_llp = nullptr;
-    double* d_lpp = nullptr;
-    size_t iter_cap = 0;        // K capacity
-    EvalParams* d_gparams = nullptr;   // parameter block of a group pass led by this context (npbnn_chains_run_batched)
-    EvalParams* h_gparams = nullptr;   // its page-locked staging twin
-    double* d_pscale_w = nullptr;  // [n_weights] per-weight prior scales of the current batch (npbnn_chain_cfg.prior_scale_w)
-    double* d_smult = nullptr;  // [K][k_targets] sigma multipliers, [K] Hastings terms (regression with an estimated error parameter)
-    double* d_hast = nullptr;
-    size_t smult_cap = 0;       // K capacity of the two
+    DevBuf<double> d_shard_recv;   // [shard_n][kMaxCand][kPartialStride]: this rank's record at its own place, the peers' after the gather
+    DevBuf<double> d_shard_part;   // [kMaxCand][kPartialStride][shard_n]: the same in the layout the step kernel sums
+    PinnedBuf<double> h_shard;     // as d_shard_recv, + this rank's record (host-staged gather)
+    DevBuf<double> d_mask;
+    ChainDev* d_chain = nullptr;   // (view into d_res)
+    DevBuf<int> d_idx;             // the batch's weight indices, then (d_delta) its deviates
+    double* d_delta = nullptr;     // (view into d_idx)
+    DevBuf<int> d_pos;
+    DevBuf<float> d_pscale;
+    int* d_cnt = nullptr;          // (view into d_res)
+    double* d_logu = nullptr;      // (view into d_res)
+    unsigned char* d_acc = nullptr;   // (view into d_res)
+    double* d_llp = nullptr;       // (view into d_res)
+    double* d_lpp = nullptr;       // (view into d_res)
+    DevBuf<EvalParams> d_gparams;     // parameter block of a group pass led by this context (npbnn_chains_run_batched)
+    PinnedBuf<EvalParams> h_gparams;  // its page-locked staging twin
+    DevBuf<double> d_pscale_w;     // [n_weights] per-weight prior scales of the current batch (npbnn_chain_cfg.prior_scale_w)
+    DevBuf<double> d_smult;        // [K][NPBNN_MAX_TARGETS] sigma multipliers, [K] Hastings terms (regression with an estimated error parameter)
+    DevBuf<double> d_hast;
     // exchange run (npbnn_chains_run_exchange): [ExchangeParams | swap_j | swap_k | swap_logu || state | records | cold weights]
-    char* d_xbuf = nullptr;
-    char* h_xbuf = nullptr;
-    size_t xbuf_cap = 0;
-    hipEvent_t ev_x = nullptr;
+    DevBuf<char> d_xbuf;
+    PinnedBuf<char> h_xbuf;
     // feature matrices shared between the chains of one run (npbnn_share_data): a borrower points at its owner, an owner
     // counts its borrowers and outlives them (a destroyed owner lingers until the last borrower lets go)
-    // flag-ordered overlapped chain schedule: the launches alternate between these two streams
-    hipStream_t stream_e[2] = {nullptr, nullptr};
     bool sync_failed = false;      // a wait timed out once: the schedule stays off for this context
     int debug_sync_skip = -1;      // npbnn_debug_sync_skip_ (diagnostics, not part of the ABI)
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
@@ -218,17 +226,14 @@ struct npbnn_ctx {
     bool wide = false;
     int wide_option = 0;           // NPBNN_OPT_WIDE: 0 when the resident path cannot hold the network, 1 always
     WideMeta wmeta{};
-    // Sizes: d_wide_cand and d_wide_cs by the network alone (wide_build); d_prep_terms by the widest proposal (prep_cap, chain_prepare);
+    // Sizes: d_wide_cand and d_wide_cs by the network alone (wide_build); d_prep_terms by the widest proposal (chain_prepare);
     // the fp16-split copy Dataset::X16w by its own table (built by wide_plan, freed with the table); d_wide_act by the largest table a plan
     // was made for (wide_plan: rows x widest layer, and npbnn_wide_slice_room for the K-slices), which wide_forward checks every launch against.
-    float* d_wide_cand = nullptr;  // candidate image of a device chain (the committed image with the pending proposal patched in)
-    float* d_wide_act[3] = {nullptr, nullptr, nullptr};   // hidden activations [rows][16 * tiles], ping-pong between layers; [2]: the K-slices' sums
-    size_t wide_act_cap = 0;       // floats each of [0], [1]
-    size_t wide_slice_cap = 0;     // floats of [2] (npbnn_wide_slice_room of the largest demand met; wide_forward checks every launch against it)
-    double* d_prep_terms = nullptr;       // [kMaxCand][M] prior terms of the pending candidates' entries (ChainParams::prep_terms)
-    size_t prep_cap = 0;
-    WideCandState* d_wide_cs = nullptr;   // what the candidate image's last patch covered (wide proposals: wide_cand_sync)
-    unsigned conf_cap = 0;         // classes d_conf / h_conf are sized for
+    DevBuf<float> d_wide_cand;     // candidate image of a device chain (the committed image with the pending proposal patched in)
+    DevBuf<float> d_wide_act[3];   // hidden activations [rows][16 * tiles], ping-pong between layers; [2]: the K-slices' sums
+    DevBuf<double> d_prep_terms;   // [kMaxCand][M] prior terms of the pending candidates' entries (ChainParams::prep_terms)
+    DevBuf<WideCandState> d_wide_cs;   // what the candidate image's last patch covered (wide proposals: wide_cand_sync)
+    std::set<const void*> wide_lds_raised;   // kernels of the weight-streamed path whose dynamic-LDS limit was raised (wide_forward)
 };
 
 static_assert(sizeof(EvalParams) % 8 == 0 && sizeof(FinalizeParams) % 8 == 0, "parameter blocks are laid out back to back");
@@ -313,7 +318,7 @@ int push_eval_params(npbnn_ctx* ctx, const EvalParams& p);
 int push_finalize_params(npbnn_ctx* ctx, const FinalizeParams& f);
 int push_chain_params(npbnn_ctx* ctx, const ChainParams& c);
 EvalParams make_params(npbnn_ctx* ctx, const Dataset& d);
-void report_eval_stamps(unsigned long long* d_stamps, int grid, int wpb, int first_wg);
+void report_eval_stamps(const DevBuf<unsigned long long>& stamps, int grid, int wpb, int first_wg);
 int check_dataset_for_lik(npbnn_ctx* ctx, const Dataset& d, int lik);
 double wall_us();
 // launches of kernels that live in npbnn_capi.hip, for the other translation units: the weight image of device-resident float64

@@ -230,17 +230,11 @@ __global__ void __launch_bounds__(1024) gen_decide_kernel(const GenParams* __res
     }
 }
 
-struct DevBuf {                     // a device allocation freed at scope exit
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <typename T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
 template <typename T>
-int upload(npbnn_ctx* ctx, DevBuf& b, const T* src, size_t n) {
+int upload(npbnn_ctx* ctx, DevBuf<T>& b, const T* src, size_t n) {
     if (!src || n == 0) return NPBNN_OK;
-    HIP_TRY(ctx, hipMalloc(&b.p, n * sizeof(T)));
-    HIP_TRY(ctx, hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = b.reserve(ctx, n)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(b, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     return NPBNN_OK;
 }
 
@@ -284,77 +278,78 @@ extern "C" int npbnn_chain_run_general(npbnn_ctx* ctx, const npbnn_chain_cfg* cf
         rc = ensure_work_buffers(ctx, lp.n_waves);
         if (rc) return rc;
         hipStream_t st = ctx->stream;
-        DevBuf b_state, b_W, b_ind, b_find, b_means, b_mask, b_idx, b_val, b_cnt, b_hidx, b_hval, b_hfac, b_hcnt, b_lm, b_iptr, b_ipos, b_fptr, b_fpos,
-            b_fuse, b_logu, b_hin, b_smult, b_out, b_psw, b_params, b_flags;
+        DevBuf<GenDev> b_state;
+        DevBuf<GenParams> b_params;
+        DevBuf<double> b_W, b_ind, b_find, b_means, b_mask, b_val, b_hval, b_hfac, b_logu, b_hin, b_smult, b_psw;
+        DevBuf<int> b_idx, b_cnt, b_hidx, b_hcnt, b_lm, b_iptr, b_ipos, b_fptr, b_fpos, b_fuse, b_flags;
+        DevBuf<char> b_out;
         GenParams g{};
         // state and work buffers
-        HIP_TRY(ctx, hipMalloc(&b_state.p, sizeof(GenDev)));
-        HIP_TRY(ctx, hipMalloc(&b_W.p, (size_t)3 * nw * sizeof(double)));
-        HIP_TRY(ctx, hipMalloc(&b_flags.p, sizeof(int)));
-        HIP_TRY(ctx, hipMemsetAsync(b_flags.p, 0, sizeof(int), st));
+        if ((rc = b_state.reserve(ctx, 1)) || (rc = b_W.reserve(ctx, (size_t)3 * nw)) || (rc = b_flags.reserve(ctx, 1))) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(b_flags.get(), 0, sizeof(int), st));
         GenDev init{};
         init.logLik = cfg->cur_loglik;
         init.logPrior = cfg->cur_logprior;
         for (int j = 0; j < NPBNN_MAX_TARGETS; ++j) init.sigma[j] = cfg->cur_sigma[j];
-        HIP_TRY(ctx, hipMemcpyAsync(b_state.p, &init, sizeof init, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(b_W.p, W_inout, (size_t)nw * sizeof(double), hipMemcpyHostToDevice, st));
-        g.st = b_state.as<GenDev>();
-        g.Wc = b_W.as<double>();
+        HIP_TRY(ctx, hipMemcpyAsync(b_state.get(), &init, sizeof init, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(b_W.get(), W_inout, (size_t)nw * sizeof(double), hipMemcpyHostToDevice, st));
+        g.st = b_state.get();
+        g.Wc = b_W.get();
         g.Wp = g.Wc + nw;
         g.Weff = g.Wp + nw;
         if (gc->ind_inout) {
-            HIP_TRY(ctx, hipMalloc(&b_ind.p, (size_t)2 * n0 * sizeof(double)));
-            HIP_TRY(ctx, hipMemcpyAsync(b_ind.p, gc->ind_inout, (size_t)n0 * sizeof(double), hipMemcpyHostToDevice, st));
-            g.indc = b_ind.as<double>();
+            if ((rc = b_ind.reserve(ctx, (size_t)2 * n0))) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(b_ind.get(), gc->ind_inout, (size_t)n0 * sizeof(double), hipMemcpyHostToDevice, st));
+            g.indc = b_ind.get();
             g.indp = g.indc + n0;
         }
         if (gc->find_inout) {
-            HIP_TRY(ctx, hipMalloc(&b_find.p, (size_t)3 * F * sizeof(double)));
-            HIP_TRY(ctx, hipMemcpyAsync(b_find.p, gc->find_inout, (size_t)F * sizeof(double), hipMemcpyHostToDevice, st));
-            g.findc = b_find.as<double>();
+            if ((rc = b_find.reserve(ctx, (size_t)3 * F))) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(b_find.get(), gc->find_inout, (size_t)F * sizeof(double), hipMemcpyHostToDevice, st));
+            g.findc = b_find.get();
             g.findp = g.findc + F;
             g.colov = g.findp + F;
             if ((rc = upload(ctx, b_means, gc->feature_means, (size_t)F))) return rc;
-            g.feature_means = b_means.as<double>();
+            g.feature_means = b_means.get();
         }
         if ((rc = upload(ctx, b_mask, mask_packed, (size_t)nw))) return rc;
-        g.mask = b_mask.as<double>();
+        g.mask = b_mask.get();
         if ((rc = upload(ctx, b_idx, gc->idx, KM)) || (rc = upload(ctx, b_val, gc->val, KM)) || (rc = upload(ctx, b_cnt, gc->cnt, (size_t)K))) return rc;
-        g.idx = b_idx.as<int>(); g.val = b_val.as<double>(); g.cnt = b_cnt.as<int>();
+        g.idx = b_idx.get(); g.val = b_val.get(); g.cnt = b_cnt.get();
         if (gc->proposal_kind == NPBNN_PROP_FIXED_NORMAL) {
             if ((rc = upload(ctx, b_hidx, gc->h_idx, KM)) || (rc = upload(ctx, b_hval, gc->h_val, KM)) || (rc = upload(ctx, b_hfac, gc->h_fac, KM)) ||
                 (rc = upload(ctx, b_hcnt, gc->h_cnt, (size_t)K)))
                 return rc;
-            g.h_idx = b_hidx.as<int>(); g.h_val = b_hval.as<double>(); g.h_fac = b_hfac.as<double>(); g.h_cnt = b_hcnt.as<int>();
+            g.h_idx = b_hidx.get(); g.h_val = b_hval.get(); g.h_fac = b_hfac.get(); g.h_cnt = b_hcnt.get();
         }
         if ((rc = upload(ctx, b_lm, gc->layer_mask, (size_t)K))) return rc;
-        g.layer_mask = b_lm.as<int>();
+        g.layer_mask = b_lm.get();
         if (gc->ind_inout) {
             if ((rc = upload(ctx, b_iptr, gc->ind_ptr, (size_t)K + 1)) || (rc = upload(ctx, b_ipos, gc->ind_pos, (size_t)(gc->ind_ptr[K] > 0 ? gc->ind_ptr[K] : 1))))
                 return rc;
-            g.ind_ptr = b_iptr.as<int>(); g.ind_pos = b_ipos.as<int>();
+            g.ind_ptr = b_iptr.get(); g.ind_pos = b_ipos.get();
         }
         if (gc->find_inout) {
             if ((rc = upload(ctx, b_fptr, gc->find_ptr, (size_t)K + 1)) ||
                 (rc = upload(ctx, b_fpos, gc->find_pos, (size_t)(gc->find_ptr[K] > 0 ? gc->find_ptr[K] : 1))) || (rc = upload(ctx, b_fuse, gc->find_use, (size_t)K)))
                 return rc;
-            g.find_ptr = b_fptr.as<int>(); g.find_pos = b_fpos.as<int>(); g.find_use = b_fuse.as<int>();
+            g.find_ptr = b_fptr.get(); g.find_pos = b_fpos.get(); g.find_use = b_fuse.get();
         }
         if ((rc = upload(ctx, b_logu, log_u, (size_t)K))) return rc;
-        g.log_u = b_logu.as<double>();
+        g.log_u = b_logu.get();
         if (cfg->sigma_mult || cfg->hastings) {
             if (!cfg->sigma_mult || !cfg->hastings || lik != NPBNN_LIK_GAUSS)
                 return fail(ctx, NPBNN_E_ARG, "chain_run_general: sigma_mult and hastings go together, with the Gaussian likelihood");
             if ((rc = upload(ctx, b_smult, cfg->sigma_mult, (size_t)K * k)) || (rc = upload(ctx, b_hin, cfg->hastings, (size_t)K))) return rc;
-            g.sigma_mult = b_smult.as<double>();
-            g.hastings_in = b_hin.as<double>();
+            g.sigma_mult = b_smult.get();
+            g.hastings_in = b_hin.get();
         }
         if (cfg->prior_scale_w && cfg->prior_kind != NPBNN_PRIOR_UNIFORM) {
             if ((rc = upload(ctx, b_psw, cfg->prior_scale_w, (size_t)nw))) return rc;
-            g.prior_scale_w = b_psw.as<double>();
+            g.prior_scale_w = b_psw.get();
         }
-        HIP_TRY(ctx, hipMalloc(&b_out.p, (size_t)K * (1 + 2 * sizeof(double)) + 64));
-        g.out_ll = b_out.as<double>();
+        if ((rc = b_out.reserve(ctx, (size_t)K * (1 + 2 * sizeof(double)) + 64))) return rc;
+        g.out_ll = reinterpret_cast<double*>(b_out.get());
         g.out_lp = g.out_ll + K;
         g.out_acc = reinterpret_cast<unsigned char*>(g.out_lp + K);
         g.partials = ctx->d_partials;
@@ -370,18 +365,18 @@ extern "C" int npbnn_chain_run_general(npbnn_ctx* ctx, const npbnn_chain_cfg* cf
         for (int l = 0; l < kMaxLayers; ++l)      // (fixed activation slopes: cfg->cur_slopes, as in npbnn_chain_run)
             ctx->net.act_prm[l] = (!cfg->slope_idx && l < cfg->n_slopes && l < NPBNN_MAX_LAYERS) ? (float)cfg->cur_slopes[l] : 0.f;
         g.net = ctx->net;
-        HIP_TRY(ctx, hipMalloc(&b_params.p, sizeof(GenParams)));
-        HIP_TRY(ctx, hipMemcpyAsync(b_params.p, &g, sizeof g, hipMemcpyHostToDevice, st));      // (pageable source: staged before the call returns)
+        if ((rc = b_params.reserve(ctx, 1))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(b_params.get(), &g, sizeof g, hipMemcpyHostToDevice, st));      // (pageable source: staged before the call returns)
         EvalParams p = make_params(ctx, d);
         p.partials = ctx->d_partials;
         p.inst_w = d.inst_w;
         p.use_classw = ctx->n_classw > 0 ? 1 : 0;
         rc = push_eval_params(ctx, p);
         if (rc) return rc;
-        const GenParams* dgp = b_params.as<GenParams>();
+        const GenParams* dgp = b_params.get();
         for (int t = 0; t < K; ++t) {
             hipLaunchKernelGGL(gen_propose_kernel, dim3(1), dim3(1024), 0, st, dgp, t);
-            launch_pack_weights(ctx, g.Weff, g.colov, ctx->d_image, reinterpret_cast<int*>(b_flags.p));
+            launch_pack_weights(ctx, g.Weff, g.colov, ctx->d_image, b_flags.get());
             rc = launch_plain_eval(ctx, lp, 0);
             if (rc) return rc;
             hipLaunchKernelGGL(gen_decide_kernel, dim3(1), dim3(1024), 0, st, dgp, t);
@@ -396,8 +391,8 @@ extern "C" int npbnn_chain_run_general(npbnn_ctx* ctx, const npbnn_chain_cfg* cf
         HIP_TRY(ctx, hipMemcpyAsync(h_W.data(), g.Wc, (size_t)nw * sizeof(double), hipMemcpyDeviceToHost, st));
         if (gc->ind_inout) HIP_TRY(ctx, hipMemcpyAsync(h_ind.data(), g.indc, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, st));
         if (gc->find_inout) HIP_TRY(ctx, hipMemcpyAsync(h_find.data(), g.findc, (size_t)F * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(&fin, b_state.p, sizeof fin, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipMemcpyAsync(&flags, b_flags.p, sizeof flags, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(&fin, b_state.get(), sizeof fin, hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(&flags, b_flags.get(), sizeof flags, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
         if (flags & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "chain_run_general: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is");
         if (ctx->net.l0_f16 && (flags & kFlagF16Range)) {      // a candidate left the fp16 range: the whole batch again on the float32 path

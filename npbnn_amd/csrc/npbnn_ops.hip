@@ -9,9 +9,12 @@
 #include <cstdio>
 #include <vector>
 
+#include "npbnn_buf.hip.h"
 #include "npbnn_hip.h"
 
 extern "C" void npbnn_set_global_error_(const char* msg);
+
+using npbnn_api::DevBuf;
 
 namespace {
 
@@ -31,12 +34,11 @@ int ofail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return ofail(NPBNN_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
-struct DevBuf {          // RAII device buffer
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8); }
-    template <typename T> T* as() { return static_cast<T*>(p); }
-};
+// a device allocation that lives for one call: n elements (of 8 bytes), 8 bytes when there are none
+template <typename T>
+int alloc(DevBuf<T>& b, size_t n) {
+    return b.reserve(nullptr, n ? n : 1);
+}
 
 constexpr int kBlock = 256;
 
@@ -166,12 +168,12 @@ int npbnn_op_activation(int device, int kind, double prm, double* inout, int64_t
     if (!inout || n < 0 || kind < 0 || kind > 4) return ofail(NPBNN_E_ARG, "op_activation: bad arguments");
     if (n == 0) return NPBNN_OK;
     O_HIP(hipSetDevice(device));
-    DevBuf d;
-    O_HIP(d.alloc((size_t)n * 8));
-    O_HIP(hipMemcpy(d.p, inout, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(act_kernel, dim3(grid_for(n)), dim3(kBlock), 0, 0, d.as<double>(), (long long)n, kind, prm);
+    DevBuf<double> d;
+    if (int rc = alloc(d, (size_t)n)) return rc;
+    O_HIP(hipMemcpy(d.get(), inout, (size_t)n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(act_kernel, dim3(grid_for(n)), dim3(kBlock), 0, 0, d.get(), (long long)n, kind, prm);
     O_HIP(hipGetLastError());
-    O_HIP(hipMemcpy(inout, d.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    O_HIP(hipMemcpy(inout, d.get(), (size_t)n * 8, hipMemcpyDeviceToHost));
     return NPBNN_OK;
 }
 
@@ -180,13 +182,13 @@ int npbnn_op_output(int device, int out_kind, double* inout, int64_t rows, int32
     if (rows == 0 || out_kind == NPBNN_OUT_IDENTITY) return NPBNN_OK;
     if (ind < 0) ind = cols / 2;
     O_HIP(hipSetDevice(device));
-    DevBuf d;
+    DevBuf<double> d;
     const size_t bytes = (size_t)rows * cols * 8;
-    O_HIP(d.alloc(bytes));
-    O_HIP(hipMemcpy(d.p, inout, bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(output_kernel, dim3(grid_for(rows)), dim3(kBlock), 0, 0, d.as<double>(), (long long)rows, cols, out_kind, ind);
+    if (int rc = alloc(d, (size_t)rows * cols)) return rc;
+    O_HIP(hipMemcpy(d.get(), inout, bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(output_kernel, dim3(grid_for(rows)), dim3(kBlock), 0, 0, d.get(), (long long)rows, cols, out_kind, ind);
     O_HIP(hipGetLastError());
-    O_HIP(hipMemcpy(inout, d.p, bytes, hipMemcpyDeviceToHost));
+    O_HIP(hipMemcpy(inout, d.get(), bytes, hipMemcpyDeviceToHost));
     return NPBNN_OK;
 }
 
@@ -208,26 +210,27 @@ int npbnn_op_likelihood(int device, int lik_kind, const double* pred, int64_t ro
         if (lik_kind == NPBNN_LIK_GAUSS && !sigma) return ofail(NPBNN_E_ARG, "op_likelihood: sigma missing");
     }
     O_HIP(hipSetDevice(device));
-    DevBuf dp, dl, dt, dw, dc, ds, dpart;
-    O_HIP(dp.alloc((size_t)rows * cols * 8));
-    O_HIP(hipMemcpy(dp.p, pred, (size_t)rows * cols * 8, hipMemcpyHostToDevice));
-    if (labels) { O_HIP(dl.alloc((size_t)rows * 8)); O_HIP(hipMemcpy(dl.p, labels, (size_t)rows * 8, hipMemcpyHostToDevice)); }
-    if (targets) { O_HIP(dt.alloc((size_t)rows * k * 8)); O_HIP(hipMemcpy(dt.p, targets, (size_t)rows * k * 8, hipMemcpyHostToDevice)); }
-    if (inst_w) { O_HIP(dw.alloc((size_t)rows * 8)); O_HIP(hipMemcpy(dw.p, inst_w, (size_t)rows * 8, hipMemcpyHostToDevice)); }
+    DevBuf<double> dp, dt, dw, dc, ds, dpart;
+    DevBuf<long long> dl;
+    if (int rc = alloc(dp, (size_t)rows * cols)) return rc;
+    O_HIP(hipMemcpy(dp.get(), pred, (size_t)rows * cols * 8, hipMemcpyHostToDevice));
+    if (labels) { if (int rc = alloc(dl, (size_t)rows)) return rc; O_HIP(hipMemcpy(dl.get(), labels, (size_t)rows * 8, hipMemcpyHostToDevice)); }
+    if (targets) { if (int rc = alloc(dt, (size_t)rows * k)) return rc; O_HIP(hipMemcpy(dt.get(), targets, (size_t)rows * k * 8, hipMemcpyHostToDevice)); }
+    if (inst_w) { if (int rc = alloc(dw, (size_t)rows)) return rc; O_HIP(hipMemcpy(dw.get(), inst_w, (size_t)rows * 8, hipMemcpyHostToDevice)); }
     if (class_w) {
         if (n_class_w < cols) return ofail(NPBNN_E_ARG, "op_likelihood: %d class weights for %d classes", n_class_w, cols);
-        O_HIP(dc.alloc((size_t)n_class_w * 8));
-        O_HIP(hipMemcpy(dc.p, class_w, (size_t)n_class_w * 8, hipMemcpyHostToDevice));
+        if (int rc = alloc(dc, (size_t)n_class_w)) return rc;
+        O_HIP(hipMemcpy(dc.get(), class_w, (size_t)n_class_w * 8, hipMemcpyHostToDevice));
     }
-    if (sigma) { O_HIP(ds.alloc((size_t)k * 8)); O_HIP(hipMemcpy(ds.p, sigma, (size_t)k * 8, hipMemcpyHostToDevice)); }
+    if (sigma) { if (int rc = alloc(ds, (size_t)k)) return rc; O_HIP(hipMemcpy(ds.get(), sigma, (size_t)k * 8, hipMemcpyHostToDevice)); }
     const int g = grid_for(rows);
-    O_HIP(dpart.alloc((size_t)g * 8));
-    hipLaunchKernelGGL(lik_kernel, dim3(g), dim3(kBlock), 0, 0, lik_kind, dp.as<double>(), (long long)rows, cols, dl.as<long long>(),
-                       dt.as<double>(), k, inst_w ? dw.as<double>() : nullptr, class_w ? dc.as<double>() : nullptr,
-                       sigma ? ds.as<double>() : nullptr, dpart.as<double>());
+    if (int rc = alloc(dpart, (size_t)g)) return rc;
+    hipLaunchKernelGGL(lik_kernel, dim3(g), dim3(kBlock), 0, 0, lik_kind, dp.get(), (long long)rows, cols, dl.get(),
+                       dt.get(), k, inst_w ? dw.get() : nullptr, class_w ? dc.get() : nullptr,
+                       sigma ? ds.get() : nullptr, dpart.get());
     O_HIP(hipGetLastError());
     std::vector<double> part((size_t)g);
-    O_HIP(hipMemcpy(part.data(), dpart.p, (size_t)g * 8, hipMemcpyDeviceToHost));
+    O_HIP(hipMemcpy(part.data(), dpart.get(), (size_t)g * 8, hipMemcpyDeviceToHost));
     double s = 0.0;
     for (double v : part) s += v;
     const bool tempered = lik_kind <= NPBNN_LIK_GAUSS_PRED_SIGMA;     // the count likelihoods ignore lik_temp (BNN_lik.py)
@@ -244,19 +247,21 @@ int npbnn_op_confusion(int device, const double* pred, int64_t rows, int32_t col
             if (labels[r] < 0 || labels[r] >= cols) return ofail(NPBNN_E_ARG, "op_confusion: label %lld outside 0..%d", (long long)labels[r], cols - 1);
     }
     O_HIP(hipSetDevice(device));
-    DevBuf dp, dl, dc, dn;
-    O_HIP(dp.alloc((size_t)rows * cols * 8));
-    O_HIP(hipMemcpy(dp.p, pred, (size_t)rows * cols * 8, hipMemcpyHostToDevice));
-    if (labels) { O_HIP(dl.alloc((size_t)rows * 8)); O_HIP(hipMemcpy(dl.p, labels, (size_t)rows * 8, hipMemcpyHostToDevice)); }
-    O_HIP(dc.alloc((size_t)cols * cols * 8));
-    O_HIP(hipMemset(dc.p, 0, (size_t)cols * cols * 8));
-    O_HIP(dn.alloc((size_t)cols * 8));
-    O_HIP(hipMemset(dn.p, 0, (size_t)cols * 8));
-    hipLaunchKernelGGL(confusion_kernel, dim3(grid_for(rows)), dim3(kBlock), 0, 0, dp.as<double>(), (long long)rows, cols,
-                       labels ? dl.as<long long>() : nullptr, dc.as<unsigned long long>(), dn.as<unsigned long long>());
+    DevBuf<double> dp;
+    DevBuf<long long> dl;
+    DevBuf<unsigned long long> dc, dn;
+    if (int rc = alloc(dp, (size_t)rows * cols)) return rc;
+    O_HIP(hipMemcpy(dp.get(), pred, (size_t)rows * cols * 8, hipMemcpyHostToDevice));
+    if (labels) { if (int rc = alloc(dl, (size_t)rows)) return rc; O_HIP(hipMemcpy(dl.get(), labels, (size_t)rows * 8, hipMemcpyHostToDevice)); }
+    if (int rc = alloc(dc, (size_t)cols * cols)) return rc;
+    O_HIP(hipMemset(dc.get(), 0, (size_t)cols * cols * 8));
+    if (int rc = alloc(dn, (size_t)cols)) return rc;
+    O_HIP(hipMemset(dn.get(), 0, (size_t)cols * 8));
+    hipLaunchKernelGGL(confusion_kernel, dim3(grid_for(rows)), dim3(kBlock), 0, 0, dp.get(), (long long)rows, cols,
+                       labels ? dl.get() : nullptr, dc.get(), dn.get());
     O_HIP(hipGetLastError());
-    if (labels) O_HIP(hipMemcpy(conf, dc.p, (size_t)cols * cols * 8, hipMemcpyDeviceToHost));
-    O_HIP(hipMemcpy(pred_counts, dn.p, (size_t)cols * 8, hipMemcpyDeviceToHost));
+    if (labels) O_HIP(hipMemcpy(conf, dc.get(), (size_t)cols * cols * 8, hipMemcpyDeviceToHost));
+    O_HIP(hipMemcpy(pred_counts, dn.get(), (size_t)cols * 8, hipMemcpyDeviceToHost));
     return NPBNN_OK;
 }
 
@@ -265,18 +270,18 @@ int npbnn_op_sse(int device, const double* pred, const double* targets, int64_t 
     if (!pred || !targets || !out_per_col || rows < 1 || k < 1 || cols_pred < k || link < 0 || link > 2)
         return ofail(NPBNN_E_ARG, "op_sse: bad arguments");
     O_HIP(hipSetDevice(device));
-    DevBuf dp, dt, dpart;
-    O_HIP(dp.alloc((size_t)rows * cols_pred * 8));
-    O_HIP(hipMemcpy(dp.p, pred, (size_t)rows * cols_pred * 8, hipMemcpyHostToDevice));
-    O_HIP(dt.alloc((size_t)rows * k * 8));
-    O_HIP(hipMemcpy(dt.p, targets, (size_t)rows * k * 8, hipMemcpyHostToDevice));
+    DevBuf<double> dp, dt, dpart;
+    if (int rc = alloc(dp, (size_t)rows * cols_pred)) return rc;
+    O_HIP(hipMemcpy(dp.get(), pred, (size_t)rows * cols_pred * 8, hipMemcpyHostToDevice));
+    if (int rc = alloc(dt, (size_t)rows * k)) return rc;
+    O_HIP(hipMemcpy(dt.get(), targets, (size_t)rows * k * 8, hipMemcpyHostToDevice));
     const int g = grid_for(rows);
-    O_HIP(dpart.alloc((size_t)g * k * 8));
-    hipLaunchKernelGGL(sse_kernel, dim3(g), dim3(kBlock), 0, 0, dp.as<double>(), dt.as<double>(), (long long)rows, cols_pred, k, link,
-                       dpart.as<double>());
+    if (int rc = alloc(dpart, (size_t)g * k)) return rc;
+    hipLaunchKernelGGL(sse_kernel, dim3(g), dim3(kBlock), 0, 0, dp.get(), dt.get(), (long long)rows, cols_pred, k, link,
+                       dpart.get());
     O_HIP(hipGetLastError());
     std::vector<double> part((size_t)g * k);
-    O_HIP(hipMemcpy(part.data(), dpart.p, part.size() * 8, hipMemcpyDeviceToHost));
+    O_HIP(hipMemcpy(part.data(), dpart.get(), part.size() * 8, hipMemcpyDeviceToHost));
     for (int j = 0; j < k; ++j) {
         double s = 0.0;
         for (int b = 0; b < g; ++b) s += part[(size_t)j * g + b];

@@ -268,15 +268,10 @@ __global__ __launch_bounds__(256) void pdp_add_kernel(const float* y, int n, lon
     acc[i] = a;
 }
 
-struct DevBuf {        // device allocation that lives for one call
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-int dev_alloc(npbnn_ctx* ctx, DevBuf& b, size_t bytes) {
-    HIP_TRY(ctx, hipMalloc(&b.p, bytes ? bytes : 16));
-    return NPBNN_OK;
+// a device allocation that lives for one call: n elements, 16 bytes when there are none
+template <class T>
+int dev_alloc(npbnn_ctx* ctx, DevBuf<T>& b, size_t n) {
+    return b.reserve(ctx, n ? n : 16 / sizeof(T));
 }
 
 bool env_on(const char* name) {
@@ -322,16 +317,17 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
     const size_t chunk_bytes = per_set * sizeof(float);
     const int g_chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_grid, budget / std::max<size_t>(chunk_bytes, 1)));
 
-    DevBuf d_w, d_co, d_acc;
-    if ((rc = dev_alloc(ctx, d_w, (size_t)n_sets * wn * sizeof(double)))) return rc;
-    if ((rc = dev_alloc(ctx, d_co, co_all.size() * sizeof(double)))) return rc;
-    if ((rc = dev_alloc(ctx, d_acc, (size_t)g_chunk * per_set * sizeof(float)))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(d_w.p, W_sets, (size_t)n_sets * wn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_co.p, co_all.data(), co_all.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    DevBuf<double> d_w, d_co;
+    DevBuf<float> d_acc;
+    if ((rc = dev_alloc(ctx, d_w, (size_t)n_sets * wn))) return rc;
+    if ((rc = dev_alloc(ctx, d_co, co_all.size()))) return rc;
+    if ((rc = dev_alloc(ctx, d_acc, (size_t)g_chunk * per_set))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_w.get(), W_sets, (size_t)n_sets * wn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_co.get(), co_all.data(), co_all.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     std::vector<float> host_acc((size_t)g_chunk * per_set);
     const double inv_sets = 1.0 / (double)n_sets;
     auto take_chunk = [&](int g0, int n_g) -> int {        // accumulator of grid points g0 .. g0 + n_g - 1 -> out_mean
-        HIP_TRY(ctx, hipMemcpyAsync(host_acc.data(), d_acc.p, (size_t)n_g * per_set * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(host_acc.data(), d_acc.get(), (size_t)n_g * per_set * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         double* dst = out_mean + (size_t)g0 * per_set;
         for (size_t i = 0; i < (size_t)n_g * per_set; ++i) dst[i] = (double)host_acc[i] * inv_sets;
@@ -365,27 +361,27 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
     if ((size_t)NS * q.tail_floats * 4 > kPdpTailLds) batched = false;
 
     if (batched) {
-        DevBuf d_w0t, d_bias, d_tail, d_slopes;
-        if ((rc = dev_alloc(ctx, d_w0t, (size_t)n_sets * Fp * H0P * sizeof(float)))) return rc;
-        if ((rc = dev_alloc(ctx, d_bias, (size_t)n_sets * n_grid * H0P * sizeof(float)))) return rc;
-        if ((rc = dev_alloc(ctx, d_tail, (size_t)n_sets * q.tail_floats * sizeof(float)))) return rc;
-        if ((rc = dev_alloc(ctx, d_slopes, (size_t)n_sets * kMaxLayers * sizeof(float)))) return rc;
+        DevBuf<float> d_w0t, d_bias, d_tail, d_slopes;
+        if ((rc = dev_alloc(ctx, d_w0t, (size_t)n_sets * Fp * H0P))) return rc;
+        if ((rc = dev_alloc(ctx, d_bias, (size_t)n_sets * n_grid * H0P))) return rc;
+        if ((rc = dev_alloc(ctx, d_tail, (size_t)n_sets * q.tail_floats))) return rc;
+        if ((rc = dev_alloc(ctx, d_slopes, (size_t)n_sets * kMaxLayers))) return rc;
         std::vector<float> slopes((size_t)n_sets * kMaxLayers, 0.f);
         if (act_prm_sets)
             for (int s = 0; s < n_sets; ++s)
                 for (int l = 0; l < n_act; ++l) slopes[(size_t)s * kMaxLayers + l] = (float)act_prm_sets[(size_t)s * n_act + l];
-        HIP_TRY(ctx, hipMemcpyAsync(d_slopes.p, slopes.data(), slopes.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(pdp_prep_kernel, dim3(n_sets), dim3(256), 0, ctx->stream, q, d_w.as<const double>(), d_co.as<const double>(),
-                           d_w0t.as<float>(), d_bias.as<float>(), d_tail.as<float>());
+        HIP_TRY(ctx, hipMemcpyAsync(d_slopes.get(), slopes.data(), slopes.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(pdp_prep_kernel, dim3(n_sets), dim3(256), 0, ctx->stream, q, d_w.get(), d_co.get(),
+                           d_w0t.get(), d_bias.get(), d_tail.get());
         HIP_TRY(ctx, hipGetLastError());
         PdpParams p{};
         p.X = d.X; p.n_rows = n_rows; p.Fp = Fp;
-        p.w0t = d_w0t.as<const float>(); p.bias = d_bias.as<const float>(); p.tail = d_tail.as<const float>(); p.slopes = d_slopes.as<const float>();
+        p.w0t = d_w0t.get(); p.bias = d_bias.get(); p.tail = d_tail.get(); p.slopes = d_slopes.get();
         p.n_grid = n_grid; p.tail_floats = q.tail_floats;
         p.n_layers = L; p.act_kind = ctx->arch.act_kind; p.final_act = ctx->arch.final_act; p.out_kind = ctx->arch.out_kind;
         p.apply_out = apply_out_fn ? 1 : 0; p.C = C;
         for (int l = 1; l < L; ++l) { p.t_out[l] = q.l_out[l]; p.t_inp[l] = q.t_inp[l]; p.t_off[l] = q.t_off[l]; }
-        p.acc = d_acc.as<float>();
+        p.acc = d_acc.get();
         const void* fn = H0P == 32 ? reinterpret_cast<const void*>(pdp_kernel<32, 2>) : reinterpret_cast<const void*>(pdp_kernel<64, 1>);
         const size_t lds = ((size_t)Fp * H0P + (size_t)NS * q.tail_floats) * sizeof(float);
         HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -408,13 +404,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
     }
 
     // ---- route 2: one pass of the evaluation kernels per (grid point, group of sets)
-    if (kMaxCand * per_set > ctx->d_y_cap) {
-        if (ctx->d_y) (void)hipFree(ctx->d_y);
-        ctx->d_y = nullptr;
-        ctx->d_y_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_y, kMaxCand * per_set * sizeof(float)));
-        ctx->d_y_cap = kMaxCand * per_set;
-    }
+    if ((rc = ctx->d_y.reserve(ctx, kMaxCand * per_set))) return rc;
     const unsigned add_blocks = (unsigned)((per_set + 255) / 256);
     for (int attempt = 0; attempt < 2; ++attempt) {
         LaunchPlan lp;
@@ -425,7 +415,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
         for (int g0 = 0; g0 < n_grid && !redo; g0 += g_chunk) {
             const int n_g = std::min(g_chunk, n_grid - g0);
             for (int gi = 0; gi < n_g; ++gi) {
-                const double* d_cog = d_co.as<const double>() + (size_t)(g0 + gi) * F;
+                const double* d_cog = d_co.get() + (size_t)(g0 + gi) * F;
                 int s0 = 0;
                 while (s0 < n_sets) {
                     // sets that share their activation slopes travel together, as many as one pass carries
@@ -438,7 +428,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
                     if (act_prm_sets)
                         for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
                     for (int j = 0; j < ng; ++j)
-                        launch_pack_weights(ctx, d_w.as<const double>() + (size_t)(s0 + j) * wn, d_cog,
+                        launch_pack_weights(ctx, d_w.get() + (size_t)(s0 + j) * wn, d_cog,
                                             ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
                     HIP_TRY(ctx, hipGetLastError());
                     EvalParams p = make_params(ctx, d);
@@ -454,7 +444,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
                     rc = launch_plain_eval(ctx, lp, which);
                     if (rc) return rc;
                     hipLaunchKernelGGL(pdp_add_kernel, dim3(add_blocks), dim3(256), 0, ctx->stream, (const float*)ctx->d_y, ng,
-                                       (long long)per_set, d_acc.as<float>() + (size_t)gi * per_set, s0 > 0 ? 1 : 0);
+                                       (long long)per_set, d_acc.get() + (size_t)gi * per_set, s0 > 0 ? 1 : 0);
                     HIP_TRY(ctx, hipGetLastError());
                     // (push_eval_params stages through one pinned slot: the launch that reads it must be in before the next write)
                     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -22,9 +22,8 @@ struct GemmCfg {
     int threads, ppw;      // LDS-DMA pieces a wave requests per K-unit
     int n_stage;           // stages of the ring
     int wc;                // waves along the outputs (1: every wave holds whole rows of the block - the fused end applies)
-    bool attr16 = false, attr32 = false, attr16_d2 = false, attr32_d2 = false, attr16_d3 = false, attr32_d3 = false;
 };
-GemmCfg g_cfg[6] = {
+const GemmCfg g_cfg[6] = {
     {wide_gemm_kernel<8, 4, 2, 4, true>, wide_gemm_kernel<8, 4, 2, 4, false>, nullptr, nullptr, nullptr, nullptr, 16, 16, 512, 8, 2, 4},    // 256 x 256: 64 KiB per stage
     {wide_gemm_kernel<4, 4, 4, 2, true>, wide_gemm_kernel<4, 4, 4, 2, false>, nullptr, nullptr, nullptr, nullptr, 16, 8, 512, 6, 3, 2},     // 256 x 128: 48 KiB
     {wide_gemm_kernel<2, 4, 8, 1, true, 1, 3>, wide_gemm_kernel<2, 4, 8, 1, false, 1, 3>, wide_gemm_kernel<2, 4, 8, 1, true, 2, 3>, wide_gemm_kernel<2, 4, 8, 1, false, 2, 3>, wide_gemm_kernel<2, 4, 8, 1, true, 3, 3>, wide_gemm_kernel<2, 4, 8, 1, false, 3, 3>, 16, 4, 512, 5, 3, 1},     // 256 x 64 : 40 KiB
@@ -35,10 +34,18 @@ GemmCfg g_cfg[6] = {
 // the tiling of a layer and the K-slices of its product: npbnn_wide_plan.h (the rule the slice buffer is sized by - wide_plan)
 static_assert(kWideMaxSlices == NPBNN_WIDE_MAX_SLICES, "npbnn_wide_plan.h caps the K-slices as wide_gemm_kernel does");
 static_assert(sizeof(g_cfg) / sizeof(g_cfg[0]) == NPBNN_WIDE_N_CFG, "npbnn_wide_plan.h describes every tiling");
-GemmCfg& cfg_for(int mt, int n_row_tiles, int n_cu) { return g_cfg[npbnn_wide_cfg_index(mt, n_row_tiles, n_cu)]; }
+const GemmCfg& cfg_for(int mt, int n_row_tiles, int n_cu) { return g_cfg[npbnn_wide_cfg_index(mt, n_row_tiles, n_cu)]; }
 
 int slices_for(const GemmCfg& cf, int n_row_tiles, int mt, int units, int n_cu) {
     return npbnn_wide_slices((int)(&cf - g_cfg), n_row_tiles, mt, units, n_cu);
+}
+
+// the dynamic-LDS limit of a kernel of this path raised to `bytes` (the same for every launch of it), once per context
+int raise_lds(npbnn_ctx* ctx, const void* fn, int bytes) {
+    if (ctx->wide_lds_raised.count(fn)) return NPBNN_OK;
+    HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    ctx->wide_lds_raised.insert(fn);
+    return NPBNN_OK;
 }
 
 // floats of the K-slices' sums a pass over `d` needs (npbnn_wide_plan.h)
@@ -179,13 +186,10 @@ bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
 }
 
 void wide_free(npbnn_ctx* ctx) {
-    if (ctx->d_wide_cand) { (void)hipFree(ctx->d_wide_cand); ctx->d_wide_cand = nullptr; }
-    for (int i = 0; i < 3; ++i)
-        if (ctx->d_wide_act[i]) { (void)hipFree(ctx->d_wide_act[i]); ctx->d_wide_act[i] = nullptr; }
-    ctx->wide_act_cap = 0;
-    ctx->wide_slice_cap = 0;
-    if (ctx->d_wide_cs) { (void)hipFree(ctx->d_wide_cs); ctx->d_wide_cs = nullptr; }
-    if (ctx->d_prep_terms) { (void)hipFree(ctx->d_prep_terms); ctx->d_prep_terms = nullptr; ctx->prep_cap = 0; }
+    ctx->d_wide_cand.reset();
+    for (auto& b : ctx->d_wide_act) b.reset();
+    ctx->d_wide_cs.reset();
+    ctx->d_prep_terms.reset();
 }
 
 // image layout, device images, packed weight -> image position map (called by rebuild_net after build_net has filled ctx->net)
@@ -229,11 +233,11 @@ int wide_build(npbnn_ctx* ctx, bool f16) {
         return fail(ctx, NPBNN_E_ARG, "network too large: a weight image of %.1f GiB (this backend holds up to 2 GiB)", (double)m.image_floats * 4 / (1 << 30) / 1.0);
     ctx->wmeta = m;
     wide_free(ctx);
-    HIP_TRY(ctx, hipMalloc(&ctx->d_image, (size_t)m.image_floats * sizeof(float)));
+    if (int rc = ctx->d_image.reserve(ctx, (size_t)m.image_floats)) return rc;
     HIP_TRY(ctx, hipMemset(ctx->d_image, 0, (size_t)m.image_floats * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_wide_cand, (size_t)kWideMaxCand * m.image_floats * sizeof(float)));      // (a candidate image per weight set of a pass)
+    if (int rc = ctx->d_wide_cand.reserve(ctx, (size_t)kWideMaxCand * m.image_floats)) return rc;      // (a candidate image per weight set of a pass)
     HIP_TRY(ctx, hipMemset(ctx->d_wide_cand, 0, (size_t)kWideMaxCand * m.image_floats * sizeof(float)));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_wide_cs, sizeof(WideCandState)));
+    if (int rc = ctx->d_wide_cs.reserve(ctx, 1)) return rc;
     HIP_TRY(ctx, hipMemset(ctx->d_wide_cs, 0, sizeof(WideCandState)));
     std::vector<int> map((size_t)ctx->n_weights);
     std::vector<float> scale, wscale;
@@ -263,10 +267,10 @@ int wide_build(npbnn_ctx* ctx, bool f16) {
             }
         }
     }
-    HIP_TRY(ctx, hipMalloc(&ctx->d_w2img, map.size() * sizeof(int)));
+    if (int rc = ctx->d_w2img.reserve(ctx, map.size())) return rc;
     HIP_TRY(ctx, hipMemcpy(ctx->d_w2img, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
     if (f16) {
-        HIP_TRY(ctx, hipMalloc(&ctx->d_w2scale, scale.size() * sizeof(float)));
+        if (int rc = ctx->d_w2scale.reserve(ctx, scale.size())) return rc;
         HIP_TRY(ctx, hipMemcpy(ctx->d_w2scale, scale.data(), scale.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return NPBNN_OK;
@@ -282,20 +286,9 @@ int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand) {
     // blocks to fill the chip with) and may take another tiling, so the slice buffer has a capacity of its own, not rows x slices of
     // whichever table came first.
     const size_t need = (size_t)d.n_tiles * 16 * (size_t)max_ld;
-    if (need > ctx->wide_act_cap) {
-        for (int i = 0; i < 2; ++i)
-            if (ctx->d_wide_act[i]) { (void)hipFree(ctx->d_wide_act[i]); ctx->d_wide_act[i] = nullptr; }
-        ctx->wide_act_cap = 0;
-        for (int i = 0; i < 2; ++i) HIP_TRY(ctx, hipMalloc(&ctx->d_wide_act[i], need * sizeof(float)));
-        ctx->wide_act_cap = need;
-    }
     const size_t room = (size_t)slice_room(ctx, d);      // the K-slices' sums: the most any layer writes on this table
-    if (room > ctx->wide_slice_cap) {
-        if (ctx->d_wide_act[2]) { (void)hipFree(ctx->d_wide_act[2]); ctx->d_wide_act[2] = nullptr; }
-        ctx->wide_slice_cap = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_wide_act[2], room * sizeof(float)));
-        ctx->wide_slice_cap = room;
-    }
+    for (int i = 0; i < 3; ++i)
+        if (int rc = ctx->d_wide_act[i].reserve(ctx, i < 2 ? need : room)) return rc;
     if (m.L[0].f16 && !d.X16w) {        // the fp16-split copy in piece order
         Dataset* home = &d;
         if (d.borrowed && ctx->data_owner) {
@@ -356,7 +349,6 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
     const PassDesc* pass = chain_pass ? reinterpret_cast<const PassDesc*>(reinterpret_cast<const char*>(ctx->d_eparams) + offsetof(EvalParams, pass_desc)) : nullptr;
     const bool dev_slopes = chain_pass && ctx->batch_slopes && ctx->d_slopes;
     static const bool no_tail = getenv("NPBNN_WIDE_NO_TAIL") != nullptr;
-    static bool tail_attr = false;
     for (int l = 0; l < m.n_layers; ++l) {
         const WideLayer& L = m.L[l];
         // the narrow end of the network in one launch (wide_tail_kernel): every remaining layer of <= 128 nodes, behind <= 256 inputs,
@@ -372,13 +364,10 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
                 t.out = ctx->d_wide_act[l & 1];
                 t.ldo = 16 * m.L[m.n_layers - 1].mt;
                 t.pass = pass;
-                if ((size_t)d.n_tiles * 16 * t.ldo > ctx->wide_act_cap)
+                if ((size_t)d.n_tiles * 16 * t.ldo > ctx->d_wide_act[l & 1].size())
                     return fail(ctx, NPBNN_E_INTERNAL, "weight-streamed path: the tail on %lld rows needs %lld floats, the buffer holds %zu (internal error: planned for another table)",
-                                (long long)d.n_rows, (long long)d.n_tiles * 16 * t.ldo, ctx->wide_act_cap);
-                if (!tail_attr) {
-                    HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(wide_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024 + 1024));
-                    tail_attr = true;
-                }
+                                (long long)d.n_rows, (long long)d.n_tiles * 16 * t.ldo, ctx->d_wide_act[l & 1].size());
+                if (int rc = raise_lds(ctx, reinterpret_cast<const void*>(wide_tail_kernel), 96 * 1024 + 1024)) return rc;
                 int grid = (d.n_tiles + 7) / 8;
                 if (grid > 2 * ctx->n_cu) grid = 2 * ctx->n_cu;
                 hipLaunchKernelGGL(wide_tail_kernel, dim3(grid), dim3(512), (size_t)tail_floats * 4, st, t);
@@ -387,7 +376,7 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
                 break;
             }
         }
-        GemmCfg& cf = cfg_for(L.mt, d.n_tiles, ctx->n_cu);
+        const GemmCfg& cf = cfg_for(L.mt, d.n_tiles, ctx->n_cu);
         WideGemmArgs g{};
         g.A = A;
         g.lda = lda;
@@ -439,21 +428,18 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
         const bool use16 = L.f16 != 0;
         const int sets = fuse ? n_cand : 1;
         wide_gemm_fn_t fn = sets == 3 ? (use16 ? cf.f16_d3 : cf.f32_d3) : sets == 2 ? (use16 ? cf.f16_d2 : cf.f32_d2) : (use16 ? cf.f16 : cf.f32);
-        bool& attr = sets == 3 ? (use16 ? cf.attr16_d3 : cf.attr32_d3) : sets == 2 ? (use16 ? cf.attr16_d2 : cf.attr32_d2) : (use16 ? cf.attr16 : cf.attr32);
         if (fn == nullptr) return fail(ctx, NPBNN_E_STATE, "no build of the weight-streamed product for this launch (internal error)");
-        if (!attr) {         // (the largest ring any launch asks for: once per kernel)
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_limit));
-            attr = true;
-        }
+        if (int rc = raise_lds(ctx, reinterpret_cast<const void*>(fn), (int)ctx->lds_limit)) return rc;      // (the largest ring any launch asks for)
         const int n_rb = (d.n_tiles + cf.xt - 1) / cf.xt, n_cb = (L.mt + cf.wt - 1) / cf.wt;
         const int n_sl = slices_for(cf, d.n_tiles, L.mt, L.units, ctx->n_cu);
         float* const layer_out = ctx->d_wide_act[l & 1];
         g.k_slices = n_sl;
         g.slice_stride = (long long)d.n_tiles * 16 * g.ldo;
         // (what wide_plan sized for this table: a plan made for another table is an error here, not a write past the buffers)
-        if ((size_t)g.slice_stride > ctx->wide_act_cap || (n_sl > 1 && (size_t)g.slice_stride * n_sl > ctx->wide_slice_cap))
+        if ((size_t)g.slice_stride > ctx->d_wide_act[l & 1].size() || (n_sl > 1 && (size_t)g.slice_stride * n_sl > ctx->d_wide_act[2].size()))
             return fail(ctx, NPBNN_E_INTERNAL, "weight-streamed path: layer %d on %lld rows needs %lld floats x %d K-slices, the buffers hold %zu / %zu "
-                        "(internal error: planned for another table)", l, (long long)d.n_rows, g.slice_stride, n_sl, ctx->wide_act_cap, ctx->wide_slice_cap);
+                        "(internal error: planned for another table)", l, (long long)d.n_rows, g.slice_stride, n_sl, ctx->d_wide_act[l & 1].size(),
+                        ctx->d_wide_act[2].size());
         if (n_sl > 1) g.out = ctx->d_wide_act[2];
         const int grid = (n_rb + 7) / 8 * 8 * n_cb * n_sl;
         hipLaunchKernelGGL(fn, dim3(grid), dim3(cf.threads), lds, st, g);

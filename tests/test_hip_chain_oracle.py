@@ -568,3 +568,31 @@ def test_streamed_chain_with_a_test_set(bn, report):
     errs = [check_state("cat", bnn, mcmc)]
     drive("cat", bnn, mcmc, 60, seed=1, worst=errs, accuracy_every=1)
     _note(report, "streamed", errs)
+
+
+# ---- the architecture set again between batches ----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("path", ["resident", "streamed"])
+def test_set_arch_again_between_batches(path, bn, report, monkeypatch):
+    """npbnn_set_arch between device batches of one context - with the same architecture, then with another of the same number of
+    weights ((16, 7) and (14, 11) on 32 features: 687 each) - lays the chain's result block out again: every later batch holds to
+    float64.  (The per-weight buffers are released by set_arch; the current weights live in the result block.)"""
+    if path == "streamed":
+        monkeypatch.setenv("NPBNN_FORCE_WIDE", "1")
+    dat = make_data("cat", 3000, 32, seed=16)
+    bnn, mcmc = make_chain(bn, "cat", dat, (16, 7))
+    ctx = mcmc._backend.ctx
+    assert ctx.is_wide() == (path == "streamed")
+    mcmc.SUB_BATCH = 16
+    errs = [check_state("cat", bnn, mcmc)]
+    drive("cat", bnn, mcmc, 40, seed=1, worst=errs)
+    mcmc._backend._shapes = None               # the next batch sets the same architecture again (HipBackend._configure)
+    drive("cat", bnn, mcmc, 40, seed=2, worst=errs)
+    bnn2, mcmc2 = make_chain(bn, "cat", dat, (14, 11), seed=99)
+    assert sum(w.size for w in bnn2._w_layers) == sum(w.size for w in bnn._w_layers)
+    mcmc2.SUB_BATCH = 16
+    mcmc2._backend.ctx = ctx                   # the second network's batches on the first context: set_arch to equal weights, new shapes
+    mcmc2._backend._shapes = None
+    drive("cat", bnn2, mcmc2, 40, seed=3, worst=errs)
+    assert ctx.is_wide() == (path == "streamed")
+    _note(report, "set_arch again", errs)
