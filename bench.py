@@ -8,15 +8,20 @@ step    one chain dispatch = ITERATIONS_PER_STEP (100) Metropolis-Hastings itera
         the end of every step.  With the driver's ``--steps 20 --warmup 5`` that is BASELINE.md's protocol: 500 warm-up
         and 2 000 timed iterations, starting from the freshly initialised chain.  ``value`` = iterations per second.
 config  BASELINE.json config 2 by default (synthetic 100k x 256, 10 classes, hidden [32, 8], tanh, bias nodes in input and
-        hidden layers) - the line's ``value``; the same run then times config 4 (1M x 64 regression, [16, 4], empirical sigma)
-        and config 5 (50k x 512, layer 0 in 8 blocks of 64 inputs x 4 nodes, [32, 8]) the same way and reports them under
-        ``other_configs`` (``--only`` skips that; ``--config 4`` / ``--config 5`` make one of them the line's subject).
+        hidden layers) - the line's ``value``; ``--config 4`` (1M x 64 regression, [16, 4], empirical sigma) / ``--config 5`` (50k x 512,
+        layer 0 in 8 blocks of 64 inputs x 4 nodes, [32, 8]) make one of the others the line's subject.
+full    A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints the line: the headline and what describes
+        the timed chain, nothing that needs more work on the device or the host.  ``--full`` adds, after the timed steps, everything else
+        the benchmark measures: the pass kernel timed against the HBM roofline (``roofline``), the CPU baseline, parity with the oracle,
+        the settled and moving chains, the cost of a call, the float32 layer-0 rate and - for config 2 - configs 4 and 5 and the other
+        workloads timed the same way under ``other_configs`` (``--only`` skips those; ``--no-cpu-baseline`` skips the CPU baseline and
+        every leg after it); with several GPUs, the row-sharded chain (``row_sharded_chain``).
 N GPUs  ``--gpus N``: N chains, one per GPU, MC3 layout (config 3; weak scaling); every step ends with the temperature-swap
         proposal (np_bnn/BNN_mc3.py:98-112), whose only exchange is an all-gather of [logPost, temperature] per chain over
         RCCL.  Launched by ``torch.distributed.run`` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) - or by this script
         itself: without WORLD_SIZE it starts the N rank processes before anything touches a GPU and relays rank 0's line.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5|0] [--only] [--no-cpu-baseline] [--dump-outputs DIR]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5|0] [--dump-outputs DIR] [--full [--only] [--no-cpu-baseline]]
 
 ``--dump-outputs DIR``: after the timed steps, what a caller of ``MCMC.run_steps`` holds for the measured chain (rank 0's) is written
 as ``DIR/<name>.npy`` in float64 - the weight matrices, the chain's scalars and the predictions on the training rows (a fixed, seeded
@@ -46,9 +51,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=2, choices=(2, 4, 5, 0), help="BASELINE.json config; 0 = config 2's data under the reference's default network [50,5]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--only", action="store_true", help="the named config alone: without the other single-GPU configurations that the "
-                                                         "default run (config 2) adds under other_configs")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything else the benchmark measures (roofline, CPU "
+                                                         "baseline, parity, the other configurations, the row-sharded chain): see the "
+                                                         "module's docstring")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline and the legs after it")
+    ap.add_argument("--only", action="store_true", help="with --full: the named config alone, without the other single-GPU configurations "
+                                                         "that a full run of config 2 adds under other_configs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the measured chain's weights, scalars and predictions as DIR/<name>.npy")
     return ap.parse_args()
@@ -222,7 +230,7 @@ def main():
         if comm is not None:
             comm.barrier()
 
-    spin_up(mcmc, bnn)
+    cand = spin_up(mcmc, bnn)
     advance(args.warmup)
     book = dict(acc=mcmc._device_accepted, passes=mcmc._device_passes, voids=mcmc._device_void_passes, its=mcmc._device_iterations)
     sync()
@@ -245,10 +253,10 @@ def main():
     line = None
     if rank == 0:
         its = args.steps * ITERATIONS_PER_STEP
-        line = report(args, wl, bnn, mcmc, world, el, its, book, comm_kind, nranks_seen, device_swaps)
+        line = report(args, wl, bnn, mcmc, world, el, its, book, comm_kind, nranks_seen, device_swaps, cand)
         if per_rank is not None:
             line["per_rank"] = per_rank
-    if world > 1 and not os.environ.get("NPBNN_BENCH_NO_ROW_SHARD"):
+    if world > 1 and args.full and not os.environ.get("NPBNN_BENCH_NO_ROW_SHARD"):
         # after the timed region: the other way several GPUs serve this path - ONE chain, its rows split over the ranks.  Nothing in
         # here may cost the headline line: every failure is caught and reported inside it, on every rank
         leg, why = _with_deadline(lambda: row_sharded_chain(comm, rank, world, device_index),
@@ -514,16 +522,19 @@ def spin_up(mcmc, bnn, seconds=0.25):
     check) the device has clocked down, and the clock change that follows the first new launches stalls ONE dispatch by 70-80 ms
     somewhere in the first ten - seen as config 5 at 18-20 k instead of 62 k it/s whenever it ran behind config 4's parity
     check (NPBNN_CHAIN_TIMING=1: the stall is inside the library's wait for the stream) and never when it ran first.  The
-    driver's W warm-up steps (5 x 1 ms) are too short to absorb it; the timed region is untouched."""
+    driver's W warm-up steps (5 x 1 ms) are too short to absorb it; the timed region is untouched.  Returns the candidates per pass
+    those launches evaluated (the chain's own), or None."""
     be = mcmc._backend
     ctx = getattr(be, "ctx", None) or getattr(getattr(be, "_inner", None), "ctx", None)
     if ctx is None:
-        return
+        return None
     try:
         ms, _ = ctx.time_pass(bnn._w_layers, n_candidates=mcmc.n_candidates, iters=50)
-        ctx.time_pass(bnn._w_layers, n_candidates=mcmc.n_candidates, iters=max(50, int(seconds * 1e3 / max(ms, 1e-3))))
+        _, cand = ctx.time_pass(bnn._w_layers, n_candidates=mcmc.n_candidates, iters=max(50, int(seconds * 1e3 / max(ms, 1e-3))))
+        return cand
     except Exception as e:      # noqa: BLE001 - a courtesy to the clocks, never a reason to lose the measurement
         print("[bench] spin-up skipped: %s" % e, file=sys.stderr)
+        return None
 
 
 def moving_chain(wl):
@@ -762,7 +773,8 @@ def group_pass_leg():
     return out
 
 
-def report(args, wl, bnn, mcmc, world, el, its, book, comm_kind, nranks_seen, device_swaps):
+def report(args, wl, bnn, mcmc, world, el, its, book, comm_kind, nranks_seen, device_swaps, cand):
+    """The JSON line: the headline and what describes the timed chain; with --full also every leg that needs further runs."""
     from npbnn_amd import _capi as capi
     ctx = mcmc._backend.ctx
     passes = max(1, mcmc._device_passes - book["passes"])
@@ -772,7 +784,9 @@ def report(args, wl, bnn, mcmc, world, el, its, book, comm_kind, nranks_seen, de
     accept_rate = float(mcmc._device_accepted - book["acc"]) / max(1, done)
     accept_last = float(mcmc._acceptance_rate)
     loglik = float(mcmc._logLik)
-    roof, cand = kernel_roofline(args.config, wl, ctx, bnn, mcmc, useful=done / (passes + voids))
+    roof = None
+    if args.full:
+        roof, cand = kernel_roofline(args.config, wl, ctx, bnn, mcmc, useful=done / (passes + voids))
     line = {
         "metric": "MCMC iterations/sec (full fwd+lik per proposal)",
         "value": world * its / el,
@@ -787,7 +801,7 @@ def report(args, wl, bnn, mcmc, world, el, its, book, comm_kind, nranks_seen, de
         "dtype": "f16x3-split/f32" if ctx.l0_mode() == "f16-split" else "f32",
         "dtype_note": "layer 0 (and layer 1 of tanh networks) as three fp16 matrix-core products per term on hi/lo pairs of the float32 "
                       "operands (~22 significant bits), float32 accumulation; later layers and the likelihood terms float32; every "
-                      "cross-row sum float64.  roofline.f32_path: the same kernel with float32 matrix cores",
+                      "cross-row sum float64.  roofline.f32_path (--full): the same kernel with float32 matrix cores",
         "data": "synthetic",
         "config": {"workload": wl.description + "; one chain per GPU",
                    "step": "%d Metropolis-Hastings iterations of every chain (one MC3 chain dispatch, np_bnn/BNN_mc3.py:80-85), state "
@@ -802,14 +816,15 @@ def report(args, wl, bnn, mcmc, world, el, its, book, comm_kind, nranks_seen, de
                    "loop": "device-resident chain (npbnn_chain_run), proposals pre-drawn on the host",
                    "candidates_per_pass": cand, "iterations_per_pass": done / passes, "schedule": SCHEDULES.get(used, "host loop"),
                    "void_pass_fraction": voids / (passes + voids)},
-        "roofline": roof,
         "accept_rate": accept_rate,          # rank 0, timed region
         "accept_rate_last_100": accept_last,
         "loglik": loglik,
         "schedule_timeouts": int(ctx.sync_fallbacks),
         "torch_imported": "torch" in sys.modules,
     }
-    if not args.no_cpu_baseline and world == 1:
+    if roof is not None:
+        line["roofline"] = roof
+    if args.full and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline(wl)
         line["parity"] = wl.parity(bnn, mcmc)
         # the same chain once it has settled (acceptance of the default proposal falls to a few per cent): steady-state rate

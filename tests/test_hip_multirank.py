@@ -90,7 +90,7 @@ def test_bench_two_ranks_without_torch(tmp_path):
     env = dict(os.environ)
     if n_gpus() < 2:
         env["NPBNN_BENCH_DIST_BACKEND"] = "socket"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -110,7 +110,7 @@ def test_bench_four_ranks_on_one_gpu_rehearsal(tmp_path):
     row-sharded chain over the four ranks.  (Four, not eight: a GPU box admits six processes on its card; the eight-rank run is
     the driver's, on eight GPUs.)"""
     env = dict(os.environ, NPBNN_BENCH_DIST_BACKEND="socket")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1"], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--full"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
@@ -147,7 +147,8 @@ def test_bench_under_the_drivers_launcher(tmp_path):
     if n_gpus() < 2:
         env["NPBNN_BENCH_DIST_BACKEND"] = "socket"
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                        "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                        "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
