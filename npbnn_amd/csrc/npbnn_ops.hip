@@ -122,14 +122,15 @@ __global__ void lik_kernel(int lik_kind, const double* pred, long long rows, int
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-// argmax per row (first maximum wins, np.argmax) -> confusion counts [true][predicted] or predicted-class counts
+// argmax per row (first maximum wins, and the first NaN if there is one, as np.argmax) -> confusion counts [true][predicted] or
+// predicted-class counts
 __global__ void confusion_kernel(const double* pred, long long rows, int cols, const long long* labels, unsigned long long* conf,
                                  unsigned long long* pred_counts) {
     for (long long r = (long long)blockIdx.x * kBlock + threadIdx.x; r < rows; r += (long long)gridDim.x * kBlock) {
         const double* p = pred + r * cols;
         int best = 0;
-        for (int c = 1; c < cols; ++c)
-            if (p[c] > p[best]) best = c;
+        for (int c = 1; c < cols && !isnan(p[best]); ++c)
+            if (p[c] > p[best] || isnan(p[c])) best = c;
         atomicAdd(pred_counts + best, 1ull);
         if (labels) atomicAdd(conf + labels[r] * cols + best, 1ull);
     }

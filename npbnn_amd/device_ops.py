@@ -61,28 +61,48 @@ def output_fn(z, kind, ind=None):
     return buf
 
 
-def likelihood(kind, prediction, labels, class_weight=None, instance_weight=None, lik_temp=1, sig2=None):
-    lib, dev = _lib()
+def _rows_match(what, a, rows, fn):
+    """The per-row arguments of an operator must cover exactly the rows it uses: the C operators read ``rows`` entries of each."""
+    if len(a) != rows:
+        raise ValueError("%s: %s has %d rows, the prediction rows used are %d" % (fn, what, len(a), rows))
+
+
+def likelihood(kind, prediction, labels, class_weight=None, instance_weight=None, lik_temp=1, sig2=None, sample_id=None):
+    """``sample_id`` selects the prediction's rows of a categorical likelihood, ``labels`` aligned to it, as the reference's
+    ``prediction[sample_id, labels]`` (BNN_lib.py:100-121); the other kinds ignore it, as upstream does.  Every argument is
+    checked against the rows used before the device is touched."""
     pred = capi.as_f64(prediction)
-    rows, cols = pred.shape
-    out = C.c_double(0)
+    if pred.ndim != 2:
+        raise ValueError("likelihood: the prediction must be a matrix, got shape %s" % (pred.shape,))
     lab = tg = None
     k = 0
     cw = None if class_weight is None or len(class_weight) == 0 else capi.as_f64(class_weight)
-    iw = None if instance_weight is None else capi.as_f64(instance_weight)
+    iw = None
     sg = None
     if kind == capi.LIK_CATEGORICAL:
-        if cw is not None and iw is not None:
+        if cw is not None and instance_weight is not None:
             # upstream sums a vector over axis 1 here and fails (BNN_lib.py:105); keep the failure
             raise np.exceptions.AxisError("axis 1 is out of bounds for array of dimension 1")
-        lab = np.ascontiguousarray(labels, dtype=np.int64)
+        if sample_id is not None:
+            pred = np.ascontiguousarray(pred[np.asarray(sample_id)])
+            if pred.ndim != 2:
+                raise ValueError("likelihood: sample_id must select rows of the prediction")
+        lab = np.ascontiguousarray(labels, dtype=np.int64).reshape(-1)
+        _rows_match("labels", lab, pred.shape[0], "likelihood")
+        if instance_weight is not None:
+            iw = capi.as_f64(instance_weight).reshape(-1)
+            _rows_match("instance_weight", iw, pred.shape[0], "likelihood")
     else:
         tg = capi.as_f64(labels)
         if tg.ndim == 1:
             tg = tg.reshape(-1, 1)
+        _rows_match("targets", tg, pred.shape[0], "likelihood")
         k = tg.shape[1]
         if kind == capi.LIK_GAUSS:
             sg = capi.as_f64(np.broadcast_to(1 if sig2 is None else sig2, (k,)))
+    rows, cols = pred.shape
+    out = C.c_double(0)
+    lib, dev = _lib()
     _chk(lib, lib.npbnn_op_likelihood(dev, int(kind), capi.dptr(pred), rows, cols,
                                       None if lab is None else lab.ctypes.data_as(_I64P), capi.dptr(tg), k, capi.dptr(iw),
                                       capi.dptr(cw), 0 if cw is None else cw.shape[0], float(lik_temp), capi.dptr(sg),
@@ -91,14 +111,18 @@ def likelihood(kind, prediction, labels, class_weight=None, instance_weight=None
 
 
 def _confusion(y, lab):
-    lib, dev = _lib()
     pred = capi.as_f64(y)
+    if pred.ndim != 2:
+        raise ValueError("confusion: the prediction must be a matrix, got shape %s" % (pred.shape,))
     rows, cols = pred.shape
+    if lab is not None:
+        lab = np.ascontiguousarray(lab, dtype=np.int64).reshape(-1)
+        _rows_match("labels", lab, rows, "confusion")
+    lib, dev = _lib()
     counts = np.zeros(cols, dtype=np.int64)
     conf = None
     labp = None
     if lab is not None:
-        lab = np.ascontiguousarray(lab, dtype=np.int64)
         labp = lab.ctypes.data_as(_I64P)
         conf = np.zeros((cols, cols), dtype=np.int64)
     _chk(lib, lib.npbnn_op_confusion(dev, capi.dptr(pred), rows, cols, labp,
@@ -107,14 +131,19 @@ def _confusion(y, lab):
 
 
 def _sse(y, lab, link, first_col_only):
-    lib, dev = _lib()
     pred = capi.as_f64(y)
+    if pred.ndim != 2:
+        raise ValueError("sse: the prediction must be a matrix, got shape %s" % (pred.shape,))
     tg = capi.as_f64(lab)
     if tg.ndim == 1:
         tg = tg.reshape(-1, 1)
     if first_col_only:
         tg = np.ascontiguousarray(tg[:, :1])
+    _rows_match("targets", tg, pred.shape[0], "sse")
     k = tg.shape[1]
+    if k > pred.shape[1]:
+        raise ValueError("sse: %d target columns for a prediction of %d columns" % (k, pred.shape[1]))
+    lib, dev = _lib()
     out = np.zeros(k)
     _chk(lib, lib.npbnn_op_sse(dev, capi.dptr(pred), capi.dptr(tg), pred.shape[0], pred.shape[1], k, link, capi.dptr(out)))
     return out, pred.shape[0]

@@ -26,7 +26,7 @@ class _Likelihood:
         if self.kind in (capi.LIK_GAUSS, capi.LIK_GAUSS_PRED_SIGMA) and instance_weight is not None:
             sys.exit("instance_weight not implemented for regression")     # reference: BNN_lib.py:129-130,140-141
         return device_ops.likelihood(self.kind, prediction, labels, class_weight=class_weight,
-                                     instance_weight=instance_weight, lik_temp=lik_temp, sig2=sig2)
+                                     instance_weight=instance_weight, lik_temp=lik_temp, sig2=sig2, sample_id=sample_id)
 
     def __repr__(self):
         return "<likelihood %s>" % self.__name__

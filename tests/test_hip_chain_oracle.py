@@ -22,6 +22,7 @@ import io
 
 import numpy as np
 import pytest
+import scipy.special
 
 import cases
 import oracle as orc
@@ -35,6 +36,8 @@ COMMON = 150
 
 # likelihood class of a build (npbnn::lik_class): 0 categorical, 1 Gaussian, 2 float64 row-wise (Poisson here)
 LIK_OF_LK = {0: "cat", 1: "gauss", 2: "pois"}
+# every likelihood the float64 row-wise (LK 2, "generic") builds serve: kind -> target columns
+GENERIC = {"pois": 1, "nb": 1, "nb10": 1, "nb2d": 3, "err": 4}
 
 
 def _group(mti, d, lk, fast, spec, chain, mt0s, blk_mt0s=()):
@@ -109,6 +112,14 @@ def make_data(lik, n, f, n_test=0, seed=5, x_kind="normal", k=2):
         dat["data"], dat["labels"] = dat["data"][:n], dat["labels"][:n]
     elif lik == "gauss":
         dat = cases.regression_data(seed, n, f, k, n_test)
+    elif lik == "err":
+        dat = cases.regression_data(seed, n, f, GENERIC["err"], n_test)
+    elif lik == "nb2d":                 # three count columns, each with its own log-mean
+        rs = np.random.default_rng(seed)
+        x = rs.standard_normal((n + n_test, f))
+        eta = 0.8 + x[:, :3] @ np.array([[0.5, -0.2, 0.1], [-0.4, 0.3, 0.2], [0.3, 0.1, -0.5]])
+        y = rs.poisson(np.exp(eta)).astype(float)
+        dat = dict(data=x[:n], labels=y[:n], test_data=x[n:], test_labels=y[n:])
     else:
         dat = cases.count_data(seed, n, f, n_test)
     if x_kind != "normal":
@@ -132,6 +143,13 @@ def make_chain(bn, lik, dat, widths, seed=1234, mask_blocks=0, fun="tanh", **mcm
     elif lik == "pois":
         extra = dict(estimation_mode="custom", size_output=1)
         mk.update(likelihood_f=bn.poi_likelihood, accuracy_f=bn.poi_acc)
+    elif lik in ("nb", "nb10", "nb2d"):
+        extra = dict(estimation_mode="custom", size_output=2 * GENERIC[lik])
+        mk.update({"nb": dict(likelihood_f=bn.negbin_likelihood, accuracy_f=bn.negbin_acc),
+                   "nb10": dict(likelihood_f=bn.negbin_likelihood_base10, accuracy_f=bn.negbin_acc_base10),
+                   "nb2d": dict(likelihood_f=bn.negbin_likelihood2d, accuracy_f=bn.negbin2d_acc)}[lik])
+    elif lik == "err":
+        extra = dict(estimation_mode="regression-error", output_act_fun=bn.RegressTransformError)
     mk.update(mcmc_kw)
     np.random.seed(seed)
     bnn = quiet(bn.npBNN, dat, n_nodes=list(widths), actFun=bn.ActFun(fun=fun), use_bias_node=2, prior_f=1, p_scale=1, seed=seed,
@@ -148,7 +166,28 @@ def make_chain(bn, lik, dat, widths, seed=1234, mask_blocks=0, fun="tanh", **mcm
 
 
 def _out_fn(lik):
+    if lik == "err":
+        return orc.out_regress_error
     return orc.out_softmax if lik == "cat" else orc.out_identity
+
+
+def generic_addends(lik, y, labels):
+    """S for the row-wise likelihoods: the sum over rows and columns of the absolute values of the separate addends (the count
+    log-likelihoods cancel by orders of magnitude, so their bar is relative to S, not to the sum)."""
+    g = scipy.special.gammaln
+    k = labels.shape[1]
+    with np.errstate(all="ignore"):
+        if lik == "err":
+            r = (labels - y[:, :k]) / y[:, k:2 * k]
+            return float(np.sum(0.9189385332046727 + np.abs(np.log(y[:, k:2 * k])) + 0.5 * r * r))
+        if lik == "pois":
+            return float(np.sum(np.abs(labels[:, 0] * y[:, 0]) + np.exp(y[:, 0]) + np.abs(g(labels[:, 0] + 1))))
+        kk = k if lik == "nb2d" else 1
+        b = np.log(10.0) if lik == "nb10" else 1.0
+        mean, p = np.exp(b * y[:, :kk]), 1 / (1 + np.exp(-b * y[:, kk:2 * kk]))
+        n = p * mean / (1 - p)
+        c = labels[:, :kk]
+        return float(np.sum(np.abs(g(c + n)) + np.abs(g(c + 1)) + np.abs(g(n)) + np.abs(n * np.log(p)) + np.abs(c * np.log1p(-p))))
 
 
 def _accuracy_ok(got, y64, labels):
@@ -166,7 +205,9 @@ def oracle_loglik(lik, x, labels, weights, fun="tanh"):
             return orc.lik_categorical(y, labels, np.arange(len(x))), y
     if lik == "gauss":
         return orc.lik_gaussian(y, labels, None, sig2=np.ones(labels.shape[1])), y
-    return orc.lik_poisson(y, labels, None), y
+    if lik == "err":
+        return orc.lik_gaussian_error(y, labels, None), y
+    return {"pois": orc.lik_poisson, "nb": orc.lik_negbin, "nb10": orc.lik_negbin_base10, "nb2d": orc.lik_negbin2d}[lik](y, labels), y
 
 
 def check_state(lik, bnn, mcmc, worst=None, accuracy=True):
@@ -174,7 +215,10 @@ def check_state(lik, bnn, mcmc, worst=None, accuracy=True):
     Returns the relative log-likelihood error."""
     w = bnn._w_layers
     want, y = oracle_loglik(lik, bnn._data, bnn._labels, w)
-    err = abs(mcmc._logLik - want) / max(abs(want), 1e-300)      # (one row of one class: both are 0 exactly)
+    if lik in GENERIC and lik != "pois":         # (relative to S: test_hip_generic_lik's forward bar)
+        err = abs(mcmc._logLik - want) / generic_addends(lik, y, bnn._labels)
+    else:
+        err = abs(mcmc._logLik - want) / max(abs(want), 1e-300)      # (one row of one class: both are 0 exactly)
     assert err <= LL_RTOL, ("logLik", mcmc._logLik, want, err)
     lp = orc.log_prior(w, bnn._prior_kind() if bnn._prior else 0, bnn._prior_scale)
     assert abs(mcmc._logPrior - lp) <= LP_RTOL * max(1.0, abs(lp)), ("logPrior", mcmc._logPrior, lp)
@@ -185,9 +229,14 @@ def check_state(lik, bnn, mcmc, worst=None, accuracy=True):
             y_t = orc.forward(bnn._test_data, w, orc.Act("tanh"), orc.out_softmax)
             ok, info = _accuracy_ok(mcmc._test_accuracy, y_t, bnn._test_labels)
             assert ok, ("test accuracy", info)
-    elif accuracy and lik == "gauss":
+    elif accuracy and lik in ("gauss", "err"):
         want_mse = float(np.mean(orc.mse_per_column(y, bnn._labels)))
         assert abs(mcmc._accuracy - want_mse) <= ACC_TOL * max(1.0, want_mse), ("mse", mcmc._accuracy, want_mse)
+    elif accuracy and lik in GENERIC and lik != "pois":       # negbin_acc / negbin_acc_base10 / negbin2d_acc (BNN_lik.py:81-91)
+        kk = bnn._labels.shape[1] if lik == "nb2d" else 1
+        mean = 10.0 ** y[:, :kk] if lik == "nb10" else np.exp(y[:, :kk])
+        want_mse = float(np.mean((mean - bnn._labels[:, :kk]) ** 2))
+        assert abs(mcmc._accuracy - want_mse) <= ACC_TOL * max(1.0, want_mse), ("count mse", mcmc._accuracy, want_mse)
     if worst is not None:
         worst.append(err)
     return err
@@ -596,3 +645,27 @@ def test_set_arch_again_between_batches(path, bn, report, monkeypatch):
     drive("cat", bnn2, mcmc2, 40, seed=3, worst=errs)
     assert ctx.is_wide() == (path == "streamed")
     _note(report, "set_arch again", errs)
+
+
+# ---- every float64 row-wise likelihood --------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("path", ["resident", "streamed"])
+@pytest.mark.parametrize("widths", [(20, 6), (20, 40)], ids=["mti1", "mti8"])
+@pytest.mark.parametrize("lik", list(GENERIC))
+def test_generic_likelihood_chain_against_float64(lik, widths, path, bn, report, monkeypatch):
+    """Chains of every kind the generic builds serve - Poisson, NegBin, NegBin base 10, NegBin2D (3 count columns) and the
+    predicted-sigma Gaussian (4 targets) - on 20 000 rows with a test table, later layers <= 16 (MTI 1) and of 40 nodes (MTI 8),
+    resident and with the streamed path forced: after every dispatch the chain's logLik is float64's on its current weights,
+    within 2e-6 of S (the sum of the absolute values of the likelihood's addends: count log-likelihoods cancel)."""
+    if path == "streamed":
+        monkeypatch.setenv("NPBNN_FORCE_WIDE", "1")
+    dat = make_data(lik, 20000, 16, n_test=700, seed=21)
+    bnn, mcmc = make_chain(bn, lik, dat, widths)
+    assert mcmc._backend.ctx.is_wide() == (path == "streamed")
+    mcmc.SUB_BATCH = 16
+    errs = [check_state(lik, bnn, mcmc)]
+    before = mcmc._device_iterations
+    dec = drive(lik, bnn, mcmc, 300, seed=len(lik), worst=errs, accuracy_every=2)
+    assert mcmc._device_iterations - before == 300, "the chain did not run on the device"
+    assert sum(dec) > 0, "no proposal was accepted"
+    _note(report, "generic_%s" % lik, errs)
