@@ -221,6 +221,18 @@ int npbnn_predict_sets(npbnn_ctx* ctx, const double* W_sets, const double* act_p
 int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, const int32_t* focal, int32_t n_focal,
                       const double* grid, int32_t n_grid, const double* col_override, int which, int apply_out_fn, double* out_mean);
 
+/* Posterior credible intervals: calcHPD (np_bnn/BNN_lib.py:286-302) applied to every (row, output) of the n_sets stored samples'
+ * predictions, as its summary code does once per row (np_bnn/BNN_plot.py:73-75).  The sets replay as in npbnn_predict_sets, but
+ * each group writes its float32 predictions into a device stack [n_sets][n_rows][out_dim] that never leaves the device; one HPD
+ * launch then reads it once.  out_mean / out_lo / out_hi [n_rows][out_dim]: the mean over the sets (float64 sum) and the bounds of
+ * the narrowest window holding nIn = round(level * n_sets) values (round half to even), the first one among equally narrow ones;
+ * widths in float64 from the float32 values, so the bounds are calcHPD's on the float64 array npbnn_predict_sets returns.
+ * NPBNN_E_ARG: more than 16384 sets, level outside (0, 1), nIn < 2, or a prediction that is NaN or infinite.  NPBNN_E_NOMEM: the
+ * stack is over its byte budget (1 GiB; NPBNN_HPD_STACK_BYTES in the environment overrides it), the message names the largest row
+ * count that fits. */
+int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which, int apply_out_fn,
+                           double level, double* out_mean, double* out_lo, double* out_hi);
+
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events
  * around each launch) and of the whole evaluation, in milliseconds. */
@@ -393,6 +405,16 @@ int npbnn_op_confusion(int device, const double* pred, int64_t rows, int32_t col
                        int64_t* pred_counts);
 int npbnn_op_sse(int device, const double* pred, const double* targets, int64_t rows, int32_t cols_pred, int32_t k, int link,
                  double* out_per_col);
+
+/* npbnn_op_hpd: calcHPD (np_bnn/BNN_lib.py:286-302) of each of n_cols columns, column c's n_samples values at
+ * values[s * col_stride + c] (value_type NPBNN_VALUE_F64 or NPBNN_VALUE_F32; window widths are computed in that type, as upstream
+ * computes them in the type of its input).  out_lo / out_hi [n_cols]: the bounds of the first narrowest window holding
+ * nIn = round(level * n_samples) sorted values (round half to even).  NPBNN_E_ARG: more than 16384 samples, level outside (0, 1),
+ * nIn < 2, or a value that is NaN or infinite. */
+#define NPBNN_VALUE_F64 0
+#define NPBNN_VALUE_F32 1
+int npbnn_op_hpd(int device, const void* values, int value_type, int64_t n_samples, int64_t n_cols, int64_t col_stride, double level,
+                 double* out_lo, double* out_hi);
 
 /* ---- MC3 temperature-swap exchange over RCCL (xGMI inside a node): replaces the multiprocessing pool
  * round trip of whole pickled chains in MC3.run_mcmc (np_bnn/BNN_mc3.py:94-112), of which the swap

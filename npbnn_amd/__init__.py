@@ -31,6 +31,7 @@ from .mc3 import MC3  # noqa: F401
 from .posterior import (feature_importance, get_posterior_cat_prob, get_posterior_est, predictBNN,  # noqa: F401
                         sample_from_categorical)
 from .pdp import get_feature_summary, get_pdp, make_pdp_features, pdp  # noqa: F401
+from .hpd import calcHPD, get_posterior_hpd, posterior_hpd  # noqa: F401
 from . import comm  # noqa: F401
 
 BNN = npBNN                       # BASELINE.json's wording

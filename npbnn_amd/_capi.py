@@ -31,6 +31,9 @@ INFO_IT_NS_OVERLAPPED, INFO_IT_NS_BETWEEN = 8, 9
 INFO_WIDE = 10
 INFO_F16_MOVED_COLUMNS, INFO_F16_MAX_MOVE = 11, 12
 INFO_PDP_ROUTE = 13
+VALUE_F64, VALUE_F32 = 0, 1
+E_ARG = -1
+E_NOMEM = -4
 E_RANGE = -6
 E_SYNC = -7
 E_INTERNAL = -8
@@ -135,6 +138,7 @@ SIGNATURES = {
     "npbnn_predict_sets": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, _DP]),
     "npbnn_predict_pdp": (C.c_int, [_P, _DP, _DP, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _DP, C.c_int32, _DP, C.c_int,
                                     C.c_int, _DP]),
+    "npbnn_predict_sets_hpd": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
     "npbnn_time_eval": (C.c_int, [_P, _DP, C.c_int, _DP, _DP]),
     "npbnn_time_pass": (C.c_int, [_P, _DP, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
     "npbnn_time_wide": (C.c_int, [_P, _DP, C.c_int, _DP, _DP, C.POINTER(C.c_int)]),
@@ -156,6 +160,7 @@ SIGNATURES = {
     "npbnn_op_confusion": (C.c_int, [C.c_int, _DP, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64)]),
     "npbnn_op_sse": (C.c_int, [C.c_int, _DP, _DP, C.c_int64, C.c_int32, C.c_int32, C.c_int, _DP]),
+    "npbnn_op_hpd": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _DP, _DP]),
     "npbnn_comm_unique_id": (C.c_int, [C.c_char * 128]),
     "npbnn_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char * 128, C.POINTER(_P)]),
     "npbnn_comm_allgather_f64": (C.c_int, [_P, _DP, C.c_int, _DP]),

@@ -274,6 +274,23 @@ class HipContext:
                                                1 if apply_out_fn else 0, capi.dptr(out)))
         return out
 
+    def predict_sets_hpd(self, weight_sets, level=0.95, act_prm_sets=None, which=capi.TRAIN, apply_out_fn=True):
+        """Posterior mean and HPD interval of several weight sets' predictions on the resident matrix (npbnn_predict_sets_hpd):
+        ``(mean, lower, upper)``, each [n_rows, n_out].  The sets replay as in ``predict_sets`` into a float32 stack that stays
+        on the device; the bounds equal calcHPD's on the float64 array ``predict_sets`` returns."""
+        packed = capi.as_f64(np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel()
+                                       for w in weight_sets]))
+        n_sets = packed.shape[0]
+        ap = None
+        if act_prm_sets is not None and self.arch.n_layers > 1:
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        shape = (self.n_rows[which], self.n_out)
+        mean, lo, hi = np.empty(shape), np.empty(shape), np.empty(shape)
+        self._chk(self._lib.npbnn_predict_sets_hpd(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which,
+                                                   1 if apply_out_fn else 0, float(level), capi.dptr(mean), capi.dptr(lo),
+                                                   capi.dptr(hi)))
+        return mean, lo, hi
+
     def predict_pdp(self, weight_sets, focal, grid, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
         prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]

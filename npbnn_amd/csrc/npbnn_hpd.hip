@@ -1,0 +1,292 @@
+// Highest-posterior-density intervals (include/npbnn_hip.h): calcHPD of np_bnn/BNN_lib.py:286-302 over many columns at once.
+//
+// calcHPD sorts one vector of S values, takes nIn = round(level * S) of them (round half to even: nearbyint under the default
+// rounding mode) and returns the first window d[k] .. d[k + nIn - 1] of smallest width (a later window replaces the best only when
+// strictly narrower).  hpd_kernel gives each workgroup a tile of TC adjacent columns: the tile is read sample row by sample row
+// (adjacent columns are contiguous, so a row of the tile is one coalesced read), transposed into LDS as TC columns of P = next
+// power of two >= S values (padded with +inf, column pitch P + 1 against bank conflicts) and sorted there by a bitonic network.
+// Each wave then scans the windows of its columns - widths in W, the input's type for npbnn_op_hpd and float64 for the float32
+// stack of npbnn_predict_sets_hpd - and a shuffle reduction picks the smallest width, the smallest k among equal ones.  The mean
+// (float64 sum in a fixed order) comes from the same LDS copy.  No atomics but the non-finite flag, no scratch.
+//
+// npbnn_predict_sets_hpd replays the stored sets as npbnn_predict_sets does (np_bnn/BNN_lib.py:375-381, 715-748: groups of sets
+// that share their slopes, up to kMaxCand per read of X on the resident path, one on the weight-streamed path, the float32 retry
+// after the fp16 range flag), each group writing its float32 predictions straight into a device stack [S][rows][C]; one launch of
+// hpd_kernel then reads the stack once.
+#include "npbnn_ctx.hip.h"
+
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+namespace npbnn_api {
+
+namespace {
+
+constexpr int kHpdThreads = 256;
+constexpr int kHpdMaxSamples = 16384;
+constexpr int kHpdMaxTile = 64;                        // columns of a workgroup at most
+constexpr size_t kHpdTileLds = 80 * 1024;              // LDS a tile may take when it holds more than one column (two per CU)
+constexpr size_t kHpdStackBytes = 1ull << 30;          // default budget of npbnn_predict_sets_hpd's float32 stack
+
+struct HpdParams {
+    const void* values;       // values[s * col_stride + c]
+    long long n_cols, col_stride;
+    int S, P, log2P, n_in, tile, log2tile;
+    double* lo;
+    double* hi;
+    double* mean;             // or nullptr
+    int* flag;                // bit 0: a value is not finite
+};
+
+template <class T, class W>
+__global__ __launch_bounds__(kHpdThreads) void hpd_kernel(HpdParams p) {
+    extern __shared__ __align__(16) unsigned char hpd_lds[];
+    T* sh = reinterpret_cast<T*>(hpd_lds);
+    const T* values = static_cast<const T*>(p.values);
+    const int pitch = p.P + 1;
+    const long long c0 = (long long)blockIdx.x * p.tile;
+    const int tc = (int)min((long long)p.tile, p.n_cols - c0);
+
+    // ---- the tile, sample row by sample row, into LDS columns; +inf past S
+    bool bad = false;
+    for (int i = threadIdx.x; i < (p.P << p.log2tile); i += kHpdThreads) {
+        const int s = i >> p.log2tile, c = i & (p.tile - 1);
+        T v = (T)INFINITY;
+        if (s < p.S && c < tc) {
+            v = values[(long long)s * p.col_stride + c0 + c];
+            if (!isfinite(v)) bad = true;
+        }
+        sh[c * pitch + s] = v;
+    }
+    if (bad) atomicOr(p.flag, 1);
+
+    // ---- bitonic sort of every column, ascending
+    const int log2half = p.log2P - 1;
+    const int n_pairs = tc << log2half;
+    for (int k = 2; k <= p.P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (int t = threadIdx.x; t < n_pairs; t += kHpdThreads) {
+                const int c = t >> log2half, q = t & ((1 << log2half) - 1);
+                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1));
+                T* col = sh + c * pitch;
+                const T a = col[i], b = col[i + j];
+                if ((a > b) == ((i & k) == 0)) {
+                    col[i] = b;
+                    col[i + j] = a;
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- per column (one wave each): the first narrowest window, and the mean
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = p.S - p.n_in + 1;
+    for (int c = wave; c < tc; c += kHpdThreads / 64) {
+        const T* col = sh + c * pitch;
+        W best = (W)0;
+        int bk = -1;
+        for (int k = lane; k < m; k += 64) {
+            const W w = (W)col[k + p.n_in - 1] - (W)col[k];
+            if (bk < 0 || w < best) { best = w; bk = k; }
+        }
+        double sum = 0.0;
+        if (p.mean)
+            for (int s = lane; s < p.S; s += 64) sum += (double)col[s];
+        for (int off = 32; off > 0; off >>= 1) {
+            const W ob = __shfl_xor(best, off);
+            const int ok = __shfl_xor(bk, off);
+            if (ok >= 0 && (bk < 0 || ob < best || (ob == best && ok < bk))) { best = ob; bk = ok; }
+            sum += __shfl_xor(sum, off);
+        }
+        if (lane == 0) {
+            p.lo[c0 + c] = (double)col[bk];
+            p.hi[c0 + c] = (double)col[bk + p.n_in - 1];
+            if (p.mean) p.mean[c0 + c] = sum / (double)p.S;
+        }
+    }
+}
+
+template <class T>
+int dev_alloc(npbnn_ctx* ctx, DevBuf<T>& b, size_t n) {
+    return b.reserve(ctx, n ? n : 16 / sizeof(T));
+}
+
+int ilog2(long long v) {
+    int r = 0;
+    while ((1ll << r) < v) ++r;
+    return r;
+}
+
+// nIn of calcHPD, or an error through fail(ctx, ...)
+int hpd_window(npbnn_ctx* ctx, const char* who, long long S, double level, int* n_in) {
+    if (!(level > 0.0 && level < 1.0)) return fail(ctx, NPBNN_E_ARG, "%s: level %g outside (0, 1)", who, level);
+    if (S > kHpdMaxSamples) return fail(ctx, NPBNN_E_ARG, "%s: %lld samples, at most %d", who, S, kHpdMaxSamples);
+    const double r = nearbyint(level * (double)S);
+    if (r < 2.0) return fail(ctx, NPBNN_E_ARG, "%s: too little data to calculate marginal parameters (round(%g * %lld) < 2)", who, level, S);
+    *n_in = (int)r;
+    return NPBNN_OK;
+}
+
+// hpd_kernel over n_cols columns of the device array `values` (T = float or double, widths in W); lo / hi / mean device arrays
+// [n_cols].  Returns NPBNN_E_ARG when a value is not finite.
+template <class T, class W>
+int launch_hpd(npbnn_ctx* ctx, hipStream_t stream, const char* who, const T* values, long long S, long long n_cols, long long col_stride,
+               int n_in, double* lo, double* hi, double* mean) {
+    HpdParams p{};
+    p.values = values;
+    p.n_cols = n_cols;
+    p.col_stride = col_stride;
+    p.S = (int)S;
+    p.log2P = ilog2(S);
+    p.P = 1 << p.log2P;
+    p.n_in = n_in;
+    const size_t col_bytes = (size_t)(p.P + 1) * sizeof(T);
+    p.tile = 1;
+    while (p.tile < kHpdMaxTile && (size_t)(2 * p.tile) * col_bytes <= kHpdTileLds && 2 * p.tile <= n_cols) p.tile *= 2;
+    p.log2tile = ilog2(p.tile);
+    p.lo = lo;
+    p.hi = hi;
+    p.mean = mean;
+    DevBuf<int> flag;
+    int rc = dev_alloc(ctx, flag, 1);
+    if (rc) return rc;
+    p.flag = flag.get();
+    HIP_TRY(ctx, hipMemsetAsync(p.flag, 0, sizeof(int), stream));
+    const size_t lds = (size_t)p.tile * col_bytes;      // <= 16385 * 8 bytes for one column of 16384 float64 values
+    const void* fn = reinterpret_cast<const void*>(hpd_kernel<T, W>);
+    HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const long long blocks = (n_cols + p.tile - 1) / p.tile;
+    hipLaunchKernelGGL((hpd_kernel<T, W>), dim3((unsigned)blocks), dim3(kHpdThreads), lds, stream, p);
+    HIP_TRY(ctx, hipGetLastError());
+    int bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, p.flag, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (bad) return fail(ctx, NPBNN_E_ARG, "%s: a value is NaN or infinite", who);
+    return NPBNN_OK;
+}
+
+}  // namespace
+
+}  // namespace npbnn_api
+
+using namespace npbnn_api;
+
+extern "C" int npbnn_op_hpd(int device, const void* values, int value_type, int64_t n_samples, int64_t n_cols, int64_t col_stride,
+                            double level, double* out_lo, double* out_hi) {
+    if (!values || !out_lo || !out_hi || n_cols < 0 || col_stride < n_cols || n_samples < 1 ||
+        (value_type != NPBNN_VALUE_F64 && value_type != NPBNN_VALUE_F32))
+        return fail(nullptr, NPBNN_E_ARG, "op_hpd: bad arguments");
+    int n_in = 0;
+    int rc = hpd_window(nullptr, "op_hpd", n_samples, level, &n_in);
+    if (rc) return rc;
+    if (n_cols == 0) return NPBNN_OK;
+    HIP_TRY(nullptr, hipSetDevice(device));
+    const size_t esize = value_type == NPBNN_VALUE_F64 ? 8 : 4;
+    const size_t n_el = (size_t)(n_samples - 1) * (size_t)col_stride + (size_t)n_cols;
+    DevBuf<double> d_v, d_lo, d_hi;          // (d_v: n_el values of esize bytes)
+    if ((rc = dev_alloc(nullptr, d_v, (n_el * esize + 7) / 8))) return rc;
+    if ((rc = dev_alloc(nullptr, d_lo, (size_t)n_cols))) return rc;
+    if ((rc = dev_alloc(nullptr, d_hi, (size_t)n_cols))) return rc;
+    HIP_TRY(nullptr, hipMemcpy(d_v.get(), values, n_el * esize, hipMemcpyHostToDevice));
+    if (value_type == NPBNN_VALUE_F64)
+        rc = launch_hpd<double, double>(nullptr, nullptr, "op_hpd", d_v.get(), n_samples, n_cols, col_stride, n_in, d_lo, d_hi, nullptr);
+    else
+        rc = launch_hpd<float, float>(nullptr, nullptr, "op_hpd", reinterpret_cast<const float*>(d_v.get()), n_samples, n_cols, col_stride,
+                                      n_in, d_lo, d_hi, nullptr);
+    if (rc) return rc;
+    HIP_TRY(nullptr, hipMemcpy(out_lo, d_lo.get(), (size_t)n_cols * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(nullptr, hipMemcpy(out_hi, d_hi.get(), (size_t)n_cols * 8, hipMemcpyDeviceToHost));
+    return NPBNN_OK;
+}
+
+extern "C" int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
+                                      int apply_out_fn, double level, double* out_mean, double* out_lo, double* out_hi) {
+    if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
+    if (!W_sets || !out_mean || !out_lo || !out_hi || n_sets < 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_hpd: bad arguments");
+    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_hpd: which must be 0 or 1");
+    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_hpd: call npbnn_set_arch first");
+    int n_in = 0;
+    int rc = hpd_window(ctx, "predict_sets_hpd", n_sets, level, &n_in);
+    if (rc) return rc;
+    Dataset& d = ctx->ds[which];
+    if ((rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE))) return rc;
+    const int C = ctx->net.n_out;
+    const int n_act = ctx->net.n_layers - 1;
+    const size_t per_set = (size_t)d.n_rows * C;
+    const size_t wn = (size_t)ctx->n_weights;
+    size_t budget = kHpdStackBytes;
+    if (const char* e = getenv("NPBNN_HPD_STACK_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    const size_t row_bytes = (size_t)n_sets * C * sizeof(float);
+    if ((size_t)d.n_rows * row_bytes > budget)
+        return fail(ctx, NPBNN_E_NOMEM, "predict_sets_hpd: the [%d][%lld][%d] float32 stack takes %zu bytes, over the budget of %zu "
+                    "(NPBNN_HPD_STACK_BYTES); at most %zu rows fit", n_sets, (long long)d.n_rows, C, (size_t)d.n_rows * row_bytes,
+                    budget, budget / row_bytes);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf<float> stack;
+    DevBuf<double> d_res;
+    if ((rc = dev_alloc(ctx, stack, (size_t)n_sets * per_set))) return rc;
+    if ((rc = dev_alloc(ctx, d_res, 3 * per_set))) return rc;
+    std::vector<double> wstage(kMaxCand * wn);
+    int s0 = 0;
+    while (s0 < n_sets) {
+        // sets that share their activation slopes travel together, up to kMaxCand per streaming read of X (npbnn_predict_sets)
+        int g = 1;
+        while (s0 + g < n_sets && g < kMaxCand &&
+               (!act_prm_sets || n_act == 0 ||
+                memcmp(act_prm_sets + (size_t)(s0 + g) * n_act, act_prm_sets + (size_t)s0 * n_act, (size_t)n_act * sizeof(double)) == 0))
+            ++g;
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            LaunchPlan lp;
+            rc = plan_launch(ctx, which, &lp, attempt, g, true);
+            if (rc) return rc;
+            if (lp.n_cand < g) g = lp.n_cand;
+            memcpy(wstage.data(), W_sets + (size_t)s0 * wn, (size_t)g * wn * sizeof(double));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_wraw, wstage.data(), (size_t)g * wn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            for (int l = 0; l < kMaxLayers; ++l) ctx->net.act_prm[l] = 0.f;
+            if (act_prm_sets)
+                for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), ctx->stream));
+            for (int j = 0; j < g; ++j)
+                launch_pack_weights(ctx, ctx->d_wraw + (size_t)j * wn, nullptr, ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
+            HIP_TRY(ctx, hipGetLastError());
+            EvalParams p = make_params(ctx, d);
+            p.labels = nullptr;
+            p.targets = nullptr;
+            p.net.lik_kind = NPBNN_LIK_NONE;
+            p.y_out = stack.get() + (size_t)s0 * per_set;          // sets s0 .. s0 + g - 1 of the stack
+            p.predict_mode = apply_out_fn ? 2 : 1;
+            p.weight_sets = 1;
+            p.lay = layout_for(ctx, d, true);
+            rc = push_eval_params(ctx, p);
+            if (rc) return rc;
+            rc = launch_plain_eval(ctx, lp, which);
+            if (rc) return rc;
+            HIP_TRY(ctx, hipGetLastError());
+            int ovf = 0;
+            HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            // (push_eval_params stages through one pinned slot: the launch that reads it must be in before the next write)
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "predict_sets_hpd: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is");
+            if (!(ctx->net.l0_f16 && (ovf & kFlagF16Range))) break;
+            if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "predict_sets_hpd: a layer-0 weight left the fp16 range");
+        }
+        s0 += g;
+    }
+    // bounds from the float32 values with float64 widths: upstream's calcHPD on the float64 array npbnn_predict_sets returns
+    double* lo = d_res.get();
+    double* hi = lo + per_set;
+    double* mean = hi + per_set;
+    rc = launch_hpd<float, double>(ctx, ctx->stream, "predict_sets_hpd", stack.get(), n_sets, (long long)per_set, (long long)per_set,
+                                   n_in, lo, hi, mean);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(out_lo, lo, per_set * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_hi, hi, per_set * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_mean, mean, per_set * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NPBNN_OK;
+}

@@ -34,18 +34,34 @@ class _SamplePredictor:
         self._ctx = HipContext()
         self._arch_set = False
 
-    def predict(self, features):
-        """[n_samples, n_rows, n_out] predictions of every stored sample on ``features``."""
+    def _load(self, features):
         ctx = self._ctx
         ctx.set_data(features)
         if not self._arch_set:
             ctx.set_arch_from_weights(self._weights[0], self._n_features, self._act.device_kind(),
                                       capi.OUT_IDENTITY if self._kind is None else self._kind, capi.LIK_NONE)
             self._arch_set = True
+        return ctx
+
+    def predict(self, features):
+        """[n_samples, n_rows, n_out] predictions of every stored sample on ``features``."""
+        ctx = self._load(features)
         y = ctx.predict_sets(list(self._packed), act_prm_sets=self._slopes, apply_out_fn=self._kind is not None)
         if self._kind is None and self._out_fn is not None:      # custom output callable: host side, sample by sample
             y = np.array([self._out_fn(yi) for yi in y])
         return y
+
+    def predict_hpd(self, features, level):
+        """(mean, lower, upper) [n_rows, n_out] over the stored samples' predictions on ``features``; the stack stays on the
+        device (npbnn_predict_sets_hpd).  A custom output callable has no device kind: its stack is built on the host and goes
+        through ``posterior_hpd``."""
+        if self._kind is None and self._out_fn is not None:
+            from .hpd import posterior_hpd
+            y = self.predict(features)
+            lo, hi = posterior_hpd(y, level)
+            return np.mean(y, axis=0), lo, hi
+        ctx = self._load(features)
+        return ctx.predict_sets_hpd(list(self._packed), level, act_prm_sets=self._slopes, apply_out_fn=self._kind is not None)
 
     def close(self):
         self._ctx.close()
