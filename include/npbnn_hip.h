@@ -180,7 +180,11 @@ enum { NPBNN_L0_AUTO = 0, NPBNN_L0_F32 = 1, NPBNN_L0_F16 = 2 };
 enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 3, NPBNN_INFO_FAST_TAILS = 4,
        NPBNN_INFO_TURN_NS_OVERLAPPED = 5, NPBNN_INFO_TURN_NS_BETWEEN = 6, NPBNN_INFO_MAX_CANDIDATES = 7,
        NPBNN_INFO_IT_NS_OVERLAPPED = 8, NPBNN_INFO_IT_NS_BETWEEN = 9, NPBNN_INFO_WIDE = 10,
-       NPBNN_INFO_F16_MOVED_COLUMNS = 11, NPBNN_INFO_F16_MAX_MOVE = 12, NPBNN_INFO_PDP_ROUTE = 13 };
+       NPBNN_INFO_F16_MOVED_COLUMNS = 11, NPBNN_INFO_F16_MAX_MOVE = 12, NPBNN_INFO_PDP_ROUTE = 13,
+       /* with NPBNN_FI_TIMING=1 in the environment (HIP events; 0 otherwise): device time in nanoseconds of the last
+        * npbnn_permute_columns (restore, gather and the patch of the split copies), and of the last npbnn_predict_sets_summary's
+        * evaluation passes (weight packing included), accumulation launches and final kernel */
+       NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -232,6 +236,33 @@ int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const double* act_pr
  * count that fits. */
 int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which, int apply_out_fn,
                            double level, double* out_mean, double* out_lo, double* out_hi);
+
+/* Permutation importance (feature_importance, np_bnn/BNN_lib.py:504-597) without leaving the device.
+ *
+ * npbnn_permute_columns replaces the copy of the feature matrix and the shuffle of some of its columns at the top of
+ * get_posterior_cat_prob (np_bnn/BNN_lib.py:364-371) and the upload that would follow: column cols[j] of the resident matrix `which`
+ * reads X0[perm[p][r]][cols[j]] in row r, X0 being the matrix as npbnn_set_data_* left it; p = 0 for every column when n_perm == 1
+ * (the block moves as a whole, :371), p = j when n_perm == n_cols (every column by its own permutation, :368-369).  perm:
+ * [n_perm][n_rows] int64 row indices.  A call first puts back the columns the previous call moved (the library keeps those columns
+ * alone, n_rows x n_cols floats); n_cols == 0 or perm == NULL only puts them back.  The fp16-split copies are patched in the moved
+ * columns under the column scales they were built with (a column's largest entry does not move with its rows).
+ * NPBNN_E_STATE: the matrix is borrowed (npbnn_share_data) or other contexts borrow it.  NPBNN_E_ARG: a column outside the matrix
+ * or named twice, n_perm not in {1, n_cols}, or a row index outside [0, n_rows) (found on the device before anything is written:
+ * the matrix stays as it was).  npbnn_set_data_* drops the saved columns. */
+int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* cols, int32_t n_cols, const int64_t* perm, int32_t n_perm);
+
+/* Summary of the n_sets stored samples' predictions on the resident matrix `which`, and its confusion table: the loop over
+ * RunPredict and the summary of get_posterior_cat_prob (np_bnn/BNN_lib.py:375-392) and CalcAccuracy's argmax against the labels
+ * (:203-209), with nothing but the results leaving the device.  The sets replay as in npbnn_predict_sets; each group's float32
+ * predictions are folded into a device accumulator before the next group overwrites them.
+ *   mode 0  out_summary[r][c] = share of the sets whose largest prediction in row r is class c, the first such class (:382-390);
+ *   mode 1  out_summary[r][c] = mean of the sets' predictions, the float32 values added in float64 in set order (:391-392).
+ * out_summary: [n_rows][out_dim] float64, or NULL.  labels: [n_rows] int64 in [0, out_dim), or NULL; out_confusion:
+ * [out_dim][out_dim] int64, [label][argmax of the summary row, the first class among equal ones], or NULL (labels and
+ * out_confusion go together; out_summary and out_confusion both NULL is an error).  NPBNN_E_ARG also for a prediction that is
+ * NaN and for a label outside the classes. */
+int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
+                               int apply_out_fn, int mode, const int64_t* labels, double* out_summary, int64_t* out_confusion);
 
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events

@@ -31,8 +31,10 @@ INFO_IT_NS_OVERLAPPED, INFO_IT_NS_BETWEEN = 8, 9
 INFO_WIDE = 10
 INFO_F16_MOVED_COLUMNS, INFO_F16_MAX_MOVE = 11, 12
 INFO_PDP_ROUTE = 13
+INFO_PERMUTE_NS, INFO_SUMMARY_PASS_NS, INFO_SUMMARY_ACC_NS, INFO_SUMMARY_FINAL_NS = 14, 15, 16, 17
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
+E_STATE = -2
 E_NOMEM = -4
 E_RANGE = -6
 E_SYNC = -7
@@ -139,6 +141,9 @@ SIGNATURES = {
     "npbnn_predict_pdp": (C.c_int, [_P, _DP, _DP, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _DP, C.c_int32, _DP, C.c_int,
                                     C.c_int, _DP]),
     "npbnn_predict_sets_hpd": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
+    "npbnn_permute_columns": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_int32]),
+    "npbnn_predict_sets_summary": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _DP,
+                                             C.POINTER(C.c_int64)]),
     "npbnn_time_eval": (C.c_int, [_P, _DP, C.c_int, _DP, _DP]),
     "npbnn_time_pass": (C.c_int, [_P, _DP, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
     "npbnn_time_wide": (C.c_int, [_P, _DP, C.c_int, _DP, _DP, C.POINTER(C.c_int)]),

@@ -291,6 +291,57 @@ class HipContext:
                                                    capi.dptr(hi)))
         return mean, lo, hi
 
+    def permute_columns(self, cols, perms, which=capi.TRAIN):
+        """Shuffle columns of the resident matrix between its rows, on the device (npbnn_permute_columns): column ``cols[j]`` reads
+        ``X0[perms[p][r], cols[j]]`` in row ``r``, ``X0`` being the matrix as ``set_data`` left it - ``perms`` [1, n_rows] moves the
+        block as a whole, [len(cols), n_rows] every column by its own permutation.  The columns an earlier call moved go back
+        first; no columns (or ``perms`` None) only puts them back."""
+        c = np.ascontiguousarray(np.asarray(cols, dtype=np.int64).ravel(), dtype=np.int32)
+        if perms is None or len(c) == 0:
+            self._chk(self._lib.npbnn_permute_columns(self._ctx, which, None, 0, None, 0))
+            return
+        p = np.ascontiguousarray(perms, dtype=np.int64)
+        if p.ndim == 1:
+            p = p.reshape(1, -1)
+        if p.ndim != 2 or p.shape[0] not in (1, len(c)):
+            raise ValueError("permute_columns: %s permutations for %d columns (one for the block, or one per column)" % (p.shape[:-1], len(c)))
+        if p.shape[1] != self.n_rows[which]:
+            raise ValueError("permute_columns: permutations of %d rows but the matrix has %d" % (p.shape[1], self.n_rows[which]))
+        self._chk(self._lib.npbnn_permute_columns(self._ctx, which, c.ctypes.data_as(C.POINTER(C.c_int32)), len(c),
+                                                  p.ctypes.data_as(C.POINTER(C.c_int64)), p.shape[0]))
+
+    def predict_sets_summary(self, weight_sets, mode, labels=None, act_prm_sets=None, which=capi.TRAIN, want_summary=True,
+                             apply_out_fn=True):
+        """Summary over several weight sets' predictions on the resident matrix, and its confusion table against ``labels``
+        (npbnn_predict_sets_summary): ``(summary [n_rows, n_out] or None, confusion [n_out, n_out] int64 or None)``.  ``mode`` 0:
+        the share of the sets whose largest prediction is the class; 1: the mean prediction.  The sets replay as in
+        ``predict_sets``; the per-set predictions stay on the device."""
+        if mode not in (0, 1):
+            raise ValueError("predict_sets_summary: mode must be 0 (votes) or 1 (mean)")
+        if labels is None and not want_summary:
+            raise ValueError("predict_sets_summary: nothing asked for (no labels and want_summary off)")
+        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
+            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
+        packed = capi.as_f64(packed)
+        n_sets = packed.shape[0]
+        ap = None
+        if act_prm_sets is not None and self.arch.n_layers > 1:
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        lab = conf = summary = None
+        if labels is not None:
+            lab = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+            if lab.shape[0] != self.n_rows[which]:
+                raise ValueError("predict_sets_summary: %d labels but the matrix has %d rows" % (lab.shape[0], self.n_rows[which]))
+            conf = np.zeros((self.n_out, self.n_out), dtype=np.int64)
+        if want_summary:
+            summary = np.empty((self.n_rows[which], self.n_out), dtype=np.float64)
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._lib.npbnn_predict_sets_summary(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which,
+                                                       1 if apply_out_fn else 0, int(mode),
+                                                       None if lab is None else lab.ctypes.data_as(i64), capi.dptr(summary),
+                                                       None if conf is None else conf.ctypes.data_as(i64)))
+        return summary, conf
+
     def predict_pdp(self, weight_sets, focal, grid, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
         prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]

@@ -87,6 +87,8 @@ struct Dataset {
     bool borrowed = false;     // X / X16 belong to another ctx (npbnn_share_data)
     float* X16w = nullptr;     // the fp16-split copy in the weight-streamed path's piece order (split_x_tiled_kernel), built when a
     bool x16w_borrowed = false;   // network on that path first asks for it; a borrower of X uses (and, if need be, builds) its owner's
+    std::vector<int> perm_cols;   // npbnn_permute_columns: the columns of X (and of its split copies) that hold permuted values now ...
+    DevBuf<float> perm_saved;     // ... and those columns as npbnn_set_data left them, [perm_cols.size()][n_rows]
 };
 
 }  // namespace npbnn_api
@@ -218,6 +220,8 @@ struct npbnn_ctx : npbnn_ctx_streams {
     // counts its borrowers and outlives them (a destroyed owner lingers until the last borrower lets go)
     bool sync_failed = false;      // a wait timed out once: the schedule stays off for this context
     int debug_sync_skip = -1;      // npbnn_debug_sync_skip_ (diagnostics, not part of the ABI)
+    int fi_ns[4] = {0, 0, 0, 0};   // NPBNN_FI_TIMING: device time of the last npbnn_permute_columns, and of the passes / accumulation / final
+                                   // kernel of the last npbnn_predict_sets_summary (NPBNN_INFO_PERMUTE_NS ...)
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     npbnn_ctx* data_owner = nullptr;
     int n_borrowers = 0;

@@ -4,7 +4,13 @@
 The reference runs ``RunPredict`` once per stored sample - a fresh copy of the feature matrix and a full pass over
 it every time.  Here the matrix is uploaded once and the samples go through ``npbnn_predict_sets``: up to three
 weight sets per streaming read of X, all layers fused.  Shuffling of feature columns (feature importance) and the
-posterior-predictive resampling draw from numpy's global stream exactly as the reference does."""
+posterior-predictive resampling draw from numpy's global stream exactly as the reference does.
+
+``feature_importance`` keeps a permutation on the device when it can (summary modes 0 and 1, a built-in output function,
+integer class labels): the shuffle is a gather of the block's columns inside the resident matrix
+(``npbnn_permute_columns``, row indices drawn here), the summary over the samples and its confusion table against the labels
+are accumulated there (``npbnn_predict_sets_summary``), and C x C integers come back per permutation.  ``NPBNN_FI_HOST=1``
+keeps every permutation on the route through ``get_posterior_cat_prob`` (one upload and one stack of predictions each)."""
 import os
 
 import numpy as np
@@ -63,8 +69,51 @@ class _SamplePredictor:
         ctx = self._load(features)
         return ctx.predict_sets_hpd(list(self._packed), level, act_prm_sets=self._slopes, apply_out_fn=self._kind is not None)
 
+    def load(self, features):
+        """Upload ``features`` (and describe the network on the first call): what ``permute`` and ``summary`` work on."""
+        self._load(features)
+        self._n_rows = len(features)
+
+    def permute(self, columns, independently):
+        """Shuffle ``columns`` of the loaded matrix between its rows on the device; columns an earlier call moved go back first.
+        Draws what ``_shuffled_copy`` draws from numpy's global stream - ``np.random.permutation(n_rows)`` leaves the stream
+        where ``np.random.permutation(values)`` does, and ``values[indices]`` is the array the latter returns: one permutation
+        per column when ``independently`` and ``columns`` is a list, else one for the block (np_bnn/BNN_lib.py:366-371).
+        Nothing to shuffle (``not columns``) only restores."""
+        if not columns:
+            self._ctx.permute_columns([], None)
+            return
+        if independently and type(columns) == list:
+            perms = {}                                     # a column named again is shuffled again: x[p1][p2] = x[p1[p2]]
+            for col in columns:
+                idx = np.random.permutation(self._n_rows)
+                col = _column_index(col, self._n_features)
+                perms[col] = perms[col][idx] if col in perms else idx
+            self._ctx.permute_columns(list(perms), np.stack(list(perms.values())))
+        else:
+            idx = np.random.permutation(self._n_rows)
+            cols = list(dict.fromkeys(_column_index(c, self._n_features) for c in np.atleast_1d(columns).ravel()))
+            self._ctx.permute_columns(cols, idx.reshape(1, -1))
+
+    def summary(self, mode, labels=None, want_summary=True):
+        """(summary [n_rows, n_out] or None, confusion table against ``labels`` or None) of the stored samples' predictions on
+        the loaded matrix as it stands, mode 0 (votes) or 1 (mean): ``_summarise`` and CalcAccuracy's table, accumulated on
+        the device."""
+        if self._kind is None and self._out_fn is not None:
+            raise ValueError("a custom output callable has no device summary")
+        return self._ctx.predict_sets_summary(self._packed, mode, labels=labels, act_prm_sets=self._slopes,
+                                              want_summary=want_summary, apply_out_fn=self._kind is not None)
+
     def close(self):
         self._ctx.close()
+
+
+def _column_index(col, n_features):
+    """A column as numpy indexes it: negative values count from the end."""
+    c = int(col)
+    if c != col or not -n_features <= c < n_features:
+        raise IndexError("column %r outside a matrix of %d features" % (col, n_features))
+    return c % n_features
 
 
 def _predict_samples(features, post_samples, actFun, output_act_fun):
@@ -211,13 +260,33 @@ def _feature_blocks(feature_blocks, names):
     return list(feature_blocks), ['block_%d' % i for i in range(len(feature_blocks))]
 
 
+def _device_route(post_summary_mode, predictor, features, true_labels, weights_posterior):
+    """Can a permutation of feature_importance stay on the device?  Summary modes 0 and 1 (mode 2 needs a uniform per instance
+    and sample from the host stream), an output function with a device kind, one integer class label per instance, and
+    NPBNN_FI_HOST not set."""
+    if os.environ.get("NPBNN_FI_HOST", "") not in ("", "0"):
+        return False
+    if post_summary_mode not in (0, 1) or (predictor._kind is None and predictor._out_fn is not None):
+        return False
+    if features.ndim != 2 or len(features) == 0 or len(weights_posterior) == 0:
+        return False
+    labels = np.asarray(true_labels)
+    if labels.ndim != 1 or len(labels) != len(features) or labels.dtype.kind not in "iuf":
+        return False
+    n_classes = predictor._weights[0][-1].shape[0]
+    return bool(np.all(labels == np.floor(labels)) and np.all(labels >= 0) and np.all(labels < n_classes))
+
+
 def feature_importance(input_features, weights_pkl=None, weights_posterior=None, true_labels=[], fname_stem='',
                        feature_names=[], verbose=False, post_summary_mode=0, n_permutations=100, feature_blocks=dict(),
                        write_to_file=True, predictions_outdir='', unlink_features_within_block=True, actFun=None,
                        output_act_fun=None):
     """Permutation importance (np_bnn/BNN_lib.py:504-597): how much accuracy is lost when a block of feature columns is
     shuffled between the instances, ``n_permutations`` shuffles per block (numpy's global stream, upstream's order).  The
-    stored samples stay packed on the device; a shuffle costs one upload of the matrix and one ``npbnn_predict_sets``.
+    stored samples stay packed on the device.  With ``post_summary_mode`` 0 or 1, a built-in output function and integer class
+    labels the matrix is uploaded once and a shuffle is a column gather, the passes and one confusion table on the device
+    (``_device_route``); otherwise (and with ``NPBNN_FI_HOST=1``) a shuffle costs one upload of the matrix and one
+    ``npbnn_predict_sets``.
     Returns a data frame, most important block first, with upstream's column names; written to
     ``<fname_stem_>feature_importance.txt`` unless ``write_to_file`` is off."""
     import pandas as pd
@@ -231,16 +300,30 @@ def feature_importance(input_features, weights_pkl=None, weights_posterior=None,
 
     predictor = _SamplePredictor(features.shape[1], weights_posterior, act, output_act_fun)
     try:
-        def accuracy(shuffle=None):
-            summary = get_posterior_cat_prob(features, weights_posterior, feature_index_to_shuffle=shuffle,
-                                             post_summary_mode=post_summary_mode, actFun=act, output_act_fun=output_act_fun,
-                                             unlink_features_within_block=unlink_features_within_block, _predictor=predictor)[1]
-            return CalcAccuracy(summary, true_labels)
+        on_device = _device_route(post_summary_mode, predictor, features, true_labels, weights_posterior)
+        if on_device:
+            labels = np.asarray(true_labels).astype(np.int64).ravel()
+            if len(weights_posterior):
+                act.reset_prm(weights_posterior[-1]['alphas'])      # (as get_posterior_cat_prob leaves it)
+            predictor.load(features)                                # the one upload
+
+            def accuracy(shuffle=None):
+                predictor.permute(shuffle, unlink_features_within_block)
+                table = predictor.summary(post_summary_mode, labels, want_summary=False)[1]
+                return np.trace(table) / len(labels)
+        else:
+            def accuracy(shuffle=None):
+                summary = get_posterior_cat_prob(features, weights_posterior, feature_index_to_shuffle=shuffle,
+                                                 post_summary_mode=post_summary_mode, actFun=act, output_act_fun=output_act_fun,
+                                                 unlink_features_within_block=unlink_features_within_block, _predictor=predictor)[1]
+                return CalcAccuracy(summary, true_labels)
 
         baseline = accuracy()
         if verbose:
             print("Reference accuracy (mean):", np.mean(baseline))
         shuffled = np.array([[accuracy(block) for _ in range(n_permutations)] for block in blocks])    # [block, permutation]
+        if on_device:
+            predictor.permute(None, False)                          # the columns go back
     finally:
         predictor.close()
 
