@@ -183,8 +183,10 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
        NPBNN_INFO_F16_MOVED_COLUMNS = 11, NPBNN_INFO_F16_MAX_MOVE = 12, NPBNN_INFO_PDP_ROUTE = 13,
        /* with NPBNN_FI_TIMING=1 in the environment (HIP events; 0 otherwise): device time in nanoseconds of the last
         * npbnn_permute_columns (restore, gather and the patch of the split copies), and of the last npbnn_predict_sets_summary's
-        * evaluation passes (weight packing included), accumulation launches and final kernel */
-       NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17 };
+        * evaluation passes (weight packing included), accumulation launches and final kernel; npbnn_predict_sets_support leaves its
+        * passes and accumulation in the same two slots and its own final kernel in NPBNN_INFO_SUPPORT_FINAL_NS */
+       NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17,
+       NPBNN_INFO_SUPPORT_FINAL_NS = 18 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -263,6 +265,25 @@ int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* cols, int32_
  * NaN and for a label outside the classes. */
 int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
                                int apply_out_fn, int mode, const int64_t* labels, double* out_summary, int64_t* out_confusion);
+
+/* Confidence thresholds and Bayes-factor support of the n_sets stored samples' summary on the resident matrix `which`: what
+ * get_posterior_threshold's sweep (np_bnn/BNN_lib.py:640-671, get_accuracy_threshold :627-637), CalcTP / CalcFP (:305-317),
+ * CalcTP_BF / CalcFP_BF (:320-337) and turn_low_pp_instances_to_nan (:674-679) compute from it, in one pass.  The sets replay and
+ * accumulate exactly as in npbnn_predict_sets_summary (same mode, same quotient q = accumulator / n_sets, same first argmax k* of the
+ * quotient); with p = q[k*] per row:
+ *   out_cube   int64 [n_thresholds + 1][out_dim][out_dim]: cell [b][label][k*] counts the rows with exactly b thresholds strictly
+ *              below p (p > t in float64 against thresholds[], which must ascend).  The rows retained at thresholds[i] are the bins
+ *              b > i; summed over b the cube is npbnn_predict_sets_summary's confusion table.
+ *   out_bf     int64 [n_bf + 1][2], with prior_summary [n_rows][out_dim] (else both NULL, n_bf 0): cell [b][k* == label] counts the rows
+ *              with exactly b of bf_thresholds[] strictly below (p / (1e-10 + 1 - p)) / (r / (1e-10 + 1 - r)), r = prior_summary[row][k*].
+ *   out_summary [n_rows][out_dim] float64 or NULL: the summary; with a cutoff (pointer, or NULL for none) the rows where p > *cutoff
+ *              is false are NaN in every class.  out_keep uint8 [n_rows] or NULL: 1 where p > *cutoff (1 everywhere without one).
+ * labels [n_rows] int64 in [0, out_dim) are required.  NPBNN_E_ARG before any launch: thresholds or bf_thresholds not ascending or NaN,
+ * a NaN cutoff; after the pass: a prediction that is NaN, a label outside the classes. */
+int npbnn_predict_sets_support(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which, int apply_out_fn,
+                               int mode, const int64_t* labels, const double* thresholds, int32_t n_thresholds, const double* prior_summary,
+                               const double* bf_thresholds, int32_t n_bf, const double* cutoff, int64_t* out_cube, int64_t* out_bf,
+                               double* out_summary, uint8_t* out_keep);
 
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events

@@ -30,6 +30,8 @@ from .logger import init_output_files, postLogger  # noqa: F401
 from .mc3 import MC3  # noqa: F401
 from .posterior import (feature_importance, get_posterior_cat_prob, get_posterior_est, predictBNN,  # noqa: F401
                         sample_from_categorical)
+from .support import (CalcAccAboveThreshold, CalcConfusionMatrix, CalcFP, CalcFP_BF, CalcTP, CalcTP_BF,  # noqa: F401
+                      get_accuracy_threshold, get_posterior_threshold, turn_low_pp_instances_to_nan)
 from .pdp import get_feature_summary, get_pdp, make_pdp_features, pdp  # noqa: F401
 from .hpd import calcHPD, get_posterior_hpd, posterior_hpd  # noqa: F401
 from . import comm  # noqa: F401

@@ -342,6 +342,57 @@ class HipContext:
                                                        None if conf is None else conf.ctypes.data_as(i64)))
         return summary, conf
 
+    def predict_sets_support(self, weight_sets, mode, labels, thresholds, prior_summary=None, bf_thresholds=(), cutoff=None,
+                             act_prm_sets=None, which=capi.TRAIN, want_summary=False, want_keep=False, apply_out_fn=True):
+        """Confidence-threshold and Bayes-factor support of the summary over several weight sets' predictions on the resident
+        matrix (npbnn_predict_sets_support).  Per row, ``p`` the largest summary value and ``k`` its (first) class:
+        ``cube`` [len(thresholds) + 1, n_out, n_out] int64 counts the row in ``[b, label, k]``, ``b`` the number of ``thresholds``
+        (float64, ascending) strictly below ``p`` - the rows retained at ``thresholds[i]`` are ``cube[i + 1:]``; with
+        ``prior_summary`` [n_rows, n_out], ``bf`` [len(bf_thresholds) + 1, 2] int64 counts it in ``[b, k == label]``, ``b`` the number
+        of ``bf_thresholds`` strictly below CalcTP_BF's Bayes factor.  ``cutoff``: rows with ``p > cutoff`` false are NaN in the
+        summary and 0 in the keep mask.  Returns a dict with ``cube``, ``bf``, ``summary``, ``keep`` (None where not asked for).
+        The sets replay as in ``predict_sets_summary``, whose quotients these are bit for bit."""
+        if mode not in (0, 1):
+            raise ValueError("predict_sets_support: mode must be 0 (votes) or 1 (mean)")
+        if labels is None:
+            raise ValueError("predict_sets_support: labels are required")
+        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
+            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
+        packed = capi.as_f64(packed)
+        n_sets, n_rows, c = packed.shape[0], self.n_rows[which], self.n_out
+        ap = None
+        if act_prm_sets is not None and self.arch.n_layers > 1:
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        lab = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        if lab.shape[0] != n_rows:
+            raise ValueError("predict_sets_support: %d labels but the matrix has %d rows" % (lab.shape[0], n_rows))
+        thr = capi.as_f64(np.asarray(thresholds, dtype=np.float64).ravel())
+        bft = capi.as_f64(np.asarray(bf_thresholds, dtype=np.float64).ravel())
+        for name, t in (("thresholds", thr), ("bf_thresholds", bft)):
+            if np.any(np.isnan(t)) or np.any(np.diff(t) < 0):
+                raise ValueError("predict_sets_support: %s must ascend and hold no NaN" % name)
+        prior = bf = None
+        if prior_summary is not None:
+            prior = capi.as_f64(prior_summary)
+            if prior.shape != (n_rows, c):
+                raise ValueError("predict_sets_support: prior_summary is %s, the summary %s" % (prior.shape, (n_rows, c)))
+            bf = np.zeros((len(bft) + 1, 2), dtype=np.int64)
+        elif len(bft):
+            raise ValueError("predict_sets_support: bf_thresholds without prior_summary")
+        if cutoff is not None and np.isnan(cutoff):
+            raise ValueError("predict_sets_support: the cutoff is NaN")
+        cube = np.zeros((len(thr) + 1, c, c), dtype=np.int64)
+        summary = np.empty((n_rows, c), dtype=np.float64) if want_summary else None
+        keep = np.empty(n_rows, dtype=np.uint8) if want_keep else None
+        cut = None if cutoff is None else C.c_double(float(cutoff))
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._lib.npbnn_predict_sets_support(
+            self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which, 1 if apply_out_fn else 0, int(mode), lab.ctypes.data_as(i64),
+            capi.dptr(thr) if len(thr) else None, len(thr), capi.dptr(prior), capi.dptr(bft) if len(bft) else None, len(bft),
+            None if cut is None else C.cast(C.byref(cut), capi._DP), cube.ctypes.data_as(i64), None if bf is None else bf.ctypes.data_as(i64),
+            capi.dptr(summary), None if keep is None else keep.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return dict(cube=cube, bf=bf, summary=summary, keep=None if keep is None else keep.astype(bool))
+
     def predict_pdp(self, weight_sets, focal, grid, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
         prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]

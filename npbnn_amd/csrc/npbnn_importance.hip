@@ -10,38 +10,23 @@
 // permuted matrix writes, since a column's largest entry - all its scale depends on - does not move with its rows.  Row indices are
 // checked by a kernel of their own before anything is written.
 //
-// npbnn_predict_sets_summary: the sets replay as in npbnn_predict_sets (groups that share their slopes, the float32 retry); after each
+// npbnn_predict_sets_summary: the sets replay as in npbnn_predict_sets (groups that share their slopes, the float32 retry; the replay
+// is replay_sets_accumulate, which npbnn_predict_sets_support of npbnn_support.hip calls too); after each
 // group summary_accumulate_kernel folds the group's float32 predictions [g][rows][C] into uint32 votes (mode 0: per set and row the
 // first class holding the row's maximum - numpy's argmax) or float64 sums (mode 1: set after set - the order np.mean(axis=0) adds a
 // C-contiguous [S, N, C] array in).  Streaming: g x N x C floats in, N x C accumulators in and out, one thread per row (mode 0) or per
 // four (row, class) entries (mode 1), 16-byte accesses where C allows.  summary_final_kernel divides by the number of sets, takes each
 // row's first argmax of the QUOTIENT (a division can turn an inequality into a tie) and counts [label][argmax] in an LDS histogram
 // with integer atomics, one global integer atomic per nonzero cell and workgroup: the table does not depend on the order.
-#include "npbnn_ctx.hip.h"
+#include "npbnn_sets.hip.h"
 
-#include <climits>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 namespace npbnn_api {
 
 namespace {
 
-constexpr int kFiThreads = 256;
-constexpr int kFiMaxBlocks = 2048;                 // memory-bound kernels: grid-stride beyond this many workgroups
 constexpr int kConfLdsClasses = 64;                // confusion tables up to this many classes are counted in LDS first (16 KiB)
-
-constexpr int kFlagBadRow = 1;                     // permutation index outside [0, n_rows)
-constexpr int kFlagNaN = 2;                        // a prediction is NaN
-constexpr int kFlagBadLabel = 4;                   // a label outside [0, C)
-
-unsigned grid_for(long long items) {
-    long long b = (items + kFiThreads - 1) / kFiThreads;
-    if (b < 1) b = 1;
-    if (b > kFiMaxBlocks) b = kFiMaxBlocks;
-    return (unsigned)b;
-}
 
 // ---- permutation -------------------------------------------------------------------------------
 
@@ -234,33 +219,6 @@ __global__ __launch_bounds__(kFiThreads) void summary_final_kernel(const ACC* __
     }
 }
 
-// HIP events around the parts of a call, when NPBNN_FI_TIMING is set (tools/time_feature_importance.py)
-struct FiTimer {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool on = false;
-    FiTimer() {
-        const char* e = getenv("NPBNN_FI_TIMING");
-        on = e && *e && strcmp(e, "0") != 0;
-        if (on)
-            for (hipEvent_t& x : ev)
-                if (hipEventCreate(&x) != hipSuccess) on = false;
-    }
-    FiTimer(const FiTimer&) = delete;
-    FiTimer& operator=(const FiTimer&) = delete;
-    ~FiTimer() {
-        for (hipEvent_t x : ev)
-            if (x) (void)hipEventDestroy(x);
-    }
-    void mark(int i, hipStream_t s) { if (on) (void)hipEventRecord(ev[i], s); }
-    // nanoseconds between marks a and b (both reached: the stream was synchronised)
-    int ns(int a, int b) {
-        float ms = 0.f;
-        if (!on || hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) return 0;
-        const double v = (double)ms * 1e6;
-        return v > (double)INT_MAX ? INT_MAX : (int)v;
-    }
-};
-
 }  // namespace
 
 }  // namespace npbnn_api
@@ -363,41 +321,17 @@ extern "C" int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* c
     return NPBNN_OK;
 }
 
-extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
-                                          int apply_out_fn, int mode, const int64_t* labels, double* out_summary, int64_t* out_confusion) {
-    if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
-    if (!W_sets || n_sets < 1 || (!out_summary && !out_confusion) || (out_confusion != nullptr) != (labels != nullptr))
-        return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: bad arguments");
-    if (mode != 0 && mode != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: mode must be 0 (votes) or 1 (mean), got %d", mode);
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: which must be 0 or 1");
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_summary: call npbnn_set_arch first");
+int npbnn_api::replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which,
+                                      int apply_out_fn, int mode, double* d_acc, int* d_flag) {
     Dataset& d = ctx->ds[which];
-    int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int C = ctx->net.n_out;
     const int n_act = ctx->net.n_layers - 1;
     const long long n_rows = d.n_rows;
     const size_t per_set = (size_t)n_rows * C;
     const size_t wn = (size_t)ctx->n_weights;
     hipStream_t st = ctx->stream;
+    int rc;
     if ((rc = ctx->d_y.reserve(ctx, kMaxCand * per_set))) return rc;
-    // accumulators (per_set doubles, or as many unsigned), the summary, the confusion table, the labels, the flag word
-    DevBuf<double> d_acc, d_summary;
-    DevBuf<unsigned long long> d_conf;
-    DevBuf<long long> d_labels;
-    DevBuf<int> d_flag;
-    if ((rc = d_acc.reserve(ctx, per_set))) return rc;
-    if ((rc = d_flag.reserve(ctx, 4))) return rc;
-    if (out_summary && (rc = d_summary.reserve(ctx, per_set))) return rc;
-    if (labels) {
-        if ((rc = d_conf.reserve(ctx, (size_t)C * C))) return rc;
-        if ((rc = d_labels.reserve(ctx, (size_t)n_rows))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(d_labels, labels, (size_t)n_rows * sizeof(long long), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemsetAsync(d_conf, 0, (size_t)C * C * sizeof(unsigned long long), st));
-    }
-    HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, per_set * sizeof(double), st));
-    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
     FiTimer tm;
     double pass_ns = 0.0, acc_ns = 0.0;
     std::vector<double> wstage(kMaxCand * wn);
@@ -443,25 +377,25 @@ extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, 
             // (push_eval_params stages through one pinned slot: the launch that reads it must be in before the next write)
             HIP_TRY(ctx, hipStreamSynchronize(st));
             pass_ns += tm.ns(0, 1);
-            if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is");
+            if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "%s: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is", who);
             if (!(ctx->net.l0_f16 && (ovf & kFlagF16Range))) break;
-            if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "predict_sets_summary: a layer-0 weight left the fp16 range");
+            if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "%s: a layer-0 weight left the fp16 range", who);
         }
         // the group's predictions [g][rows][C] into the accumulator, before the next group overwrites them
         tm.mark(2, st);
         if (mode == 0) {
-            unsigned* votes = reinterpret_cast<unsigned*>(d_acc.get());
+            unsigned* votes = reinterpret_cast<unsigned*>(d_acc);
             if (C % 4 == 0)
-                hipLaunchKernelGGL(summary_votes_kernel<true>, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g, n_rows, C, votes, d_flag.get());
+                hipLaunchKernelGGL(summary_votes_kernel<true>, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g, n_rows, C, votes, d_flag);
             else
-                hipLaunchKernelGGL(summary_votes_kernel<false>, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g, n_rows, C, votes, d_flag.get());
+                hipLaunchKernelGGL(summary_votes_kernel<false>, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g, n_rows, C, votes, d_flag);
         } else {
             if (per_set % 4 == 0)
                 hipLaunchKernelGGL(summary_sums_kernel<true>, dim3(grid_for((long long)(per_set / 4))), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g,
-                                   (long long)per_set, d_acc.get(), d_flag.get());
+                                   (long long)per_set, d_acc, d_flag);
             else
                 hipLaunchKernelGGL(summary_sums_kernel<false>, dim3(grid_for((long long)per_set)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g,
-                                   (long long)per_set, d_acc.get(), d_flag.get());
+                                   (long long)per_set, d_acc, d_flag);
         }
         HIP_TRY(ctx, hipGetLastError());
         tm.mark(3, st);
@@ -471,6 +405,46 @@ extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, 
         }
         s0 += g;
     }
+    ctx->fi_ns[1] = pass_ns > (double)INT_MAX ? INT_MAX : (int)pass_ns;
+    ctx->fi_ns[2] = acc_ns > (double)INT_MAX ? INT_MAX : (int)acc_ns;
+    return NPBNN_OK;
+}
+
+extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
+                                          int apply_out_fn, int mode, const int64_t* labels, double* out_summary, int64_t* out_confusion) {
+    if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
+    if (!W_sets || n_sets < 1 || (!out_summary && !out_confusion) || (out_confusion != nullptr) != (labels != nullptr))
+        return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: bad arguments");
+    if (mode != 0 && mode != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: mode must be 0 (votes) or 1 (mean), got %d", mode);
+    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: which must be 0 or 1");
+    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_summary: call npbnn_set_arch first");
+    Dataset& d = ctx->ds[which];
+    int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int C = ctx->net.n_out;
+    const long long n_rows = d.n_rows;
+    const size_t per_set = (size_t)n_rows * C;
+    hipStream_t st = ctx->stream;
+    // accumulators (per_set doubles, or as many unsigned), the summary, the confusion table, the labels, the flag word
+    DevBuf<double> d_acc, d_summary;
+    DevBuf<unsigned long long> d_conf;
+    DevBuf<long long> d_labels;
+    DevBuf<int> d_flag;
+    if ((rc = d_acc.reserve(ctx, per_set))) return rc;
+    if ((rc = d_flag.reserve(ctx, 4))) return rc;
+    if (out_summary && (rc = d_summary.reserve(ctx, per_set))) return rc;
+    if (labels) {
+        if ((rc = d_conf.reserve(ctx, (size_t)C * C))) return rc;
+        if ((rc = d_labels.reserve(ctx, (size_t)n_rows))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(d_labels, labels, (size_t)n_rows * sizeof(long long), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemsetAsync(d_conf, 0, (size_t)C * C * sizeof(unsigned long long), st));
+    }
+    HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, per_set * sizeof(double), st));
+    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    rc = replay_sets_accumulate(ctx, "predict_sets_summary", W_sets, act_prm_sets, n_sets, which, apply_out_fn, mode, d_acc.get(), d_flag.get());
+    if (rc) return rc;
+    FiTimer tm;
     tm.mark(0, st);
     const int lds_conf = C <= kConfLdsClasses ? 1 : 0;
     const long long* lab = labels ? d_labels.get() : nullptr;
@@ -486,8 +460,6 @@ extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, 
     int flags = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->fi_ns[1] = pass_ns > (double)INT_MAX ? INT_MAX : (int)pass_ns;
-    ctx->fi_ns[2] = acc_ns > (double)INT_MAX ? INT_MAX : (int)acc_ns;
     ctx->fi_ns[3] = tm.ns(0, 1);
     if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: a prediction is NaN");
     if (flags & kFlagBadLabel) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: a label lies outside [0, %d)", C);

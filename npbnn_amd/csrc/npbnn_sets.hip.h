@@ -1,0 +1,63 @@
+// What the entries that summarise stored weight sets on the device share (npbnn_importance.hip: npbnn_predict_sets_summary;
+// npbnn_support.hip: npbnn_predict_sets_support): the replay of the sets into an accumulator, the flag word's bits, the launch shape of
+// the streaming kernels and the HIP-event timer behind NPBNN_FI_TIMING.  Not part of the ABI.
+#pragma once
+#include "npbnn_ctx.hip.h"
+
+#include <climits>
+#include <cstdlib>
+#include <cstring>
+
+namespace npbnn_api {
+
+constexpr int kFiThreads = 256;
+constexpr int kFiMaxBlocks = 2048;                 // memory-bound kernels: grid-stride beyond this many workgroups
+
+constexpr int kFlagBadRow = 1;                     // permutation index outside [0, n_rows)
+constexpr int kFlagNaN = 2;                        // a prediction is NaN
+constexpr int kFlagBadLabel = 4;                   // a label outside [0, C)
+
+inline unsigned grid_for(long long items) {
+    long long b = (items + kFiThreads - 1) / kFiThreads;
+    if (b < 1) b = 1;
+    if (b > kFiMaxBlocks) b = kFiMaxBlocks;
+    return (unsigned)b;
+}
+
+// HIP events around the parts of a call, when NPBNN_FI_TIMING is set (tools/time_feature_importance.py, tools/time_posterior_threshold.py)
+struct FiTimer {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool on = false;
+    FiTimer() {
+        const char* e = getenv("NPBNN_FI_TIMING");
+        on = e && *e && strcmp(e, "0") != 0;
+        if (on)
+            for (hipEvent_t& x : ev)
+                if (hipEventCreate(&x) != hipSuccess) on = false;
+    }
+    FiTimer(const FiTimer&) = delete;
+    FiTimer& operator=(const FiTimer&) = delete;
+    ~FiTimer() {
+        for (hipEvent_t x : ev)
+            if (x) (void)hipEventDestroy(x);
+    }
+    void mark(int i, hipStream_t s) { if (on) (void)hipEventRecord(ev[i], s); }
+    // nanoseconds between marks a and b (both reached: the stream was synchronised)
+    int ns(int a, int b) {
+        float ms = 0.f;
+        if (!on || hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess) return 0;
+        const double v = (double)ms * 1e6;
+        return v > (double)INT_MAX ? INT_MAX : (int)v;
+    }
+};
+
+// The n_sets weight sets against the resident matrix `which`, group after group as npbnn_predict_sets replays them (sets that share
+// their slopes travel together, the float32 retry), each group's float32 predictions folded into d_acc before the next group
+// overwrites them: mode 0 uint32 votes [n_rows][C] (d_acc read as unsigned), mode 1 float64 sums [n_rows][C], in set order.  d_acc
+// (n_rows x C doubles) and the flag word d_flag are the caller's, zeroed by it in stream order before the call; kFlagNaN is raised
+// there.  `who` names the entry in error messages.  Leaves the pass and accumulation times in ctx->fi_ns[1], [2] (NPBNN_FI_TIMING).
+// Defined in npbnn_importance.hip.
+int replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which, int apply_out_fn,
+                           int mode, double* d_acc, int* d_flag);
+
+}  // namespace npbnn_api

@@ -57,6 +57,13 @@ class _SamplePredictor:
             y = np.array([self._out_fn(yi) for yi in y])
         return y
 
+    def predict_loaded(self):
+        """``predict`` on the matrix ``load`` uploaded, without a second upload."""
+        y = self._ctx.predict_sets(list(self._packed), act_prm_sets=self._slopes, apply_out_fn=self._kind is not None)
+        if self._kind is None and self._out_fn is not None:
+            y = np.array([self._out_fn(yi) for yi in y])
+        return y
+
     def predict_hpd(self, features, level):
         """(mean, lower, upper) [n_rows, n_out] over the stored samples' predictions on ``features``; the stack stays on the
         device (npbnn_predict_sets_hpd).  A custom output callable has no device kind: its stack is built on the host and goes
@@ -103,6 +110,14 @@ class _SamplePredictor:
             raise ValueError("a custom output callable has no device summary")
         return self._ctx.predict_sets_summary(self._packed, mode, labels=labels, act_prm_sets=self._slopes,
                                               want_summary=want_summary, apply_out_fn=self._kind is not None)
+
+    def support(self, mode, labels, thresholds, **kw):
+        """Threshold cube (and Bayes-factor table, NaN-masked summary, keep mask: ``HipContext.predict_sets_support``'s keywords) of
+        the stored samples' summary on the loaded matrix, mode 0 or 1."""
+        if self._kind is None and self._out_fn is not None:
+            raise ValueError("a custom output callable has no device summary")
+        return self._ctx.predict_sets_support(self._packed, mode, labels, thresholds, act_prm_sets=self._slopes,
+                                              apply_out_fn=self._kind is not None, **kw)
 
     def close(self):
         self._ctx.close()
@@ -218,27 +233,9 @@ def _confusion_table(true_labels, predicted, n_classes):
     return table
 
 
-def predictBNN(predict_features, pickle_file, test_labels=[], instance_id=[], post_summary_mode=0, fname="", wd="",
-               verbose=1):
-    """Posterior predictions for a feature matrix from a checkpoint ``[bnn, mcmc, logger]`` (np_bnn/BNN_lib.py:404-501,
-    without its Bayes-factor and threshold extras).  Files, next to the checkpoint or in ``wd``:
-    ``<fname_><checkpoint>_pred_pr.npy`` (every sample's predictions), ``..._pred_mean_pr.txt`` (the summary, with the
-    instance names in front when given), ``..._accuracy.txt`` when labels are given."""
-    model, _, logger = load_obj(pickle_file)
-    per_sample, summary = get_posterior_cat_prob(predict_features, logger._post_weight_samples,
-                                                 post_summary_mode=post_summary_mode, actFun=model._act_fun,
-                                                 output_act_fun=model._output_act_fun)
-    stem = os.path.join(wd if wd else os.path.dirname(pickle_file),
-                        (fname + "_" if fname else "") + os.path.splitext(os.path.basename(pickle_file))[0])
-    result = {'post_prob_predictions': summary, 'mean_accuracy': np.nan, 'confusion_matrix': np.nan}
-    if len(test_labels):
-        result['mean_accuracy'] = np.mean(CalcAccuracy(summary, test_labels))
-        result['confusion_matrix'] = _confusion_table(test_labels, np.argmax(summary, axis=1), summary.shape[1])
-        with open(stem + '_accuracy.txt', 'w') as fh:
-            fh.write("Mean accuracy: %s" % result['mean_accuracy'])
-        if verbose:
-            print("Accuracy:", result['mean_accuracy'])
-            print("Confusion matrix:\n", result['confusion_matrix'])
+def _write_predictions(stem, per_sample, summary, instance_id, verbose):
+    """``<stem>_pred_mean_pr.txt`` (the summary, with the instance names in front when given) and ``<stem>_pred_pr.npy`` (every
+    sample's predictions), as np_bnn/BNN_lib.py:489-500 writes them."""
     if len(instance_id):
         names = np.asarray(instance_id).reshape(-1, 1)
         np.savetxt(stem + '_pred_mean_pr.txt', np.hstack((names, np.round(summary, 4).astype(str))), fmt='%s', delimiter='\t')
@@ -247,6 +244,83 @@ def predictBNN(predict_features, pickle_file, test_labels=[], instance_id=[], po
     np.save(stem + '_pred_pr.npy', per_sample)
     if verbose:
         print("Predictions saved in files:\n    %s\n    %s\n" % (stem + '_pred_pr.npy', stem + '_pred_mean_pr.txt'))
+
+
+def _output_stem(pickle_file, fname, wd):
+    return os.path.join(wd if wd else os.path.dirname(pickle_file),
+                        (fname + "_" if fname else "") + os.path.splitext(os.path.basename(pickle_file))[0])
+
+
+def _accuracy_report(summary, test_labels, stem, threshold, verbose):
+    """(mean accuracy, C x C confusion table) of a summary against its labels; ``<stem>_accuracy.txt`` with the true- and
+    false-positive rates at ``threshold`` (np_bnn/BNN_lib.py:440-455)."""
+    from .support import CalcFP, CalcTP
+    accuracy = np.mean(CalcAccuracy(summary, test_labels))
+    tp, fp = CalcTP(summary, test_labels, threshold=threshold), CalcFP(summary, test_labels, threshold=threshold)
+    table = _confusion_table(test_labels, np.argmax(summary, axis=1), summary.shape[1])
+    with open(stem + '_accuracy.txt', 'w') as fh:
+        fh.write("Mean accuracy: %s (TP: %s; FP: %s)" % (accuracy, tp, fp))
+    if verbose:
+        print("Accuracy:", accuracy)
+        print("True positive rate:", np.mean(tp))
+        print("False positive rate:", np.mean(fp))
+        print("Confusion matrix:\n", table)
+    return accuracy, table
+
+
+def _prior_mean_prediction(features, prior_samples, act, output_act_fun):
+    """Mean over the prior samples of their predictions on ``features`` [row, class]: accumulated on the device
+    (``npbnn_predict_sets_summary`` mode 1, no stack) when the output function has a device kind, else from the stack."""
+    act.reset_prm(prior_samples[-1]['alphas'])            # (upstream installs every prior sample's slopes in turn: the last stays)
+    pred = _SamplePredictor(features.shape[1], prior_samples, act, output_act_fun)
+    try:
+        if pred._kind is None and pred._out_fn is not None:
+            return np.mean(pred.predict(features), axis=0)
+        pred.load(features)
+        return pred.summary(1)[0]
+    finally:
+        pred.close()
+
+
+def predictBNN(predict_features, pickle_file, test_labels=[], instance_id=[], pickle_file_prior=0, target_acc=None,
+               post_cutoff=None, threshold=0.95, bf=150, post_summary_mode=0, fname="", wd="", verbose=1):
+    """Posterior predictions for a feature matrix from a checkpoint ``[bnn, mcmc, logger]`` (np_bnn/BNN_lib.py:404-501), with
+    upstream's keywords, defaults and order of effects.  Files, next to the checkpoint or in ``wd``:
+    ``<fname_><checkpoint>_pred_pr.npy`` (every sample's predictions), ``..._pred_mean_pr.txt`` (the summary, with the
+    instance names in front when given), ``..._accuracy.txt`` when labels are given (mean accuracy, and the true- / false-positive
+    rates ``CalcTP`` / ``CalcFP`` at ``threshold``).
+
+    ``pickle_file_prior``: a pickled list of prior samples (dicts with ``weights`` and ``alphas``); their mean prediction gives
+    the Bayes factor of every instance's call, and the true- / false-positive rates at ``bf`` (``CalcTP_BF`` / ``CalcFP_BF``) are
+    printed.  Upstream's branch cannot run as written: it calls ``RunPredict`` without an
+    output function (:468).  What it means is built here - the prior samples go through the model's own output function.
+    ``target_acc`` (a threshold from ``get_posterior_threshold`` on the checkpoint's test set; upstream compares against the whole
+    selected row, :482-485, where the row's first entry, the threshold, is meant) or ``post_cutoff`` (a threshold given): the
+    summary and every sample's slice of the stack are NaN in the instances whose largest summary value does not exceed it, in the
+    returned summary and in both files (``turn_low_pp_instances_to_nan``).  ``confusion_matrix`` stays the plain C x C table."""
+    from . import support
+    model, _, logger = load_obj(pickle_file)
+    per_sample, summary = get_posterior_cat_prob(predict_features, logger._post_weight_samples,
+                                                 post_summary_mode=post_summary_mode, actFun=model._act_fun,
+                                                 output_act_fun=model._output_act_fun)
+    stem = _output_stem(pickle_file, fname, wd)
+    result = {'post_prob_predictions': summary, 'mean_accuracy': np.nan, 'confusion_matrix': np.nan}
+    if len(test_labels):
+        result['mean_accuracy'], result['confusion_matrix'] = _accuracy_report(summary, test_labels, stem, threshold, verbose)
+    if pickle_file_prior:
+        prior_samples = load_obj(pickle_file_prior)
+        prior = _prior_mean_prediction(np.asarray(predict_features, dtype=np.float64), prior_samples, model._act_fun,
+                                       model._output_act_fun)
+        if len(test_labels) and verbose:
+            print("True positive rate (BF):", np.mean(support.CalcTP_BF(summary, prior, test_labels, threshold=bf)))
+            print("False positive rate (BF):", np.mean(support.CalcFP_BF(summary, prior, test_labels, threshold=bf)))
+    if target_acc or post_cutoff:
+        cutoff = support.get_posterior_threshold(pickle_file, target_acc, post_summary_mode)[0] if target_acc else post_cutoff
+        high_pp_indices = np.where(np.max(summary, axis=1) > cutoff)[0]
+        summary = support.turn_low_pp_instances_to_nan(summary, high_pp_indices)
+        per_sample = np.array([support.turn_low_pp_instances_to_nan(y, high_pp_indices) for y in per_sample])
+        result['post_prob_predictions'] = summary
+    _write_predictions(stem, per_sample, summary, instance_id, verbose)
     return result
 
 
