@@ -184,9 +184,10 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
        /* with NPBNN_FI_TIMING=1 in the environment (HIP events; 0 otherwise): device time in nanoseconds of the last
         * npbnn_permute_columns (restore, gather and the patch of the split copies), and of the last npbnn_predict_sets_summary's
         * evaluation passes (weight packing included), accumulation launches and final kernel; npbnn_predict_sets_support leaves its
-        * passes and accumulation in the same two slots and its own final kernel in NPBNN_INFO_SUPPORT_FINAL_NS */
+        * passes and accumulation in the same two slots and its own final kernel in NPBNN_INFO_SUPPORT_FINAL_NS; npbnn_predict_sets_lppd
+        * does the same with NPBNN_INFO_LPPD_FINAL_NS (and leaves 0 in its three slots when it refuses a call before any launch) */
        NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17,
-       NPBNN_INFO_SUPPORT_FINAL_NS = 18 };
+       NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -284,6 +285,28 @@ int npbnn_predict_sets_support(npbnn_ctx* ctx, const double* W_sets, const doubl
                                int mode, const int64_t* labels, const double* thresholds, int32_t n_thresholds, const double* prior_summary,
                                const double* bf_thresholds, int32_t n_bf, const double* cutoff, int64_t* out_cube, int64_t* out_bf,
                                double* out_summary, uint8_t* out_keep);
+
+/* Log pointwise predictive density and WAIC of the n_sets stored samples on the resident matrix `which`, from the per-row terms of the
+ * reference's own likelihoods, unweighted and untempered: ll[s][i] = log(prediction[i, label_i]) (calc_likelihood,
+ * np_bnn/BNN_lib.py:100-121, the summand of :121) for NPBNN_LIK_CATEGORICAL, and sum over the target columns t of
+ * norm.logpdf(y[i][t], mu[i][t], sigma[s][t]) (calc_likelihood_regression, :123-131) for NPBNN_LIK_GAUSS; predictions as the loop over
+ * RunPredict gives them per stored sample (:375-381, 715-748).  The [n_sets][n_rows] matrix is never built: the sets replay as in
+ * npbnn_predict_sets_summary with the pre-output values left on the device, and each group is folded into float64 per-row
+ * accumulators (the log-softmax is taken from the float32 logits in float64, not as the log of a float32 probability).
+ *   lppd_i    = logsumexp_s ll[s][i] - log n_sets          mean_ll_i = mean_s ll[s][i]
+ *   p_waic_i  = var_s ll[s][i], ddof 1 (0 for one set)     ll_sample[s] = sum_i ll[s][i]
+ * lik_kind: NPBNN_LIK_CATEGORICAL (softmax output; labels from npbnn_set_labels_i64 on `which`) or NPBNN_LIK_GAUSS (identity output;
+ * targets from npbnn_set_targets_f64, as many columns as the network has outputs; sigma_sets [n_sets][n_targets], every entry
+ * positive and finite; NULL for CATEGORICAL); the predicted-sigma and count likelihoods are refused.  out_lppd_i / out_mean_ll_i /
+ * out_pwaic_i: [n_rows] each, any may be NULL; out_ll_sample [n_sets] or NULL; out_totals[3] (required): sum_i lppd_i, sum_i mean_ll_i,
+ * sum_i p_waic_i - elpd_waic = out_totals[0] - out_totals[2], WAIC = -2 elpd_waic.  Every cross-row sum is made of per-workgroup
+ * float64 partials added in a fixed order: two calls return the same bits, however the sets are grouped.  NPBNN_E_ARG before any
+ * evaluation: another lik_kind, NULL out_totals, sigma_sets missing or holding a non-positive or non-finite entry, targets of another
+ * width, a label outside [0, out_dim); NPBNN_E_STATE: no labels / targets on `which`.  NPBNN_E_ARG after the passes: a prediction that
+ * is NaN. */
+int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which, int lik_kind,
+                            const double* sigma_sets, double* out_lppd_i, double* out_mean_ll_i, double* out_pwaic_i,
+                            double* out_ll_sample, double out_totals[3]);
 
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events

@@ -393,6 +393,53 @@ class HipContext:
             capi.dptr(summary), None if keep is None else keep.ctypes.data_as(C.POINTER(C.c_uint8))))
         return dict(cube=cube, bf=bf, summary=summary, keep=None if keep is None else keep.astype(bool))
 
+    def predict_sets_lppd(self, weight_sets, lik_kind, sigma_sets=None, act_prm_sets=None, which=capi.TRAIN, pointwise=True):
+        """Log pointwise predictive density and WAIC terms of several weight sets on the resident matrix, against the labels
+        (``lik_kind`` LIK_CATEGORICAL) or targets (LIK_GAUSS, ``sigma_sets`` [n_sets, n_targets] or [n_sets]) set on it
+        (npbnn_predict_sets_lppd).  With ``ll[s, i]`` the log-likelihood of row ``i`` under set ``s``: a dict with the totals
+        ``lppd`` (sum of ``logsumexp_s ll - log S``), ``mean_log_lik`` (sum of ``mean_s ll``), ``p_waic`` (sum of ``var_s ll``,
+        ddof 1), ``log_lik_sample`` [n_sets] (``sum_i ll``), and with ``pointwise`` the three [n_rows] arrays ``lppd_i``,
+        ``mean_log_lik_i``, ``p_waic_i`` (None otherwise).  The sets replay as in ``predict_sets_summary``; ``ll`` never leaves
+        the device."""
+        if lik_kind not in (capi.LIK_CATEGORICAL, capi.LIK_GAUSS):
+            raise ValueError("predict_sets_lppd: lik_kind must be LIK_CATEGORICAL or LIK_GAUSS (predicted-sigma regression and the "
+                             "count likelihoods are out of scope), got %r" % (lik_kind,))
+        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
+            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
+        packed = capi.as_f64(packed)
+        n_sets, n_rows = packed.shape[0], self.n_rows[which]
+        if n_sets < 1:
+            raise ValueError("predict_sets_lppd: no weight sets")
+        if n_rows < 1:
+            raise ValueError("predict_sets_lppd: the matrix has no rows")
+        sig = None
+        if lik_kind == capi.LIK_GAUSS:
+            if sigma_sets is None:
+                raise ValueError("predict_sets_lppd: the Gaussian likelihood needs sigma_sets")
+            sig = np.asarray(sigma_sets, dtype=np.float64)
+            if sig.ndim == 1:
+                sig = sig.reshape(-1, 1)
+            if sig.ndim != 2 or sig.shape[0] != n_sets or sig.shape[1] not in (1, self.n_out):
+                raise ValueError("predict_sets_lppd: sigma_sets is %s, expected (%d, %d)" % (sig.shape, n_sets, self.n_out))
+            sig = capi.as_f64(np.broadcast_to(sig, (n_sets, self.n_out)))
+            if not (np.all(np.isfinite(sig)) and np.all(sig > 0)):
+                raise ValueError("predict_sets_lppd: every sigma must be positive and finite")
+        elif sigma_sets is not None:
+            raise ValueError("predict_sets_lppd: sigma_sets goes with LIK_GAUSS only")
+        ap = None
+        if act_prm_sets is not None and self.arch.n_layers > 1:
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+            if ap.shape[0] != n_sets:
+                raise ValueError("predict_sets_lppd: %d slope vectors for %d weight sets" % (ap.shape[0], n_sets))
+        point = [np.empty(n_rows, dtype=np.float64) for _ in range(3)] if pointwise else [None] * 3
+        trace = np.empty(n_sets, dtype=np.float64)
+        totals = np.zeros(3, dtype=np.float64)
+        self._chk(self._lib.npbnn_predict_sets_lppd(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which, int(lik_kind), capi.dptr(sig),
+                                                    capi.dptr(point[0]), capi.dptr(point[1]), capi.dptr(point[2]), capi.dptr(trace),
+                                                    capi.dptr(totals)))
+        return dict(lppd=float(totals[0]), mean_log_lik=float(totals[1]), p_waic=float(totals[2]), log_lik_sample=trace,
+                    lppd_i=point[0], mean_log_lik_i=point[1], p_waic_i=point[2])
+
     def predict_pdp(self, weight_sets, focal, grid, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
         prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]

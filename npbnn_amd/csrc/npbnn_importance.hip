@@ -11,7 +11,8 @@
 // checked by a kernel of their own before anything is written.
 //
 // npbnn_predict_sets_summary: the sets replay as in npbnn_predict_sets (groups that share their slopes, the float32 retry; the replay
-// is replay_sets_accumulate, which npbnn_predict_sets_support of npbnn_support.hip calls too); after each
+// is replay_sets_accumulate, which npbnn_predict_sets_support of npbnn_support.hip and, in a mode of its own, npbnn_predict_sets_lppd of
+// npbnn_lppd.hip call too); after each
 // group summary_accumulate_kernel folds the group's float32 predictions [g][rows][C] into uint32 votes (mode 0: per set and row the
 // first class holding the row's maximum - numpy's argmax) or float64 sums (mode 1: set after set - the order np.mean(axis=0) adds a
 // C-contiguous [S, N, C] array in).  Streaming: g x N x C floats in, N x C accumulators in and out, one thread per row (mode 0) or per
@@ -322,7 +323,8 @@ extern "C" int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* c
 }
 
 int npbnn_api::replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which,
-                                      int apply_out_fn, int mode, double* d_acc, int* d_flag) {
+                                      int apply_out_fn, int mode, double* d_acc, int* d_flag, const ReplayLppd* lppd) {
+    if (mode == kReplayLppd && (!lppd || apply_out_fn)) return fail(ctx, NPBNN_E_INTERNAL, "%s: the log-likelihood replay takes pre-output values", who);
     Dataset& d = ctx->ds[which];
     const int C = ctx->net.n_out;
     const int n_act = ctx->net.n_layers - 1;
@@ -383,7 +385,9 @@ int npbnn_api::replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const dou
         }
         // the group's predictions [g][rows][C] into the accumulator, before the next group overwrites them
         tm.mark(2, st);
-        if (mode == 0) {
+        if (mode == kReplayLppd) {
+            launch_lppd_accumulate(st, ctx->d_y.get(), g, s0, n_rows, C, d_acc, *lppd, d_flag);
+        } else if (mode == kReplayVotes) {
             unsigned* votes = reinterpret_cast<unsigned*>(d_acc);
             if (C % 4 == 0)
                 hipLaunchKernelGGL(summary_votes_kernel<true>, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g, n_rows, C, votes, d_flag);

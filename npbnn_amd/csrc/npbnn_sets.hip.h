@@ -51,13 +51,34 @@ struct FiTimer {
     }
 };
 
+// What replay_sets_accumulate folds a group's float32 values into
+enum { kReplayVotes = 0, kReplaySums = 1, kReplayLppd = 2 };
+
+constexpr int kLppdAcc = 5;                        // float64 accumulators per row of kReplayLppd, each an array [n_rows]
+
+// The extra pointers of kReplayLppd (npbnn_lppd.hip), all on the device.  The accumulator d_acc is [kLppdAcc][n_rows]: the running
+// maximum m of the row's log-likelihoods, sum exp(ll - m), K (the row's ll under the first set), sum (ll - K), sum (ll - K)^2.
+struct ReplayLppd {
+    int lik_kind = 0;                 // NPBNN_LIK_CATEGORICAL or NPBNN_LIK_GAUSS
+    const int* labels = nullptr;      // [n_rows] (categorical)
+    const float* targets = nullptr;   // [n_rows][C] (Gaussian)
+    const double* lconst = nullptr;   // [n_sets][C] -0.5 log(2 pi) - log(sigma) (Gaussian)
+    const double* isigma = nullptr;   // [n_sets][C] 1 / sigma (Gaussian)
+    double* part = nullptr;           // [n_sets][n_wg]: every workgroup's sum of its rows' ll under a set
+    int n_wg = 0;                     // workgroups of the accumulate launch: grid_for(n_rows)
+};
+
 // The n_sets weight sets against the resident matrix `which`, group after group as npbnn_predict_sets replays them (sets that share
 // their slopes travel together, the float32 retry), each group's float32 predictions folded into d_acc before the next group
-// overwrites them: mode 0 uint32 votes [n_rows][C] (d_acc read as unsigned), mode 1 float64 sums [n_rows][C], in set order.  d_acc
-// (n_rows x C doubles) and the flag word d_flag are the caller's, zeroed by it in stream order before the call; kFlagNaN is raised
-// there.  `who` names the entry in error messages.  Leaves the pass and accumulation times in ctx->fi_ns[1], [2] (NPBNN_FI_TIMING).
-// Defined in npbnn_importance.hip.
+// overwrites them: kReplayVotes uint32 votes [n_rows][C] (d_acc read as unsigned), kReplaySums float64 sums [n_rows][C], in set order;
+// kReplayLppd (with `lppd`, and apply_out_fn 0: the values are the pre-output ones) the per-row log-likelihood accumulators above.  d_acc
+// (n_rows x C doubles, or kLppdAcc x n_rows) and the flag word d_flag are the caller's, zeroed by it in stream order before the call;
+// kFlagNaN (and kFlagBadLabel, kReplayLppd) is raised there.  `who` names the entry in error messages.  Leaves the pass and accumulation
+// times in ctx->fi_ns[1], [2] (NPBNN_FI_TIMING).  Defined in npbnn_importance.hip.
 int replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which, int apply_out_fn,
-                           int mode, double* d_acc, int* d_flag);
+                           int mode, double* d_acc, int* d_flag, const ReplayLppd* lppd = nullptr);
+
+// lppd_accumulate_kernel over a group's values y [g][n_rows][C], the sets s0 .. s0 + g - 1.  Defined in npbnn_lppd.hip.
+void launch_lppd_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int C, double* d_acc, const ReplayLppd& a, int* d_flag);
 
 }  // namespace npbnn_api

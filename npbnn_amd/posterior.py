@@ -119,6 +119,22 @@ class _SamplePredictor:
         return self._ctx.predict_sets_support(self._packed, mode, labels, thresholds, act_prm_sets=self._slopes,
                                               apply_out_fn=self._kind is not None, **kw)
 
+    def lppd(self, features, labels, lik_kind, sigma_sets=None, pointwise=False):
+        """``HipContext.predict_sets_lppd``'s dict for the stored samples on ``features`` against ``labels`` (class indices,
+        LIK_CATEGORICAL) or targets (LIK_GAUSS, ``sigma_sets`` per sample): the log-likelihood matrix stays on the device
+        (npbnn_predict_sets_lppd).  A custom output callable has no device route: its stack is built on the host and goes through
+        ``posterior_lppd``."""
+        if self._kind is None and self._out_fn is not None:
+            from .lppd import log_lik_of_stack, posterior_lppd
+            res = posterior_lppd(log_lik_of_stack(self.predict(features), labels, lik_kind, sigma_sets))
+            return res if pointwise else dict(res, lppd_i=None, mean_log_lik_i=None, p_waic_i=None)
+        ctx = self._load(features)
+        if lik_kind == capi.LIK_CATEGORICAL:
+            ctx.set_labels(labels)
+        else:
+            ctx.set_targets(labels)
+        return ctx.predict_sets_lppd(self._packed, lik_kind, sigma_sets=sigma_sets, act_prm_sets=self._slopes, pointwise=pointwise)
+
     def close(self):
         self._ctx.close()
 
