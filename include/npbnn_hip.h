@@ -224,7 +224,17 @@ int npbnn_predict_sets(npbnn_ctx* ctx, const double* W_sets, const double* act_p
  *   1  grid-batched kernel (networks on the LDS-resident path with narrow layers): one read of X per group of sets computes layer 0
  *      with the focal columns at 0; each grid point adds its shift sum_f grid[g][f] * W0[:, f] and runs the later layers;
  *   2  one pass of the evaluation kernels per (grid point, set), the grid values folded into layer 0's bias like col_override.
- * Sums over the sets run in a fixed order (deterministic results).  NPBNN_PDP_PER_GRID=1 (environment) forces route 2. */
+ * Sums over the sets run in a fixed order (deterministic results).  NPBNN_PDP_PER_GRID=1 (environment) forces route 2.
+ * Route 1's envelope, for in_dim F and layer widths out_dim[0] = H0, out_dim[1], ..., out_dim[n_layers - 1]; a network on the
+ * LDS-resident path that meets all four limits takes route 1, every other one route 2 (tests/test_hip_pdp_envelope.py holds both
+ * sides of each limit to the float64 oracle).  With H0P = 32 when H0 <= 32, else 64:
+ *   a  H0 <= 64;
+ *   b  round_up(F, 16) * H0P * 4 bytes <= 64 KiB: one set's first layer in LDS (F <= 512 when H0 <= 32, F <= 256 above);
+ *   c  out_dim[l] <= 32 for every l >= 1, and out_dim[0] <= 32 as well when n_layers == 1 (the outputs stay in 32 registers);
+ *   d  (64 / H0P) * T * 4 bytes <= 32 KiB, T = sum over l >= 1 of round_up(out_dim[l], 4) + out_dim[l] * round_up(out_dim[l-1], 8):
+ *      the later layers of the 64 / H0P sets of one launch in LDS (after H0 = 32, three layers of 32 and 4 outputs have T = 3300
+ *      and fit, four layers of 32 have T = 4356 and do not).
+ * These figures are constants of the code (kPdp* in npbnn_pdp.hip), chosen for register and LDS room, not measured cross-over points. */
 int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, const int32_t* focal, int32_t n_focal,
                       const double* grid, int32_t n_grid, const double* col_override, int which, int apply_out_fn, double* out_mean);
 

@@ -451,7 +451,9 @@ class HipContext:
         if act_prm_sets is not None and self.arch.n_layers > 1:
             ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
         cols = np.ascontiguousarray(focal, dtype=np.int32).ravel()
-        g = capi.as_f64(np.asarray(grid, dtype=np.float64).reshape(-1, len(cols)))
+        g = np.asarray(grid, dtype=np.float64)
+        # (no focal column: the grid has rows and no entries, so its first dimension alone says how many points there are)
+        g = capi.as_f64(g.reshape(-1, len(cols)) if len(cols) else g.reshape(g.shape[0] if g.ndim else 1, 0))
         co = None if col_override is None else capi.as_f64(np.asarray(col_override, dtype=np.float64).ravel())
         out = np.empty((g.shape[0], self.n_rows[which], self.n_out), dtype=np.float64)
         self._chk(self._lib.npbnn_predict_pdp(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets,

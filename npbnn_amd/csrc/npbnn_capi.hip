@@ -204,8 +204,13 @@ int build_net(npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
             }
             // rows per tile in the image (NetMeta::l0_rows): a dense fp16-split first layer of three or more tiles whose width is not a
             // multiple of 16 is stored without its padding rows (the builds for one and two tiles - every BASELINE shape - keep 16)
+            // (never a network of one matrix: its first layer's positions are the outputs' - the predictions and the likelihood read
+            // output c at position c, and there is no layer 1 whose weights could meet the moved units.  Until this was excluded, one
+            // matrix of 33 or more outputs, not a multiple of 16, gave its outputs in the image's order: found by the partial-dependence
+            // envelope test's 33-output case on route 2, wrong by 0.2 in a probability)
             net.l0_rows = 16;
-            if (f16 && ctx->l0_blocks.empty() && L.mt >= 3 && out % 16 != 0 && !getenv("NPBNN_NO_COMPACT_ROWS")) net.l0_rows = (out + L.mt - 1) / L.mt;
+            if (f16 && ctx->l0_blocks.empty() && a->n_layers >= 2 && L.mt >= 3 && out % 16 != 0 && !getenv("NPBNN_NO_COMPACT_ROWS"))
+                net.l0_rows = (out + L.mt - 1) / L.mt;
             off += slots * (f16 ? 32 * net.l0_rows : 256);
         } else if (l == 1 && net.l1_f16) {
             off += ((net.L[0].mt + 1) / 2) * 512;      // a high and a low block of 256 floats per K-step

@@ -122,7 +122,7 @@ size_t resident_lds_bytes(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16, i
         if (l == 0) {
             const int units = f16 ? (in + 31) / 32 : (in + 15) / 16;
             int rows = 16;
-            if (f16 && ctx->l0_blocks.empty() && mt >= 3 && out % 16 != 0) rows = (out + mt - 1) / mt;
+            if (f16 && ctx->l0_blocks.empty() && a->n_layers >= 2 && mt >= 3 && out % 16 != 0) rows = (out + mt - 1) / mt;
             long long slots = (long long)mt * units;
             if (!ctx->l0_blocks.empty()) {       // block-structured first layer (npbnn_set_layer_mask): per output tile the hull of its K-units
                 const int g16 = (in + 15) / 16, per_unit = f16 ? 2 : 1;

@@ -46,6 +46,27 @@ def test_plain_evaluation_against_the_oracle(hidden, fun, bias):
     ctx.close()
 
 
+@pytest.mark.parametrize("n_out,bias", [(33, 1), (45, 0), (50, 1)])
+def test_one_matrix_network_keeps_its_outputs_in_place(n_out, bias):
+    """A network of one matrix has no layer 1 to meet the moved units: its three or more tiles keep 16 rows, so that output c is
+    read where unit c is (with the compact image the predictions came back in the image's order)."""
+    rs = np.random.default_rng(n_out)
+    n, f = 403, 40
+    x = rs.standard_normal((n, f))
+    lab = rs.integers(0, n_out, n)
+    w = [rs.normal(0, 1.0 / np.sqrt(f + 1), (n_out, f + bias))]
+    y64 = orc.forward(x, w, orc.Act("tanh"), orc.out_softmax)
+    ctx = bn.HipContext(0)
+    ctx.set_data(x)
+    ctx.set_labels(lab)
+    ctx.set_arch_from_weights(w, f, 3, 0, 0, 0)
+    got = ctx.predict(w)
+    assert np.max(np.abs(got - y64)) <= 2e-5
+    np.testing.assert_allclose(ctx.eval(w)["loglik"], orc.lik_categorical(y64, lab, np.arange(n)), rtol=5e-6)
+    assert ctx.l0_mode() == "f16-split"
+    ctx.close()
+
+
 @pytest.mark.parametrize("hidden,fun", [([50, 5], "ReLU"), ([40, 6], "tanh")])
 def test_chain_on_the_compact_image_stays_on_the_true_weights(hidden, fun):
     """Every accepted proposal is committed to the device's weight image entry by entry, at the positions the host worked out for

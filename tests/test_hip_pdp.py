@@ -22,14 +22,18 @@ def quiet(f, *a, **k):
         return f(*a, **k)
 
 
-def device_means(x, weights, focal, grid, fun="tanh", out_kind=capi.OUT_SOFTMAX, slopes=None, override=None):
-    """(per grid point and row the mean over the sets, route taken)"""
+def device_means(x, weights, focal, grid, fun="tanh", out_kind=capi.OUT_SOFTMAX, slopes=None, override=None, which=capi.TRAIN,
+                 apply_out_fn=True, x_test=None, trainable=False, want_l0=False):
+    """(per grid point and row of the table ``which`` the mean over the sets, route taken[, layer-0 path of the last launch])"""
     ctx = bn.HipContext()
     try:
         ctx.set_data(x)
-        ctx.set_arch_from_weights(weights[0], x.shape[1], bn.ActFun(fun=fun).device_kind(), out_kind, capi.LIK_NONE)
-        y = ctx.predict_pdp(weights, focal, grid, act_prm_sets=slopes, col_override=override)
-        return y, ctx.info(capi.INFO_PDP_ROUTE)
+        if x_test is not None:
+            ctx.set_data(x_test, capi.TEST)
+        ctx.set_arch_from_weights(weights[0], x.shape[1], bn.ActFun(fun=fun, trainable=trainable).device_kind(), out_kind, capi.LIK_NONE)
+        y = ctx.predict_pdp(weights, focal, grid, act_prm_sets=slopes, col_override=override, which=which, apply_out_fn=apply_out_fn)
+        route = ctx.info(capi.INFO_PDP_ROUTE)
+        return (y, route, ctx.l0_mode()) if want_l0 else (y, route)
     finally:
         ctx.close()
 
