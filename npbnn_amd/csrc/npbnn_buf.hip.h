@@ -1,6 +1,6 @@
 // Owners of the library's device (hipMalloc) and page-locked host (hipHostMalloc) memory.  Every allocation the library keeps is
-// one of these; the only other calls of the allocator are npbnn_pinned_alloc / npbnn_pinned_free (memory handed to the caller) and
-// the matrices a context may share with others (npbnn_share_data).  Not part of the ABI.
+// one of these, the matrices that contexts share (npbnn_share_data: FeatureStore, npbnn_ctx.hip.h) included; the only other calls of
+// the allocator are npbnn_pinned_alloc / npbnn_pinned_free (memory handed to the caller).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

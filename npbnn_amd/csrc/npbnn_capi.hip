@@ -21,29 +21,19 @@ int fail(npbnn_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
-void free_dataset(Dataset& d) {
-    if (d.X && !d.borrowed) (void)hipFree(d.X);
-    if (d.X16 && !d.borrowed) (void)hipFree(d.X16);
-    if (d.X16w && !d.x16w_borrowed) (void)hipFree(d.X16w);
-    d = Dataset();
+// What a context keeps for a table (labels, targets, weights, permuted columns) belongs to the matrix it came with, and goes with it.
+void forget_rows(npbnn_ctx* ctx, int which) {
+    ctx->ds[which] = Dataset();
+    ctx->ds[which].m = &ctx->store->table[which];
 }
 
-void destroy_ctx(npbnn_ctx* c);
-
-// a borrower lets go of its owner's matrices (before it uploads its own, or when it is destroyed)
-void unshare_data(npbnn_ctx* ctx) {
-    npbnn_ctx* owner = ctx->data_owner;
-    if (!owner) return;
-    for (int w = 0; w < 2; ++w)
-        if (ctx->ds[w].borrowed) {
-            ctx->ds[w].X = nullptr; ctx->ds[w].X16 = nullptr; ctx->ds[w].borrowed = false; ctx->ds[w].f16_state = 0;
-            if (ctx->ds[w].x16w_borrowed) { ctx->ds[w].X16w = nullptr; ctx->ds[w].x16w_borrowed = false; }
-        }
-    ctx->d_xscale = nullptr;          // (the scales travel with the training matrix)
-    ctx->d_wscale = nullptr;
-    ctx->scale_F = 0;
-    ctx->data_owner = nullptr;
-    if (--owner->n_borrowers == 0 && owner->zombie) destroy_ctx(owner);
+// The context lets go of the store it holds (freed here if nobody else holds it: the device is current) and holds `store` instead.
+// taken: from another context (npbnn_share_data), not for its own uploads.
+void hold_store(npbnn_ctx* ctx, std::shared_ptr<FeatureStore> store, bool taken) {
+    ctx->store = std::move(store);
+    ctx->store_taken = taken;
+    forget_rows(ctx, 0);
+    forget_rows(ctx, 1);
 }
 
 template <typename T>
@@ -54,43 +44,42 @@ int upload_matrix(npbnn_ctx* ctx, const T* X, int64_t n_rows, int32_t F, int whi
                     (long long)n_rows, F, which);
     if (n_rows > (int64_t)1 << 30) return fail(ctx, NPBNN_E_ARG, "set_data: too many rows");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (ctx->n_borrowers > 0) return fail(ctx, NPBNN_E_STATE, "set_data: %d other context(s) use this one's matrices (npbnn_share_data)", ctx->n_borrowers);
-    if (ctx->data_owner) {       // a borrower that gets data of its own: all borrowed matrices go back first
-        unshare_data(ctx);
-        free_dataset(ctx->ds[0]);
-        free_dataset(ctx->ds[1]);
-    }
+    if (!ctx->store_taken && ctx->store.use_count() > 1)
+        return fail(ctx, NPBNN_E_STATE, "set_data: %d other context(s) use this one's matrices (npbnn_share_data)", (int)ctx->store.use_count() - 1);
+    if (ctx->store_taken)        // data of its own for a context that took another's: it lets go of both tables first
+        hold_store(ctx, std::make_shared<FeatureStore>(ctx->device), false);
+    ctx->store->table[which] = FeatureTable();
+    forget_rows(ctx, which);
     Dataset& d = ctx->ds[which];
-    free_dataset(d);
     if (which == 0) {            // the fp16-split scales come from the training matrix
-        if (ctx->d_xscale) { (void)hipFree(ctx->d_xscale); ctx->d_xscale = nullptr; }
-        if (ctx->d_wscale) { (void)hipFree(ctx->d_wscale); ctx->d_wscale = nullptr; }
-        ctx->scale_F = 0;
-        if (ctx->ds[1].X16) { (void)hipFree(ctx->ds[1].X16); ctx->ds[1].X16 = nullptr; }
-        if (ctx->ds[1].X16w) { (void)hipFree(ctx->ds[1].X16w); ctx->ds[1].X16w = nullptr; }
-        ctx->ds[1].f16_state = 0;
+        FeatureStore& fs = *ctx->store;
+        fs.xscale.reset();
+        fs.wscale.reset();
+        fs.scale_F = 0;
+        fs.table[1].X16.reset();
+        fs.table[1].X16w.reset();
+        fs.table[1].f16_state = 0;
     }
-    d.n_rows = n_rows;
-    d.F = F;
-    d.Fp = round_up(F, 16);
-    d.n_tiles = (int)((n_rows + 15) / 16);
-    const size_t n_pad = (size_t)d.n_tiles * 16;
-    const size_t bytes = n_pad * d.Fp * sizeof(float);
-    HIP_TRY(ctx, hipMalloc(&d.X, bytes));
+    d.m->n_rows = n_rows;
+    d.m->F = F;
+    d.m->Fp = round_up(F, 16);
+    d.m->n_tiles = (int)((n_rows + 15) / 16);
+    const size_t n_pad = (size_t)d.m->n_tiles * 16;
+    if (int rc = d.m->X.reserve(ctx, n_pad * d.m->Fp)) return rc;
     // convert + pad on the host in slabs, so the staging buffer stays small
     const size_t slab_rows = 16384;
-    std::vector<float> stage(slab_rows * d.Fp);
+    std::vector<float> stage(slab_rows * d.m->Fp);
     for (size_t r0 = 0; r0 < n_pad; r0 += slab_rows) {
         const size_t nr = std::min(slab_rows, n_pad - r0);
-        std::fill(stage.begin(), stage.begin() + nr * d.Fp, 0.0f);
+        std::fill(stage.begin(), stage.begin() + nr * d.m->Fp, 0.0f);
         for (size_t r = 0; r < nr; ++r) {
             const size_t gr = r0 + r;
             if (gr >= (size_t)n_rows) break;
             const T* src = X + gr * F;
-            float* dst = stage.data() + r * d.Fp;
+            float* dst = stage.data() + r * d.m->Fp;
             for (int c = 0; c < F; ++c) dst[c] = (float)src[c];
         }
-        HIP_TRY(ctx, hipMemcpy(d.X + r0 * d.Fp, stage.data(), nr * d.Fp * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(d.m->X + r0 * d.m->Fp, stage.data(), nr * d.m->Fp * sizeof(float), hipMemcpyHostToDevice));
     }
     // A net built on another training matrix is built again, as npbnn_set_arch would build it on this one: the choice of path reads
     // the row count (wide_needed) and the fp16-split positions of the chain's proposals carry the old matrix's column scales
@@ -105,10 +94,10 @@ int upload_matrix(npbnn_ctx* ctx, const T* X, int64_t n_rows, int32_t F, int whi
 int check_rows(npbnn_ctx* ctx, int which, int64_t n_rows, const char* what) {
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
     if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "%s: which must be 0 or 1", what);
-    if (!ctx->ds[which].X) return fail(ctx, NPBNN_E_STATE, "%s: call npbnn_set_data first", what);
-    if (ctx->ds[which].n_rows != n_rows)
+    if (!ctx->ds[which].m->X) return fail(ctx, NPBNN_E_STATE, "%s: call npbnn_set_data first", what);
+    if (ctx->ds[which].m->n_rows != n_rows)
         return fail(ctx, NPBNN_E_ARG, "%s: %lld rows but the data matrix has %lld", what, (long long)n_rows,
-                    (long long)ctx->ds[which].n_rows);
+                    (long long)ctx->ds[which].m->n_rows);
     return NPBNN_OK;
 }
 
@@ -294,27 +283,27 @@ eval_fn_t pick_kernel(const NetMeta& net, int n_cand) {
 // Per column of a resident matrix under the context's scales (split_quality_kernel): how far the fp16 pair's largest counted entry
 // error is from its bounds - max(error / (2^-17 x mean |entry|), error / (2^-12 x typical |entry|)); <= 1 passes, 0 for an exact column.
 static int column_quality(npbnn_ctx* ctx, const Dataset& d, std::vector<double>* badness) {
-    const int Fq = d.Fp;
+    const int Fq = d.m->Fp;
     DevBuf<unsigned> d_err;
     DevBuf<unsigned long long> d_sum;
     if (int rc = d_err.reserve(ctx, (size_t)Fq)) return rc;
     if (int rc = d_sum.reserve(ctx, (size_t)Fq * 3)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_err, 0, (size_t)Fq * sizeof(unsigned), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, (size_t)Fq * 3 * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(split_quality_kernel, dim3((Fq + 255) / 256, (unsigned)((d.n_rows + 1023) / 1024)), dim3(256), 0, ctx->stream,
-                       (const float*)d.X, (long long)d.n_rows, d.Fp, (const float*)ctx->d_xscale, d_err.get(), d_sum.get(), d_sum + Fq, d_sum + 2 * (size_t)Fq);
+    hipLaunchKernelGGL(split_quality_kernel, dim3((Fq + 255) / 256, (unsigned)((d.m->n_rows + 1023) / 1024)), dim3(256), 0, ctx->stream,
+                       (const float*)d.m->X, (long long)d.m->n_rows, d.m->Fp, (const float*)ctx->store->xscale, d_err.get(), d_sum.get(), d_sum + Fq, d_sum + 2 * (size_t)Fq);
     std::vector<unsigned> h_err((size_t)Fq);
     std::vector<unsigned long long> h_sum((size_t)Fq * 3);
     HIP_TRY(ctx, hipMemcpyAsync(h_err.data(), d_err, h_err.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h_sum.data(), d_sum, h_sum.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    badness->assign((size_t)d.F, 0.0);
-    for (int c = 0; c < d.F; ++c) {
+    badness->assign((size_t)d.m->F, 0.0);
+    for (int c = 0; c < d.m->F; ++c) {
         float e;
         memcpy(&e, &h_err[(size_t)c], 4);
         const unsigned long long cnt = h_sum[2 * (size_t)Fq + c];
         if (cnt == 0 || !(e > 0.f)) continue;                 // an all-zero column, or one the pair holds exactly
-        const double mean_abs = (double)h_sum[(size_t)c] / 268435456.0 / (double)d.n_rows;
+        const double mean_abs = (double)h_sum[(size_t)c] / 268435456.0 / (double)d.m->n_rows;
         const double typical = std::exp2((double)(long long)h_sum[(size_t)Fq + c] / 65536.0 / (double)cnt);
         const double by_mean = mean_abs > 0.0 ? (double)e / mean_abs / (double)kF16QualityTol : 1e300;
         const double by_typical = (double)e / typical / (double)kF16TypicalTol;
@@ -326,54 +315,54 @@ static int column_quality(npbnn_ctx* ctx, const Dataset& d, std::vector<double>*
 // ---- fp16-split data: scales from the training matrix, split copies built on the device ----
 int ensure_scales(npbnn_ctx* ctx) {
     Dataset& tr = ctx->ds[0];
-    if (!tr.X) return fail(ctx, NPBNN_E_STATE, "the fp16-split path needs the training matrix first");
-    if (ctx->d_xscale && ctx->scale_F == tr.F) return NPBNN_OK;
-    const int Fp16 = round_up(tr.F, 32);
+    if (!tr.m->X) return fail(ctx, NPBNN_E_STATE, "the fp16-split path needs the training matrix first");
+    if (ctx->store->xscale && ctx->store->scale_F == tr.m->F) return NPBNN_OK;
+    const int Fp16 = round_up(tr.m->F, 32);
     DevBuf<unsigned> d_max;
     if (int rc = d_max.reserve(ctx, (size_t)Fp16)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_max, 0, (size_t)Fp16 * sizeof(unsigned), ctx->stream));
-    const int row_blocks = (int)((tr.n_rows + 1023) / 1024);
-    hipLaunchKernelGGL(col_absmax_kernel, dim3((tr.Fp + 255) / 256, row_blocks), dim3(256), 0, ctx->stream, tr.X,
-                       (long long)tr.n_rows, tr.Fp, d_max);
-    if (!ctx->d_xscale) HIP_TRY(ctx, hipMalloc(&ctx->d_xscale, (size_t)Fp16 * sizeof(float)));
-    if (!ctx->d_wscale) HIP_TRY(ctx, hipMalloc(&ctx->d_wscale, (size_t)Fp16 * sizeof(float)));
-    hipLaunchKernelGGL(col_scale_kernel, dim3((Fp16 + 255) / 256), dim3(256), 0, ctx->stream, d_max, Fp16, ctx->d_xscale,
-                       ctx->d_wscale, (const int*)nullptr);
+    const int row_blocks = (int)((tr.m->n_rows + 1023) / 1024);
+    hipLaunchKernelGGL(col_absmax_kernel, dim3((tr.m->Fp + 255) / 256, row_blocks), dim3(256), 0, ctx->stream, tr.m->X,
+                       (long long)tr.m->n_rows, tr.m->Fp, d_max);
+    if (int rc = ctx->store->xscale.reserve(ctx, (size_t)Fp16)) return rc;
+    if (int rc = ctx->store->wscale.reserve(ctx, (size_t)Fp16)) return rc;
+    hipLaunchKernelGGL(col_scale_kernel, dim3((Fp16 + 255) / 256), dim3(256), 0, ctx->stream, d_max, Fp16, ctx->store->xscale,
+                       ctx->store->wscale, (const int*)nullptr);
     std::vector<unsigned> h((size_t)Fp16);
     HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_max, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->scale_F = tr.F;
-    ctx->f16_shifted_cols = 0;
-    ctx->f16_max_shift = 0;
-    tr.f16_state = 0;
+    ctx->store->scale_F = tr.m->F;
+    ctx->store->f16_shifted_cols = 0;
+    ctx->store->f16_max_shift = 0;
+    tr.m->f16_state = 0;
     for (unsigned bits : h) {
         float m;
         memcpy(&m, &bits, 4);
-        if (!std::isfinite(m)) tr.f16_state = -1;     // inf / NaN in the data: stay on the exact float32 path
+        if (!std::isfinite(m)) tr.m->f16_state = -1;     // inf / NaN in the data: stay on the exact float32 path
     }
     // Heavy-tailed columns: with the largest entry just under 1 the typical entries sit where the pair's absolute error floor
     // (2^-25) is a visible fraction of them.  Such a column's scale moves up by the power of two that brings its error / typical |value|
     // under the bound with a factor 2 to spare (the fp16 range above 1 is otherwise unused); the weights' scale moves down with it.
     // Columns inside the bound keep the scale they always had.
-    if (tr.f16_state == 0 && !getenv("NPBNN_F16_NO_SHIFT")) {
+    if (tr.m->f16_state == 0 && !getenv("NPBNN_F16_NO_SHIFT")) {
         std::vector<double> ratio;
         int rcq = column_quality(ctx, tr, &ratio);
         if (rcq) return rcq;
         std::vector<int> shift((size_t)Fp16, 0);
-        for (int c = 0; c < tr.F; ++c) {
+        for (int c = 0; c < tr.m->F; ++c) {
             if (!(ratio[(size_t)c] > 1.0)) continue;
             int k = (int)std::ceil(std::log2(ratio[(size_t)c])) + 1;
             if (k > kF16MaxShift) k = kF16MaxShift;
             shift[(size_t)c] = k;
-            ++ctx->f16_shifted_cols;
-            if (k > ctx->f16_max_shift) ctx->f16_max_shift = k;
+            ++ctx->store->f16_shifted_cols;
+            if (k > ctx->store->f16_max_shift) ctx->store->f16_max_shift = k;
         }
-        if (ctx->f16_shifted_cols > 0) {
+        if (ctx->store->f16_shifted_cols > 0) {
             DevBuf<int> d_shift;
             if (int rc = d_shift.reserve(ctx, (size_t)Fp16)) return rc;
             HIP_TRY(ctx, hipMemcpy(d_shift, shift.data(), (size_t)Fp16 * sizeof(int), hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(col_scale_kernel, dim3((Fp16 + 255) / 256), dim3(256), 0, ctx->stream, d_max, Fp16, ctx->d_xscale,
-                               ctx->d_wscale, (const int*)d_shift);
+            hipLaunchKernelGGL(col_scale_kernel, dim3((Fp16 + 255) / 256), dim3(256), 0, ctx->stream, d_max, Fp16, ctx->store->xscale,
+                               ctx->store->wscale, (const int*)d_shift);
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
     }
@@ -383,41 +372,41 @@ int ensure_scales(npbnn_ctx* ctx) {
 // 1 = the set has a usable fp16-split copy, 0 = it cannot be represented (the caller stays on float32)
 int ensure_x16(npbnn_ctx* ctx, int which, int* usable) {
     *usable = 0;
-    if (ctx->data_owner && ctx->ds[which].borrowed) {      // borrowed matrices come with their split copy, or without one
-        *usable = ctx->ds[which].f16_state > 0 ? 1 : 0;
+    if (ctx->store_taken) {      // a store taken from another context comes with its split copy, or without one
+        *usable = ctx->ds[which].m->f16_state > 0 ? 1 : 0;
         return NPBNN_OK;
     }
     int rc = ensure_scales(ctx);
     if (rc) return rc;
-    if (ctx->ds[0].f16_state < 0) return NPBNN_OK;
+    if (ctx->ds[0].m->f16_state < 0) return NPBNN_OK;
     Dataset& d = ctx->ds[which];
-    if (d.f16_state == 0) {
-        d.Fp16 = round_up(d.F, 32);
-        const size_t n_pad = (size_t)d.n_tiles * 16;
-        if (!d.X16) HIP_TRY(ctx, hipMalloc(&d.X16, n_pad * d.Fp16 * sizeof(float)));
+    if (d.m->f16_state == 0) {
+        d.m->Fp16 = round_up(d.m->F, 32);
+        const size_t n_pad = (size_t)d.m->n_tiles * 16;
+        if (int rc1 = d.m->X16.reserve(ctx, n_pad * d.m->Fp16)) return rc1;
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), ctx->stream));
-        const long long items = (long long)n_pad * (d.Fp16 / 8);
-        hipLaunchKernelGGL(split_x_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, d.X, (long long)n_pad, d.Fp,
-                           d.Fp16, ctx->d_xscale, d.X16, reinterpret_cast<unsigned*>(ctx->d_overflow.get()));
+        const long long items = (long long)n_pad * (d.m->Fp16 / 8);
+        hipLaunchKernelGGL(split_x_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, d.m->X, (long long)n_pad, d.m->Fp,
+                           d.m->Fp16, ctx->store->xscale, d.m->X16, reinterpret_cast<unsigned*>(ctx->d_overflow.get()));
         unsigned bits = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&bits, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         float m;
         memcpy(&m, &bits, 4);
-        d.f16_state = (std::isfinite(m) && m <= kF16Safe) ? 1 : -1;    // a test set far outside the training range
-        if (d.f16_state > 0) {      // and is the pair of fp16 numbers a fair picture of every column? (split_quality_kernel)
+        d.m->f16_state = (std::isfinite(m) && m <= kF16Safe) ? 1 : -1;    // a test set far outside the training range
+        if (d.m->f16_state > 0) {      // and is the pair of fp16 numbers a fair picture of every column? (split_quality_kernel)
             std::vector<double> ratio;
             int rcq = column_quality(ctx, d, &ratio);
             if (rcq) return rcq;
-            d.f16_worst_col = -1;
-            d.f16_worst_ratio = 0.0;
-            for (int c = 0; c < d.F; ++c)
-                if (ratio[(size_t)c] > d.f16_worst_ratio) { d.f16_worst_ratio = ratio[(size_t)c]; d.f16_worst_col = c; }
-            if (d.f16_worst_ratio > 1.0 && !getenv("NPBNN_F16_NO_QUALITY_CHECK")) d.f16_state = -2;   // heavy-tailed column(s) past what a moved scale holds
+            d.m->f16_worst_col = -1;
+            d.m->f16_worst_ratio = 0.0;
+            for (int c = 0; c < d.m->F; ++c)
+                if (ratio[(size_t)c] > d.m->f16_worst_ratio) { d.m->f16_worst_ratio = ratio[(size_t)c]; d.m->f16_worst_col = c; }
+            if (d.m->f16_worst_ratio > 1.0 && !getenv("NPBNN_F16_NO_QUALITY_CHECK")) d.m->f16_state = -2;   // heavy-tailed column(s) past what a moved scale holds
         }
-        if (d.f16_state < 0 && d.X16) { (void)hipFree(d.X16); d.X16 = nullptr; }      // (nobody will read it)
+        if (d.m->f16_state < 0) d.m->X16.reset();      // (nobody will read it)
     }
-    *usable = d.f16_state > 0 ? 1 : 0;
+    *usable = d.m->f16_state > 0 ? 1 : 0;
     return NPBNN_OK;
 }
 
@@ -450,10 +439,10 @@ int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32, int wa
         int rc0 = ensure_x16(ctx, which, &usable);
         if (rc0) return rc0;
         if (!usable && ctx->l0_option == NPBNN_L0_F16) {
-            if (d.f16_state == -2)
+            if (d.m->f16_state == -2)
                 return fail(ctx, NPBNN_E_RANGE, "fp16-split layer 0 was requested but column %d spans too many powers of two for a pair of fp16 "
                                                 "numbers, even with its scale moved as far as fp16 allows (largest entry error %.1f x the bound: 2^-17 of the column's mean, "
-                                                "2^-12 of its typical |value|)", d.f16_worst_col, d.f16_worst_ratio);
+                                                "2^-12 of its typical |value|)", d.m->f16_worst_col, d.m->f16_worst_ratio);
             return fail(ctx, NPBNN_E_RANGE, "fp16-split layer 0 was requested but the data cannot be represented in it");
         }
         want_f16 = usable != 0;
@@ -496,7 +485,7 @@ int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32, int wa
         // 36.4 -> 33.4 us per pass there (9 or 10 waves; 11: 35.0, 8: 35.0, 7: 41.9); single-candidate launches and shares of two rounds
         // or more are best at the build's full count (config 2: 30.6 us at 12 waves, 31.3 at 10).  NPBNN_WAVES: A/B switch.
         int w_use = wpb;
-        const double share = (double)d.n_tiles / (double)(ctx->n_cu > 0 ? ctx->n_cu : 1);
+        const double share = (double)d.m->n_tiles / (double)(ctx->n_cu > 0 ? ctx->n_cu : 1);
         if (n_cand > 1 && share > (double)w_use && share < 1.25 * (double)w_use && w_use - 2 >= 8) w_use -= 2;
         if (const char* e = getenv("NPBNN_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= wpb) w_use = v; }
         if (w_use != wpb) {
@@ -511,7 +500,7 @@ int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32, int wa
                                       "NPBNN_OPT_WIDE = 1 runs it on the weight-streamed path", wpb, ctx->net.image_floats * 4 / 1024);
     lp->wpb = wpb;
     lp->lds = lds;
-    int grid = (d.n_tiles + wpb - 1) / wpb;
+    int grid = (d.m->n_tiles + wpb - 1) / wpb;
     if (grid > ctx->n_cu) grid = ctx->n_cu;     // persistent: one workgroup per CU
     if (grid < 1) grid = 1;
     lp->grid = grid;
@@ -654,15 +643,15 @@ void report_eval_stamps(const DevBuf<unsigned long long>& stamps, int grid, int 
 
 EvalParams make_params(npbnn_ctx* ctx, const Dataset& d) {
     EvalParams p{};
-    p.X = ctx->net.l0_f16 ? d.X16 : d.X;
+    p.X = ctx->net.l0_f16 ? d.m->X16 : d.m->X;
     p.labels = d.labels;
     p.targets = d.targets;
     p.inst_w = nullptr;
     p.image = ctx->d_image;
-    p.n_rows = d.n_rows;
-    p.n_tiles = d.n_tiles;
+    p.n_rows = d.m->n_rows;
+    p.n_tiles = d.m->n_tiles;
     p.has_pass = 0;
-    p.Fp = ctx->net.l0_f16 ? d.Fp16 : d.Fp;
+    p.Fp = ctx->net.l0_f16 ? d.m->Fp16 : d.m->Fp;
     p.net = ctx->net;
     p.lay = layout_for(ctx, d);
     p.cand_slopes = nullptr;
@@ -670,9 +659,9 @@ EvalParams make_params(npbnn_ctx* ctx, const Dataset& d) {
 }
 
 int check_dataset_for_lik(npbnn_ctx* ctx, const Dataset& d, int lik) {
-    if (!d.X) return fail(ctx, NPBNN_E_STATE, "no data matrix for this set");
-    if (d.F != ctx->arch.in_dim)
-        return fail(ctx, NPBNN_E_ARG, "data has %d features but the network expects %d", d.F, ctx->arch.in_dim);
+    if (!d.m->X) return fail(ctx, NPBNN_E_STATE, "no data matrix for this set");
+    if (d.m->F != ctx->arch.in_dim)
+        return fail(ctx, NPBNN_E_ARG, "data has %d features but the network expects %d", d.m->F, ctx->arch.in_dim);
     if (lik == NPBNN_LIK_CATEGORICAL && !d.labels) return fail(ctx, NPBNN_E_STATE, "categorical likelihood needs labels (npbnn_set_labels_i64)");
     if (lik == NPBNN_LIK_GAUSS || lik_needs_row_scratch(lik)) {
         if (!d.targets) return fail(ctx, NPBNN_E_STATE, "this likelihood needs targets (npbnn_set_targets_f64)");
@@ -703,7 +692,7 @@ int rebuild_net(npbnn_ctx* ctx, bool f16) {
     if (f16) {
         scale.assign((size_t)ctx->n_weights, 1.0f);
         wscale.resize((size_t)round_up(ctx->arch.in_dim, 32));
-        HIP_TRY(ctx, hipMemcpy(wscale.data(), ctx->d_wscale, wscale.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(wscale.data(), ctx->store->wscale, wscale.size() * sizeof(float), hipMemcpyDeviceToHost));
     }
     for (int l = 0; l < ctx->net.n_layers; ++l) {
         const LayerMeta& L = ctx->net.L[l];
@@ -760,7 +749,7 @@ void launch_pack_weights(npbnn_ctx* ctx, const double* d_w, const double* d_col_
     if (ctx->wide) { wide_pack(ctx, d_w, d_col_override, image, flags); return; }
     const int total = pack_item_count(ctx->net, true);
     hipLaunchKernelGGL(pack_weights_kernel, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, d_w, d_col_override,
-                       ctx->n_classw ? ctx->d_classw : nullptr, image, ctx->net, ctx->net.l0_f16 ? ctx->d_wscale : nullptr, flags);
+                       ctx->n_classw ? ctx->d_classw : nullptr, image, ctx->net, ctx->net.l0_f16 ? ctx->store->wscale : nullptr, flags);
 }
 
 int launch_plain_eval(npbnn_ctx* ctx, const LaunchPlan& lp, int which) {
@@ -783,18 +772,6 @@ void launch_finalize(npbnn_ctx* ctx) {
 }  // namespace npbnn_api
 
 extern "C" void npbnn_set_global_error_(const char* msg) { g_last_error = msg ? msg : ""; }
-
-namespace npbnn_api {
-// the buffers go with the context (their destructors, the device current), its streams and events after them (npbnn_ctx_streams)
-void destroy_ctx(npbnn_ctx* c) {
-    (void)hipSetDevice(c->device);
-    free_dataset(c->ds[0]);
-    free_dataset(c->ds[1]);
-    if (c->d_xscale) (void)hipFree(c->d_xscale);
-    if (c->d_wscale) (void)hipFree(c->d_wscale);
-    delete c;
-}
-}  // namespace npbnn_api
 
 extern "C" {
 
@@ -827,6 +804,7 @@ int npbnn_create(int device_id, npbnn_ctx** out) {
         return fail(nullptr, NPBNN_E_ARG, "device %d is %s; this library is built for gfx950 (MI355X) only", device_id, prop.gcnArchName);
     std::unique_ptr<npbnn_ctx> c(new npbnn_ctx());          // (a failure part-way frees what was made)
     c->device = device_id;
+    hold_store(c.get(), std::make_shared<FeatureStore>(device_id), false);
     c->n_cu = prop.multiProcessorCount;
     c->lds_limit = 160 * 1024;
     HIP_TRY(nullptr, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -850,50 +828,26 @@ void npbnn_destroy(npbnn_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->data_owner) unshare_data(c);
-    if (c->n_borrowers > 0) {        // others still read this context's matrices: it goes when the last of them does
-        c->zombie = true;
-        return;
-    }
-    destroy_ctx(c);
+    delete c;        // the buffers with the device current, the store if nobody else holds it, the streams and events last (npbnn_ctx_streams)
 }
 
 int npbnn_share_data(npbnn_ctx* ctx, npbnn_ctx* owner) {
     if (!ctx || !owner || ctx == owner) return fail(ctx, NPBNN_E_ARG, "share_data: bad arguments");
-    while (owner->data_owner) owner = owner->data_owner;          // the root holds the memory
-    if (owner == ctx) return fail(ctx, NPBNN_E_ARG, "share_data: contexts borrow from each other");
+    const bool others = !ctx->store_taken && ctx->store.use_count() > 1;      // contexts that took this one's store
+    if (others && owner->store == ctx->store) return fail(ctx, NPBNN_E_ARG, "share_data: contexts borrow from each other");
     if (owner->device != ctx->device) return fail(ctx, NPBNN_E_ARG, "share_data: contexts on devices %d and %d", ctx->device, owner->device);
-    if (ctx->n_borrowers > 0) return fail(ctx, NPBNN_E_STATE, "share_data: %d other context(s) use this one's matrices", ctx->n_borrowers);
-    if (!owner->ds[0].X) return fail(ctx, NPBNN_E_STATE, "share_data: the owner has no training matrix");
+    if (others) return fail(ctx, NPBNN_E_STATE, "share_data: %d other context(s) use this one's matrices", (int)ctx->store.use_count() - 1);
+    if (!owner->ds[0].m->X) return fail(ctx, NPBNN_E_STATE, "share_data: the owner has no training matrix");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // the owner's fp16-split copies are built now (on its stream) so that borrowers never have to
+    // the owner's fp16-split copies are built now (on its stream) so that those who take its store never have to
     for (int w = 0; w < 2; ++w)
-        if (owner->ds[w].X && owner->l0_option != NPBNN_L0_F32) {
+        if (owner->ds[w].m->X && owner->l0_option != NPBNN_L0_F32) {
             int usable = 0;
             int rc = ensure_x16(owner, w, &usable);
             if (rc) { ctx->err = owner->err; return rc; }
         }
     HIP_TRY(ctx, hipStreamSynchronize(owner->stream));
-    if (ctx->data_owner) unshare_data(ctx);
-    free_dataset(ctx->ds[0]);
-    free_dataset(ctx->ds[1]);
-    if (ctx->d_xscale) (void)hipFree(ctx->d_xscale);
-    if (ctx->d_wscale) (void)hipFree(ctx->d_wscale);
-    for (int w = 0; w < 2; ++w) {
-        const Dataset& o = owner->ds[w];
-        if (!o.X) continue;
-        Dataset& d = ctx->ds[w];
-        d.X = o.X; d.X16 = o.X16; d.n_rows = o.n_rows; d.n_tiles = o.n_tiles; d.F = o.F; d.Fp = o.Fp; d.Fp16 = o.Fp16;
-        d.f16_state = o.f16_state;
-        d.borrowed = true;
-    }
-    ctx->d_xscale = owner->d_xscale;
-    ctx->f16_shifted_cols = owner->f16_shifted_cols;
-    ctx->f16_max_shift = owner->f16_max_shift;
-    ctx->d_wscale = owner->d_wscale;
-    ctx->scale_F = owner->scale_F;
-    ctx->data_owner = owner;
-    owner->n_borrowers += 1;
+    hold_store(ctx, owner->store, true);
     ctx->arch_set = false;            // (layer-0 layout depends on the data: set_arch again)
     return NPBNN_OK;
 }
@@ -911,7 +865,7 @@ int npbnn_set_labels_i64(npbnn_ctx* ctx, const int64_t* y, int64_t n_rows, int w
     if (rc) return rc;
     if (!y) return fail(ctx, NPBNN_E_ARG, "set_labels: null labels");
     Dataset& d = ctx->ds[which];
-    const size_t n_pad = (size_t)d.n_tiles * 16;
+    const size_t n_pad = (size_t)d.m->n_tiles * 16;
     std::vector<int> tmp(n_pad, -1);
     for (int64_t i = 0; i < n_rows; ++i) {
         if (y[i] < 0 || y[i] >= NPBNN_MAX_WIDTH)
@@ -930,7 +884,7 @@ int npbnn_set_targets_f64(npbnn_ctx* ctx, const double* Y, int64_t n_rows, int32
     if (rc) return rc;
     if (!Y || k < 1 || k > NPBNN_MAX_TARGETS) return fail(ctx, NPBNN_E_ARG, "set_targets: need 1..%d target columns, got %d", NPBNN_MAX_TARGETS, k);
     Dataset& d = ctx->ds[which];
-    const size_t n_pad = (size_t)d.n_tiles * 16;
+    const size_t n_pad = (size_t)d.m->n_tiles * 16;
     std::vector<float> tmp(n_pad * k, 0.0f);
     for (size_t i = 0; i < (size_t)n_rows * k; ++i) tmp[i] = (float)Y[i];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -949,7 +903,7 @@ int npbnn_set_row_weights(npbnn_ctx* ctx, const double* instance_w, int64_t n_ro
     if (instance_w) {
         int rc = check_rows(ctx, 0, n_rows, "set_row_weights");
         if (rc) return rc;
-        const size_t n_pad = (size_t)d.n_tiles * 16;
+        const size_t n_pad = (size_t)d.m->n_tiles * 16;
         std::vector<float> tmp(n_pad, 0.0f);
         for (int64_t i = 0; i < n_rows; ++i) tmp[i] = (float)instance_w[i];
         rc = d.inst_w.reserve(ctx, n_pad);
@@ -1062,8 +1016,8 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     if (!ctx || !out) return fail(ctx, NPBNN_E_ARG, "get_info: bad arguments");
     if (what == NPBNN_INFO_L0_F16) { *out = ctx->net.l0_f16; return NPBNN_OK; }
     if (what == NPBNN_INFO_WIDE) { *out = (ctx->arch_set && ctx->wide) ? 1 : 0; return NPBNN_OK; }
-    if (what == NPBNN_INFO_F16_MOVED_COLUMNS) { *out = ctx->f16_shifted_cols; return NPBNN_OK; }
-    if (what == NPBNN_INFO_F16_MAX_MOVE) { *out = ctx->f16_max_shift; return NPBNN_OK; }
+    if (what == NPBNN_INFO_F16_MOVED_COLUMNS) { *out = ctx->store->f16_shifted_cols; return NPBNN_OK; }
+    if (what == NPBNN_INFO_F16_MAX_MOVE) { *out = ctx->store->f16_max_shift; return NPBNN_OK; }
     if (what == NPBNN_INFO_PDP_ROUTE) { *out = ctx->pdp_route; return NPBNN_OK; }
     if (what >= NPBNN_INFO_PERMUTE_NS && what <= NPBNN_INFO_LPPD_FINAL_NS) { *out = ctx->fi_ns[what - NPBNN_INFO_PERMUTE_NS]; return NPBNN_OK; }
     if (ctx->arch_set && ctx->wide && (what == NPBNN_INFO_WAVES_PER_BLOCK || what == NPBNN_INFO_MAX_CANDIDATES || what == NPBNN_INFO_FAST_TAILS)) {
@@ -1083,7 +1037,7 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     }
     if (what == NPBNN_INFO_MAX_CANDIDATES) {        // what plan_launch would give a chain pass that asks for as many as fit
         *out = 1;
-        if (!ctx->arch_set || !ctx->ds[0].X) return NPBNN_OK;
+        if (!ctx->arch_set || !ctx->ds[0].m->X) return NPBNN_OK;
         int n = (max_inner_tiles(ctx->net) == 1 && !lik_needs_row_scratch(ctx->net.lik_kind)) ? kMaxCand : 1;
         if (n > max_cand_for(ctx->net.L[0].mt)) n = max_cand_for(ctx->net.L[0].mt);
         const WaveLayout lay = layout_for(ctx, ctx->ds[0], false);
@@ -1129,7 +1083,7 @@ static int eval_once(npbnn_ctx* ctx, const double* W_packed, const double* act_p
     f.n_waves = lp.n_waves;
     f.lik_kind = lik;
     f.k_targets = ctx->net.k_targets;
-    f.n_rows = d.n_rows;
+    f.n_rows = d.m->n_rows;
     f.lik_temp = lik_temp;
     f.sigma_given = sigma ? 1 : 0;
     if (sigma)
@@ -1187,7 +1141,7 @@ int npbnn_predict(npbnn_ctx* ctx, const double* W_packed, const double* act_prm,
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int C = ctx->net.n_out;
-    const size_t n_el = (size_t)d.n_rows * C;
+    const size_t n_el = (size_t)d.m->n_rows * C;
     std::vector<float> tmp(n_el);
     for (int attempt = 0; attempt < 2; ++attempt) {
     LaunchPlan lp;
@@ -1231,7 +1185,7 @@ int npbnn_predict_sets(npbnn_ctx* ctx, const double* W_sets, const double* act_p
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int C = ctx->net.n_out;
     const int n_act = ctx->net.n_layers - 1;
-    const size_t per_set = (size_t)d.n_rows * C;
+    const size_t per_set = (size_t)d.m->n_rows * C;
     const size_t wn = (size_t)ctx->n_weights;
     if ((rc = ctx->d_y.reserve(ctx, kMaxCand * per_set))) return rc;
     std::vector<float> tmp(kMaxCand * per_set);
@@ -1471,7 +1425,7 @@ int npbnn_time_eval(npbnn_ctx* ctx, const double* W_packed, int iters, double* m
     f.n_waves = lp.n_waves;
     f.lik_kind = lik;
     f.k_targets = ctx->net.k_targets;
-    f.n_rows = d.n_rows;
+    f.n_rows = d.m->n_rows;
     f.lik_temp = 1.0;
     f.out = ctx->d_out;
     rc = push_eval_params(ctx, p);

@@ -456,7 +456,7 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
     c.lik_temp = cfg->lik_temp;
     c.sigma_given = cfg->sigma_given;
     for (int j = 0; j < NPBNN_MAX_TARGETS; ++j) c.sigma_fixed[j] = cfg->sigma[j];
-    c.n_rows = sharded ? ctx->shard_rows_total : d.n_rows;
+    c.n_rows = sharded ? ctx->shard_rows_total : d.m->n_rows;
     c.net = ctx->net;
     EvalParams p = make_params(ctx, d);
     p.partials = ctx->d_partials;
@@ -475,10 +475,10 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
     p.chain = overlap ? ctx->d_cparams : nullptr;
     p.sync_mode = spec ? 3 : sync ? 1 : 0;
     // (the persistent overlapped launch: workgroups run up to a pass ahead of each other, so the heavier shares taking turns evens out)
-    p.share_rot = (persist && !spec && group_blocks == 0 && lp.grid > 1 && !getenv("NPBNN_NO_SHARE_ROTATION")) ? d.n_tiles % lp.grid : 0;
+    p.share_rot = (persist && !spec && group_blocks == 0 && lp.grid > 1 && !getenv("NPBNN_NO_SHARE_ROTATION")) ? d.m->n_tiles % lp.grid : 0;
     p.cand_slopes = c.slopes ? &ctx->d_slopes->cand[0][0][0] : nullptr;
     c.class_w = ctx->n_classw ? ctx->d_classw : nullptr;
-    c.w_scale = f16 ? ctx->d_wscale : nullptr;
+    c.w_scale = f16 ? ctx->store->wscale : nullptr;
     {   // both parameter blocks in one copy (they sit in one device allocation, laid out like the staging area)
         memcpy(ctx->h_params, &p, sizeof(EvalParams));
         memcpy(ctx->h_params + sizeof(EvalParams) + sizeof(FinalizeParams), &c, sizeof(ChainParams));
@@ -497,7 +497,7 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
         pk.class_w = ctx->n_classw ? ctx->d_classw : nullptr;
         pk.image = ctx->d_image;
         pk.net = reinterpret_cast<const NetMeta*>(reinterpret_cast<const char*>(ctx->d_cparams) + offsetof(ChainParams, net));
-        pk.w_scale = f16 ? ctx->d_wscale : nullptr;
+        pk.w_scale = f16 ? ctx->store->wscale : nullptr;
         hipLaunchKernelGGL(gather_pos_kernel, dim3((unsigned)(gather_blocks + pack_blocks)), dim3(256), 0, st, ctx->d_idx, (long long)need, ctx->n_weights,
                            (const int*)ctx->d_w2img, (const float*)(f16 ? ctx->d_w2scale : nullptr), ctx->d_pos,
                            f16 ? ctx->d_pscale : (float*)nullptr, ctx->d_chain_ovf, gather_blocks, pk);
@@ -787,7 +787,7 @@ int npbnn_chains_run_batched(npbnn_chain_job* jobs, int32_t n_jobs, int32_t K) {
         // replicas of one model over the same resident matrix: same device, same X, same network shape, same likelihood
         const npbnn_ctx* a = ctx0;
         const npbnn_ctx* b = J.ctx;
-        if (b->device != a->device || b->ds[0].X != a->ds[0].X || b->ds[0].n_rows != a->ds[0].n_rows || b->n_weights != a->n_weights ||
+        if (b->device != a->device || b->ds[0].m->X != a->ds[0].m->X || b->ds[0].m->n_rows != a->ds[0].m->n_rows || b->n_weights != a->n_weights ||
             memcmp(&b->arch, &a->arch, sizeof(npbnn_arch)) != 0 || b->l0_blocks != a->l0_blocks || (b->n_classw > 0) != (a->n_classw > 0) ||
             (b->ds[0].inst_w != nullptr) != (a->ds[0].inst_w != nullptr))
             return fail(J.ctx, NPBNN_E_ARG, "chains_run_batched: job %d is not a replica of job 0 (same device, shared feature matrix "

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <set>
 #include <string>
 #include <vector>
@@ -70,29 +71,52 @@ static inline eval_fn_t npbnn_pick_eval_kernel(int mt0, int mti, int f16, int n_
 
 namespace npbnn_api {
 
-struct Dataset {
-    float* X = nullptr;
-    DevBuf<int> labels;
-    DevBuf<float> targets;
-    DevBuf<float> inst_w;
+// One feature matrix as the device holds it: the float32 table and its fp16-split copies, built lazily on the device.
+struct FeatureTable {
+    DevBuf<float> X;
     int64_t n_rows = 0;
     int n_tiles = 0;
-    int F = 0, Fp = 0, k = 0;
-    float* X16 = nullptr;      // fp16-split copy (built lazily on the device), row stride Fp16 floats
+    int F = 0, Fp = 0;
+    DevBuf<float> X16;         // fp16-split copy, row stride Fp16 floats
     int Fp16 = 0;
     int f16_state = 0;         // 0 not built, 1 usable, -1 not representable (inf/NaN or outside the fp16 range), -2 representable but
                                // too coarse for some column: its entries span too many powers of two for a pair of fp16 numbers
     int f16_worst_col = -1;    // column with the largest (max entry error / mean |entry|) of the fp16 pair, and that ratio
     double f16_worst_ratio = 0.0;
-    bool borrowed = false;     // X / X16 belong to another ctx (npbnn_share_data)
-    float* X16w = nullptr;     // the fp16-split copy in the weight-streamed path's piece order (split_x_tiled_kernel), built when a
-    bool x16w_borrowed = false;   // network on that path first asks for it; a borrower of X uses (and, if need be, builds) its owner's
+    DevBuf<float> X16w;        // the fp16-split copy in the weight-streamed path's piece order (split_x_tiled_kernel), built when a
+                               // network on that path first asks for it
+};
+
+// The training and test matrices with the fp16-split path's scales: what npbnn_share_data shares.  Every context holds one through a
+// shared_ptr: the context that uploaded it and those that took it from another context alike, all on one device.  It goes, with that
+// device current, when its last holder lets go.
+struct FeatureStore {
+    explicit FeatureStore(int device_id) : device(device_id) {}
+    ~FeatureStore() { (void)hipSetDevice(device); }      // (the buffers are freed after this body)
+    FeatureTable table[2];
+    DevBuf<float> xscale;          // per-feature power-of-two scales of the fp16-split path (from the training matrix)
+    DevBuf<float> wscale;
+    int scale_F = 0;
+    int f16_shifted_cols = 0;      // columns whose scale was moved up (heavy tails: ensure_scales) and the largest such move (powers of two)
+    int f16_max_shift = 0;
+    const int device;
+};
+
+// A table as one context sees it: the matrices in the store it holds, and what it alone keeps for them.
+struct Dataset {
+    FeatureTable* m = nullptr;    // store->table[which] of the context (hold_store)
+    DevBuf<int> labels;
+    DevBuf<float> targets;
+    DevBuf<float> inst_w;
+    int k = 0;
     std::vector<int> perm_cols;   // npbnn_permute_columns: the columns of X (and of its split copies) that hold permuted values now ...
     DevBuf<float> perm_saved;     // ... and those columns as npbnn_set_data left them, [perm_cols.size()][n_rows]
 };
 
 }  // namespace npbnn_api
 using npbnn_api::Dataset;
+using npbnn_api::FeatureStore;
+using npbnn_api::FeatureTable;
 
 // The streams and events of a context.  A base of npbnn_ctx: they are destroyed after every buffer the context owns.
 struct npbnn_ctx_streams {
@@ -116,6 +140,10 @@ struct npbnn_ctx : npbnn_ctx_streams {
     int n_cu = 256;
     size_t lds_limit = 160 * 1024;
     std::string err;
+    // The feature matrices, possibly shared with other contexts (npbnn_share_data): never null.  store_taken: this context took the
+    // store from another one - it builds no row-major split copy in it and moves no column of it, whoever else still holds it.
+    std::shared_ptr<FeatureStore> store;
+    bool store_taken = false;
     Dataset ds[2];
     DevBuf<double> d_classw;
     int n_classw = 0;
@@ -137,11 +165,6 @@ struct npbnn_ctx : npbnn_ctx_streams {
     // layer-0 block structure (npbnn_set_layer_mask): which (16-node tile, 16-feature group) blocks of the mask hold a nonzero;
     // empty = dense
     std::vector<unsigned char> l0_blocks;      // [mt][ceil(in_dim / 16)]
-    float* d_xscale = nullptr;     // per-feature power-of-two scales of the fp16-split path (from the training matrix)
-    float* d_wscale = nullptr;
-    int f16_shifted_cols = 0;      // columns whose scale was moved up (heavy tails: ensure_scales) and the largest such move (powers of two)
-    int f16_max_shift = 0;
-    int scale_F = 0;
     DevBuf<int> d_overflow;
     // parameter blocks of the kernels: device copies (kernels take a pointer) + pinned host staging, both laid out
     // EvalParams | FinalizeParams | ChainParams
@@ -216,8 +239,6 @@ struct npbnn_ctx : npbnn_ctx_streams {
     // exchange run (npbnn_chains_run_exchange): [ExchangeParams | swap_j | swap_k | swap_logu || state | records | cold weights]
     DevBuf<char> d_xbuf;
     PinnedBuf<char> h_xbuf;
-    // feature matrices shared between the chains of one run (npbnn_share_data): a borrower points at its owner, an owner
-    // counts its borrowers and outlives them (a destroyed owner lingers until the last borrower lets go)
     bool sync_failed = false;      // a wait timed out once: the schedule stays off for this context
     int debug_sync_skip = -1;      // npbnn_debug_sync_skip_ (diagnostics, not part of the ABI)
     int fi_ns[6] = {0, 0, 0, 0, 0, 0};   // NPBNN_FI_TIMING: device time of the last npbnn_permute_columns, of the passes / accumulation / final
@@ -225,15 +246,12 @@ struct npbnn_ctx : npbnn_ctx_streams {
                                    // npbnn_predict_sets_lppd's final kernels (NPBNN_INFO_PERMUTE_NS ...; a support or lppd call also
                                    // leaves its passes and accumulation in [1], [2])
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
-    npbnn_ctx* data_owner = nullptr;
-    int n_borrowers = 0;
-    bool zombie = false;
     // weight-streamed path (npbnn_wide.hip): the network does not fit a compute unit's LDS (or NPBNN_OPT_WIDE asks for it)
     bool wide = false;
     int wide_option = 0;           // NPBNN_OPT_WIDE: 0 when the resident path cannot hold the network, 1 always
     WideMeta wmeta{};
     // Sizes: d_wide_cand and d_wide_cs by the network alone (wide_build); d_prep_terms by the widest proposal (chain_prepare);
-    // the fp16-split copy Dataset::X16w by its own table (built by wide_plan, freed with the table); d_wide_act by the largest table a plan
+    // the fp16-split copy FeatureTable::X16w by its own table (built by wide_plan, freed with the table); d_wide_act by the largest table a plan
     // was made for (wide_plan: rows x widest layer, and npbnn_wide_slice_room for the K-slices), which wide_forward checks every launch against.
     DevBuf<float> d_wide_cand;     // candidate image of a device chain (the committed image with the pending proposal patched in)
     DevBuf<float> d_wide_act[3];   // hidden activations [rows][16 * tiles], ping-pong between layers; [2]: the K-slices' sums

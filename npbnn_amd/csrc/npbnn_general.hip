@@ -361,7 +361,7 @@ extern "C" int npbnn_chain_run_general(npbnn_ctx* ctx, const npbnn_chain_cfg* cf
         g.w_bound = cfg->w_bound; g.temperature = cfg->temperature; g.lik_temp = cfg->lik_temp;
         for (int l = 0; l < kMaxLayers; ++l) g.prior_scale[l] = cfg->prior_scale[l];
         for (int j = 0; j < NPBNN_MAX_TARGETS; ++j) g.sigma_fixed[j] = cfg->sigma[j];
-        g.n_rows = d.n_rows;
+        g.n_rows = d.m->n_rows;
         for (int l = 0; l < kMaxLayers; ++l)      // (fixed activation slopes: cfg->cur_slopes, as in npbnn_chain_run)
             ctx->net.act_prm[l] = (!cfg->slope_idx && l < cfg->n_slopes && l < NPBNN_MAX_LAYERS) ? (float)cfg->cur_slopes[l] : 0.f;
         g.net = ctx->net;

@@ -217,14 +217,14 @@ extern "C" int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, cons
     if ((rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE))) return rc;
     const int C = ctx->net.n_out;
     const int n_act = ctx->net.n_layers - 1;
-    const size_t per_set = (size_t)d.n_rows * C;
+    const size_t per_set = (size_t)d.m->n_rows * C;
     const size_t wn = (size_t)ctx->n_weights;
     size_t budget = kHpdStackBytes;
     if (const char* e = getenv("NPBNN_HPD_STACK_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
     const size_t row_bytes = (size_t)n_sets * C * sizeof(float);
-    if ((size_t)d.n_rows * row_bytes > budget)
+    if ((size_t)d.m->n_rows * row_bytes > budget)
         return fail(ctx, NPBNN_E_NOMEM, "predict_sets_hpd: the [%d][%lld][%d] float32 stack takes %zu bytes, over the budget of %zu "
-                    "(NPBNN_HPD_STACK_BYTES); at most %zu rows fit", n_sets, (long long)d.n_rows, C, (size_t)d.n_rows * row_bytes,
+                    "(NPBNN_HPD_STACK_BYTES); at most %zu rows fit", n_sets, (long long)d.m->n_rows, C, (size_t)d.m->n_rows * row_bytes,
                     budget, budget / row_bytes);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf<float> stack;

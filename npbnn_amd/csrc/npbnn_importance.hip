@@ -230,30 +230,31 @@ extern "C" int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* c
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
     if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "permute_columns: which must be 0 or 1");
     Dataset& d = ctx->ds[which];
-    if (!d.X) return fail(ctx, NPBNN_E_STATE, "permute_columns: call npbnn_set_data first");
-    if (d.borrowed || ctx->data_owner) return fail(ctx, NPBNN_E_STATE, "permute_columns: this context's matrices belong to another one (npbnn_share_data)");
-    if (ctx->n_borrowers > 0) return fail(ctx, NPBNN_E_STATE, "permute_columns: %d other context(s) use this one's matrices (npbnn_share_data)", ctx->n_borrowers);
+    if (!d.m->X) return fail(ctx, NPBNN_E_STATE, "permute_columns: call npbnn_set_data first");
+    if (ctx->store_taken) return fail(ctx, NPBNN_E_STATE, "permute_columns: this context's matrices belong to another one (npbnn_share_data)");
+    if (ctx->store.use_count() > 1)
+        return fail(ctx, NPBNN_E_STATE, "permute_columns: %d other context(s) use this one's matrices (npbnn_share_data)", (int)ctx->store.use_count() - 1);
     if (n_cols < 0 || (n_cols > 0 && !cols)) return fail(ctx, NPBNN_E_ARG, "permute_columns: bad arguments");
     if (!perm) n_cols = 0;                   // (restore only)
     if (n_cols > 0 && n_perm != 1 && n_perm != n_cols)
         return fail(ctx, NPBNN_E_ARG, "permute_columns: %d permutations for %d columns (one for the block, or one per column)", n_perm, n_cols);
     std::vector<int> now(cols, cols + n_cols);
     {
-        std::vector<char> seen((size_t)d.F, 0);
+        std::vector<char> seen((size_t)d.m->F, 0);
         for (int c : now) {
-            if (c < 0 || c >= d.F) return fail(ctx, NPBNN_E_ARG, "permute_columns: column %d outside the matrix (%d features)", c, d.F);
+            if (c < 0 || c >= d.m->F) return fail(ctx, NPBNN_E_ARG, "permute_columns: column %d outside the matrix (%d features)", c, d.m->F);
             if (seen[(size_t)c]) return fail(ctx, NPBNN_E_ARG, "permute_columns: column %d named twice", c);
             seen[(size_t)c] = 1;
         }
     }
     if (now.empty() && d.perm_cols.empty()) return NPBNN_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long n_rows = d.n_rows;
+    const long long n_rows = d.m->n_rows;
     const size_t n_old = d.perm_cols.size(), n_new = now.size();
     // the 8-feature groups of the split copies that a restored or a moved column lies in
     std::vector<int> groups;
     {
-        std::vector<char> seen((size_t)(d.Fp / 8 + 4), 0);
+        std::vector<char> seen((size_t)(d.m->Fp / 8 + 4), 0);
         for (const std::vector<int>* v : {&d.perm_cols, &now})
             for (int c : *v)
                 if (!seen[(size_t)(c / 8)]) { seen[(size_t)(c / 8)] = 1; groups.push_back(c / 8); }
@@ -288,7 +289,7 @@ extern "C" int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* c
     }
     tm.mark(0, st);
     if (n_old) {
-        hipLaunchKernelGGL(perm_restore_kernel, dim3(grid_for(n_rows * (long long)n_old)), dim3(kFiThreads), 0, st, d.X, d.Fp, n_rows, d_old, (int)n_old,
+        hipLaunchKernelGGL(perm_restore_kernel, dim3(grid_for(n_rows * (long long)n_old)), dim3(kFiThreads), 0, st, d.m->X, d.m->Fp, n_rows, d_old, (int)n_old,
                            (const float*)d.perm_saved.get());
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -299,9 +300,9 @@ extern "C" int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* c
             if ((rc = fresh.reserve(ctx, (size_t)n_rows * n_new))) return rc;
         }
         float* saved = fresh ? fresh.get() : d.perm_saved.get();
-        hipLaunchKernelGGL(perm_save_kernel, dim3(grid_for(n_rows * (long long)n_new)), dim3(kFiThreads), 0, st, (const float*)d.X, d.Fp, n_rows, d_new, (int)n_new,
+        hipLaunchKernelGGL(perm_save_kernel, dim3(grid_for(n_rows * (long long)n_new)), dim3(kFiThreads), 0, st, (const float*)d.m->X, d.m->Fp, n_rows, d_new, (int)n_new,
                            saved);
-        hipLaunchKernelGGL(perm_gather_kernel, dim3(grid_for(n_rows * (long long)n_new)), dim3(kFiThreads), 0, st, d.X, d.Fp, n_rows, d_new, (int)n_new,
+        hipLaunchKernelGGL(perm_gather_kernel, dim3(grid_for(n_rows * (long long)n_new)), dim3(kFiThreads), 0, st, d.m->X, d.m->Fp, n_rows, d_new, (int)n_new,
                            (const float*)saved, (const long long*)d_perm.get(), n_perm == 1 ? 0 : 1);
         HIP_TRY(ctx, hipGetLastError());
         if (fresh) {
@@ -309,10 +310,10 @@ extern "C" int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* c
             d.perm_saved = std::move(fresh);
         }
     }
-    float* x16 = (d.f16_state > 0) ? d.X16 : nullptr;
-    if ((x16 || d.X16w) && ctx->d_xscale) {
-        hipLaunchKernelGGL(perm_patch_split_kernel, dim3(grid_for(n_rows * (long long)groups.size())), dim3(kFiThreads), 0, st, (const float*)d.X, n_rows, d.Fp,
-                           d_groups, (int)groups.size(), (const float*)ctx->d_xscale, x16, d.Fp16, d.X16w, (d.F + 31) / 32);
+    float* x16 = (d.m->f16_state > 0) ? d.m->X16 : nullptr;
+    if ((x16 || d.m->X16w) && ctx->store->xscale) {
+        hipLaunchKernelGGL(perm_patch_split_kernel, dim3(grid_for(n_rows * (long long)groups.size())), dim3(kFiThreads), 0, st, (const float*)d.m->X, n_rows, d.m->Fp,
+                           d_groups, (int)groups.size(), (const float*)ctx->store->xscale, x16, d.m->Fp16, d.m->X16w, (d.m->F + 31) / 32);
         HIP_TRY(ctx, hipGetLastError());
     }
     tm.mark(1, st);
@@ -328,7 +329,7 @@ int npbnn_api::replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const dou
     Dataset& d = ctx->ds[which];
     const int C = ctx->net.n_out;
     const int n_act = ctx->net.n_layers - 1;
-    const long long n_rows = d.n_rows;
+    const long long n_rows = d.m->n_rows;
     const size_t per_set = (size_t)n_rows * C;
     const size_t wn = (size_t)ctx->n_weights;
     hipStream_t st = ctx->stream;
@@ -427,7 +428,7 @@ extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, 
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int C = ctx->net.n_out;
-    const long long n_rows = d.n_rows;
+    const long long n_rows = d.m->n_rows;
     const size_t per_set = (size_t)n_rows * C;
     hipStream_t st = ctx->stream;
     // accumulators (per_set doubles, or as many unsigned), the summary, the confusion table, the labels, the flag word

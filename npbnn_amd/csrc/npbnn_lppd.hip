@@ -247,7 +247,7 @@ extern "C" int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, con
                             sigma_sets[i]);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long n_rows = d.n_rows;
+    const long long n_rows = d.m->n_rows;
     hipStream_t st = ctx->stream;
     const int n_wg = (int)grid_for(n_rows);
     const int n_out_arr = (out_lppd_i ? 1 : 0) + (out_mean_ll_i ? 1 : 0) + (out_pwaic_i ? 1 : 0);

@@ -299,7 +299,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
         if (focal[k] < 0 || focal[k] >= F) return fail(ctx, NPBNN_E_ARG, "predict_pdp: focal column %d outside 0..%d", focal[k], F - 1);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int L = ctx->net.n_layers, C = ctx->net.n_out, n_act = L - 1;
-    const long long n_rows = d.n_rows;
+    const long long n_rows = d.m->n_rows;
     const size_t wn = (size_t)ctx->n_weights;
     const size_t per_set = (size_t)n_rows * C;
 
@@ -337,7 +337,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
     // ---- route 1: the grid-batched kernel
     const int H0 = ctx->arch.out_dim[0];
     const int H0P = H0 <= 32 ? 32 : 64;
-    const int Fp = d.Fp;
+    const int Fp = d.m->Fp;
     bool batched = !ctx->wide && !env_on("NPBNN_PDP_PER_GRID") && H0 <= kPdpMaxH0 && (size_t)Fp * H0P * 4 <= kPdpW0Lds;
     PdpPrep q{};
     q.F = F; q.Fp = Fp; q.H0 = H0; q.H0P = H0P; q.hb0 = ctx->arch.has_bias[0]; q.n_layers = L; q.n_grid = n_grid; q.wn = (int)wn;
@@ -375,7 +375,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
                            d_w0t.get(), d_bias.get(), d_tail.get());
         HIP_TRY(ctx, hipGetLastError());
         PdpParams p{};
-        p.X = d.X; p.n_rows = n_rows; p.Fp = Fp;
+        p.X = d.m->X; p.n_rows = n_rows; p.Fp = Fp;
         p.w0t = d_w0t.get(); p.bias = d_bias.get(); p.tail = d_tail.get(); p.slopes = d_slopes.get();
         p.n_grid = n_grid; p.tail_floats = q.tail_floats;
         p.n_layers = L; p.act_kind = ctx->arch.act_kind; p.final_act = ctx->arch.final_act; p.out_kind = ctx->arch.out_kind;

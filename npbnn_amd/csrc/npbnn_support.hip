@@ -157,7 +157,7 @@ extern "C" int npbnn_predict_sets_support(npbnn_ctx* ctx, const double* W_sets, 
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int C = ctx->net.n_out;
-    const long long n_rows = d.n_rows;
+    const long long n_rows = d.m->n_rows;
     const size_t per_set = (size_t)n_rows * C;
     const long long cells_ll = (long long)(n_thresholds + 1) * C * C;
     if (cells_ll > (1ll << 28)) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: %d thresholds x %d x %d classes is too large a table", n_thresholds, C, C);

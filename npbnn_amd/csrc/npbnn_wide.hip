@@ -50,7 +50,7 @@ int raise_lds(npbnn_ctx* ctx, const void* fn, int bytes) {
 
 // floats of the K-slices' sums a pass over `d` needs (npbnn_wide_plan.h)
 long long slice_room(const npbnn_ctx* ctx, const Dataset& d) {
-    return npbnn_wide_slice_room(ctx->arch.n_layers, ctx->arch.out_dim, ctx->arch.in_dim, d.n_rows, ctx->n_cu);
+    return npbnn_wide_slice_room(ctx->arch.n_layers, ctx->arch.out_dim, ctx->arch.in_dim, d.m->n_rows, ctx->n_cu);
 }
 
 // the narrow layers from layer `l` on as wide_tail_layers takes them, or false when they are not narrow (or too large for `lds_budget` bytes)
@@ -87,9 +87,9 @@ bool fused_pass(const npbnn_ctx* ctx, const Dataset& d, int* n_row_blocks, size_
     static const bool off = getenv("NPBNN_WIDE_NO_FUSE") != nullptr || getenv("NPBNN_WIDE_NO_TAIL") != nullptr;
     if (off) return false;
     const WideMeta& m = ctx->wmeta;
-    const GemmCfg& cf = cfg_for(m.L[0].mt, d.n_tiles, ctx->n_cu);
+    const GemmCfg& cf = cfg_for(m.L[0].mt, d.m->n_tiles, ctx->n_cu);
     if (cf.wc != 1 || m.L[0].mt > cf.wt || m.L[0].mt > kTailIn) return false;
-    if (slices_for(cf, d.n_tiles, m.L[0].mt, m.L[0].units, ctx->n_cu) != 1) return false;
+    if (slices_for(cf, d.m->n_tiles, m.L[0].mt, m.L[0].units, ctx->n_cu) != 1) return false;
     if (m.n_out > 128) return false;
     const int lik = ctx->net.lik_kind;          // (the float64 row-wise likelihoods and wide Gaussian targets stay with wide_lik_kernel)
     if (lik_needs_row_scratch(lik) || (lik == NPBNN_LIK_GAUSS && ctx->net.k_targets > kFuseTargets)) return false;
@@ -100,7 +100,7 @@ bool fused_pass(const npbnn_ctx* ctx, const Dataset& d, int* n_row_blocks, size_
     const size_t need = ((size_t)kWideMaxCand * ((tail_floats + 3) & ~3) + (size_t)(cf.threads / 64) * 16 * ldz) * 4      // (room for two candidates' tails,
                         + 16 + (size_t)(cf.threads / 64) * kPartialStride * 8;                                              //  the rows' scratch, the waves' sums)
     if (need > 150 * 1024) return false;
-    *n_row_blocks = (d.n_tiles + cf.xt - 1) / cf.xt;
+    *n_row_blocks = (d.m->n_tiles + cf.xt - 1) / cf.xt;
     *lds_need = need;
     return true;
 }
@@ -181,7 +181,7 @@ bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
     for (int l = 1; l < a->n_layers; ++l) fusable = fusable && a->out_dim[l] <= 128;
     // (the row count of the training matrix: npbnn_set_data rebuilds the net on a new one, so the path does not depend on whether
     // the architecture or the data came first)
-    if (!getenv("NPBNN_WIDE_MIN_WAVES") && fusable && a->out_dim[0] <= 32 && ctx->ds[0].X != nullptr && ctx->ds[0].n_rows >= 65536 && w < 8) w = 8;
+    if (!getenv("NPBNN_WIDE_MIN_WAVES") && fusable && a->out_dim[0] <= 32 && ctx->ds[0].m->X != nullptr && ctx->ds[0].m->n_rows >= 65536 && w < 8) w = 8;
     return resident_lds_bytes(ctx, a, f16, w) > ctx->lds_limit;
 }
 
@@ -244,7 +244,7 @@ int wide_build(npbnn_ctx* ctx, bool f16) {
     if (f16) {
         scale.assign((size_t)ctx->n_weights, 1.0f);
         wscale.resize((size_t)round_up(a.in_dim, 32));
-        HIP_TRY(ctx, hipMemcpy(wscale.data(), ctx->d_wscale, wscale.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(wscale.data(), ctx->store->wscale, wscale.size() * sizeof(float), hipMemcpyDeviceToHost));
     }
     for (int l = 0; l < m.n_layers; ++l) {
         const WideLayer& L = m.L[l];
@@ -285,27 +285,18 @@ int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand) {
     // Both buffers grow to the demand of the table at hand and never shrink: a smaller table is cut into MORE K-slices (fewer row
     // blocks to fill the chip with) and may take another tiling, so the slice buffer has a capacity of its own, not rows x slices of
     // whichever table came first.
-    const size_t need = (size_t)d.n_tiles * 16 * (size_t)max_ld;
+    const size_t need = (size_t)d.m->n_tiles * 16 * (size_t)max_ld;
     const size_t room = (size_t)slice_room(ctx, d);      // the K-slices' sums: the most any layer writes on this table
     for (int i = 0; i < 3; ++i)
         if (int rc = ctx->d_wide_act[i].reserve(ctx, i < 2 ? need : room)) return rc;
-    if (m.L[0].f16 && !d.X16w) {        // the fp16-split copy in piece order
-        Dataset* home = &d;
-        if (d.borrowed && ctx->data_owner) {
-            npbnn_ctx* root = ctx->data_owner;
-            while (root->data_owner) root = root->data_owner;
-            home = &root->ds[which];
-        }
-        if (!home->X16w) {
-            const int n_units = (d.F + 31) / 32;
-            const size_t n_pad = (size_t)d.n_tiles * 16;
-            HIP_TRY(ctx, hipMalloc(&home->X16w, n_pad * (size_t)n_units * 32 * sizeof(float)));
-            const long long items = (long long)n_pad * n_units * 4;
-            hipLaunchKernelGGL(split_x_tiled_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)d.X, (long long)n_pad, d.Fp,
-                               n_units, (const float*)ctx->d_xscale, home->X16w);
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        if (home != &d) { d.X16w = home->X16w; d.x16w_borrowed = true; }
+    if (m.L[0].f16 && !d.m->X16w) {        // the fp16-split copy in piece order
+        const int n_units = (d.m->F + 31) / 32;      // (built once for every context that holds the store)
+        const size_t n_pad = (size_t)d.m->n_tiles * 16;
+        if (int rc = d.m->X16w.reserve(ctx, n_pad * (size_t)n_units * 32)) return rc;
+        const long long items = (long long)n_pad * n_units * 4;
+        hipLaunchKernelGGL(split_x_tiled_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)d.m->X, (long long)n_pad, d.m->Fp,
+                           n_units, (const float*)ctx->store->xscale, d.m->X16w.get());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     lp->fn = nullptr;
     lp->fn_spec = nullptr;
@@ -314,7 +305,7 @@ int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand) {
     lp->lds = 0;
     lp->fast = false;
     lp->wide = true;
-    int grid = (int)((d.n_rows + 255) / 256);
+    int grid = (int)((d.m->n_rows + 255) / 256);
     if (grid < 1) grid = 1;
     int n_rb = 0;
     size_t fuse_lds = 0;
@@ -322,7 +313,7 @@ int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand) {
         grid = n_rb;        // (one partial record per row block of the first layer's product)
         // two candidates per pass where the fused product has a build for them: its intake of X, not its arithmetic, bounds it
         static const bool one = getenv("NPBNN_WIDE_ONE_CAND") != nullptr;
-        const GemmCfg& cf = cfg_for(m.L[0].mt, d.n_tiles, ctx->n_cu);
+        const GemmCfg& cf = cfg_for(m.L[0].mt, d.m->n_tiles, ctx->n_cu);
         if (want_cand >= 2 && !one && cf.f16_d2 != nullptr && !ctx->slopes_option) lp->n_cand = 2;
         static const int cap = getenv("NPBNN_WIDE_MAX_CAND") ? atoi(getenv("NPBNN_WIDE_MAX_CAND")) : kWideMaxCand;
         if (want_cand >= 3 && !one && cf.f16_d3 != nullptr && !ctx->slopes_option && cap >= 3) lp->n_cand = 3;
@@ -335,7 +326,7 @@ int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand) {
 void wide_pack(npbnn_ctx* ctx, const double* d_w, const double* d_col_override, float* image, int* flags) {
     const long long total = wide_item_count(ctx->wmeta);
     hipLaunchKernelGGL(wide_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_w, d_col_override,
-                       ctx->n_classw ? ctx->d_classw : nullptr, image, ctx->wmeta, ctx->wmeta.L[0].f16 ? ctx->d_wscale : nullptr, flags);
+                       ctx->n_classw ? ctx->d_classw : nullptr, image, ctx->wmeta, ctx->wmeta.L[0].f16 ? ctx->store->wscale : nullptr, flags);
 }
 
 int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass, bool only_layer0, int* info, int n_cand) {
@@ -343,9 +334,9 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
     const WideMeta& m = ctx->wmeta;
     hipStream_t st = ctx->stream;
     const bool f16 = m.L[0].f16 != 0;
-    const float* A = f16 ? d.X16w : d.X;
-    long long lda = f16 ? 32ll * m.L[0].units : d.Fp;
-    if (f16 && !d.X16w) return fail(ctx, NPBNN_E_STATE, "the weight-streamed path has no fp16-split copy of this matrix (internal error)");
+    const float* A = f16 ? d.m->X16w : d.m->X;
+    long long lda = f16 ? 32ll * m.L[0].units : d.m->Fp;
+    if (f16 && !d.m->X16w) return fail(ctx, NPBNN_E_STATE, "the weight-streamed path has no fp16-split copy of this matrix (internal error)");
     const PassDesc* pass = chain_pass ? reinterpret_cast<const PassDesc*>(reinterpret_cast<const char*>(ctx->d_eparams) + offsetof(EvalParams, pass_desc)) : nullptr;
     const bool dev_slopes = chain_pass && ctx->batch_slopes && ctx->d_slopes;
     static const bool no_tail = getenv("NPBNN_WIDE_NO_TAIL") != nullptr;
@@ -359,16 +350,16 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
             if (tail_desc(ctx, l, image, dev_slopes, 96 * 1024, &t.t, &tail_floats)) {
                 t.A = A;
                 t.lda = lda;
-                t.n_row_tiles = d.n_tiles;
+                t.n_row_tiles = d.m->n_tiles;
                 t.kt0 = (int)(lda / 16);
                 t.out = ctx->d_wide_act[l & 1];
                 t.ldo = 16 * m.L[m.n_layers - 1].mt;
                 t.pass = pass;
-                if ((size_t)d.n_tiles * 16 * t.ldo > ctx->d_wide_act[l & 1].size())
+                if ((size_t)d.m->n_tiles * 16 * t.ldo > ctx->d_wide_act[l & 1].size())
                     return fail(ctx, NPBNN_E_INTERNAL, "weight-streamed path: the tail on %lld rows needs %lld floats, the buffer holds %zu (internal error: planned for another table)",
-                                (long long)d.n_rows, (long long)d.n_tiles * 16 * t.ldo, ctx->d_wide_act[l & 1].size());
+                                (long long)d.m->n_rows, (long long)d.m->n_tiles * 16 * t.ldo, ctx->d_wide_act[l & 1].size());
                 if (int rc = raise_lds(ctx, reinterpret_cast<const void*>(wide_tail_kernel), 96 * 1024 + 1024)) return rc;
-                int grid = (d.n_tiles + 7) / 8;
+                int grid = (d.m->n_tiles + 7) / 8;
                 if (grid > 2 * ctx->n_cu) grid = 2 * ctx->n_cu;
                 hipLaunchKernelGGL(wide_tail_kernel, dim3(grid), dim3(512), (size_t)tail_floats * 4, st, t);
                 A = t.out;
@@ -376,11 +367,11 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
                 break;
             }
         }
-        const GemmCfg& cf = cfg_for(L.mt, d.n_tiles, ctx->n_cu);
+        const GemmCfg& cf = cfg_for(L.mt, d.m->n_tiles, ctx->n_cu);
         WideGemmArgs g{};
         g.A = A;
         g.lda = lda;
-        g.n_row_tiles = d.n_tiles;
+        g.n_row_tiles = d.m->n_tiles;
         g.n_units = L.units;
         g.a_half_last = lda < 32ll * L.units ? 1 : 0;
         g.mt_total = L.mt;
@@ -430,15 +421,15 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
         wide_gemm_fn_t fn = sets == 3 ? (use16 ? cf.f16_d3 : cf.f32_d3) : sets == 2 ? (use16 ? cf.f16_d2 : cf.f32_d2) : (use16 ? cf.f16 : cf.f32);
         if (fn == nullptr) return fail(ctx, NPBNN_E_STATE, "no build of the weight-streamed product for this launch (internal error)");
         if (int rc = raise_lds(ctx, reinterpret_cast<const void*>(fn), (int)ctx->lds_limit)) return rc;      // (the largest ring any launch asks for)
-        const int n_rb = (d.n_tiles + cf.xt - 1) / cf.xt, n_cb = (L.mt + cf.wt - 1) / cf.wt;
-        const int n_sl = slices_for(cf, d.n_tiles, L.mt, L.units, ctx->n_cu);
+        const int n_rb = (d.m->n_tiles + cf.xt - 1) / cf.xt, n_cb = (L.mt + cf.wt - 1) / cf.wt;
+        const int n_sl = slices_for(cf, d.m->n_tiles, L.mt, L.units, ctx->n_cu);
         float* const layer_out = ctx->d_wide_act[l & 1];
         g.k_slices = n_sl;
-        g.slice_stride = (long long)d.n_tiles * 16 * g.ldo;
+        g.slice_stride = (long long)d.m->n_tiles * 16 * g.ldo;
         // (what wide_plan sized for this table: a plan made for another table is an error here, not a write past the buffers)
         if ((size_t)g.slice_stride > ctx->d_wide_act[l & 1].size() || (n_sl > 1 && (size_t)g.slice_stride * n_sl > ctx->d_wide_act[2].size()))
             return fail(ctx, NPBNN_E_INTERNAL, "weight-streamed path: layer %d on %lld rows needs %lld floats x %d K-slices, the buffers hold %zu / %zu "
-                        "(internal error: planned for another table)", l, (long long)d.n_rows, g.slice_stride, n_sl, ctx->d_wide_act[l & 1].size(),
+                        "(internal error: planned for another table)", l, (long long)d.m->n_rows, g.slice_stride, n_sl, ctx->d_wide_act[l & 1].size(),
                         ctx->d_wide_act[2].size());
         if (n_sl > 1) g.out = ctx->d_wide_act[2];
         const int grid = (n_rb + 7) / 8 * 8 * n_cb * n_sl;
@@ -461,7 +452,7 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
     la.image = image;
     la.classw_off = m.classw_off;
     la.final_prm_dev = nullptr;
-    const int grid = (int)((d.n_rows + 255) / 256) < 1 ? 1 : (int)((d.n_rows + 255) / 256);
+    const int grid = (int)((d.m->n_rows + 255) / 256) < 1 ? 1 : (int)((d.m->n_rows + 255) / 256);
     hipLaunchKernelGGL(wide_lik_kernel, dim3(grid), dim3(256), 0, st, la);
     HIP_TRY(ctx, hipGetLastError());
     return NPBNN_OK;

@@ -1,17 +1,15 @@
 """CPU: the HIP library owns its memory through one buffer type.
 
 Every device or page-locked host allocation the library keeps is a Buffer (npbnn_amd/csrc/npbnn_buf.hip.h), freed by its destructor
-or reset().  The allocator's own calls may appear only in that header, in npbnn_pinned_alloc / npbnn_pinned_free (memory handed to
-the caller), and on lines that handle the matrices a context may share with others (npbnn_share_data): the feature matrix, its
-fp16-split copies and the per-feature scales.  A new raw owner fails here."""
+or reset().  The allocator's own calls may appear only in that header and in npbnn_pinned_alloc / npbnn_pinned_free (memory handed
+to the caller).  The matrices that contexts share (npbnn_share_data) are buffers too, in a store held through a shared_ptr: no
+context points into another, counts its users or outlives its own destruction for them.  A new raw owner fails here."""
 import os
 import re
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "npbnn_amd", "csrc")
 ALLOC = re.compile(r"\b(hipMalloc|hipHostMalloc|hipFree|hipHostFree)\b")
 BUFFER_HEADER = "npbnn_buf.hip.h"
-# the borrowable pointers: Dataset::X, X16, X16w and npbnn_ctx::d_xscale, d_wscale
-BORROWABLE = re.compile(r"\b(X|X16|X16w|d_xscale|d_wscale)\b")
 PINNED_ENTRIES = ("npbnn_pinned_alloc", "npbnn_pinned_free")
 
 
@@ -38,7 +36,7 @@ def test_allocator_calls_only_where_allowed():
             code = line.split("//")[0]
             if not ALLOC.search(code):
                 continue
-            if BORROWABLE.search(code) or function_of(lines, i) in PINNED_ENTRIES:
+            if function_of(lines, i) in PINNED_ENTRIES:
                 continue
             stray.append("%s:%d: %s" % (f, i + 1, line.strip()))
     assert not stray, "raw allocator calls outside the buffer type:\n" + "\n".join(stray)
@@ -56,3 +54,23 @@ def test_context_keeps_no_capacity_fields():
         m = re.search(r"^struct %s\b[^{]*\{(.*?)^\};" % name, open(os.path.join(CSRC, f)).read(), re.S | re.M)
         assert m, name
         assert not re.search(r"\b\w+_cap\b|\bcap_\w+\b|\bpartial_waves\b", m.group(1)), name
+
+
+def struct_body(name):
+    m = re.search(r"^struct %s\b[^{]*\{(.*?)^\};" % name, open(os.path.join(CSRC, "npbnn_ctx.hip.h")).read(), re.S | re.M)
+    assert m, name
+    return "\n".join(line.split("//")[0] for line in m.group(1).split("\n"))
+
+
+def test_shared_matrices_have_no_hand_kept_ownership():
+    """The matrices and scales that npbnn_share_data shares live in one store owned through a shared_ptr: the context and its tables
+    keep no owner pointer, user count, lingering state or borrowed flag, and no raw float pointer to a matrix or a scale."""
+    ctx, dataset = struct_body("npbnn_ctx"), struct_body("Dataset")
+    assert not re.search(r"\b(data_owner|n_borrowers|zombie)\b", ctx)
+    assert not re.search(r"\b(borrowed|x16w_borrowed)\b", dataset)
+    for body in (ctx, dataset):
+        assert not re.search(r"\bfloat\s*\*\s*(X|X16|X16w|d_xscale|d_wscale|xscale|wscale)\b", body)
+    assert re.search(r"\bstd::shared_ptr<\s*FeatureStore\s*>", ctx)
+    store = struct_body("FeatureStore") + struct_body("FeatureTable")
+    for member in ("X", "X16", "X16w", "xscale", "wscale"):
+        assert re.search(r"\bDevBuf<float>[^;]*\b%s\b" % member, store), member
