@@ -185,9 +185,10 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
         * npbnn_permute_columns (restore, gather and the patch of the split copies), and of the last npbnn_predict_sets_summary's
         * evaluation passes (weight packing included), accumulation launches and final kernel; npbnn_predict_sets_support leaves its
         * passes and accumulation in the same two slots and its own final kernel in NPBNN_INFO_SUPPORT_FINAL_NS; npbnn_predict_sets_lppd
-        * does the same with NPBNN_INFO_LPPD_FINAL_NS (and leaves 0 in its three slots when it refuses a call before any launch) */
+        * does the same with NPBNN_INFO_LPPD_FINAL_NS (and leaves 0 in its three slots when it refuses a call before any launch), and
+        * npbnn_predict_sets_uncertainty with NPBNN_INFO_UNCERTAINTY_FINAL_NS (likewise) */
        NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17,
-       NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19 };
+       NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19, NPBNN_INFO_UNCERTAINTY_FINAL_NS = 20 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -317,6 +318,37 @@ int npbnn_predict_sets_support(npbnn_ctx* ctx, const double* W_sets, const doubl
 int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which, int lik_kind,
                             const double* sigma_sets, double* out_lppd_i, double* out_mean_ll_i, double* out_pwaic_i,
                             double* out_ll_sample, double out_totals[3]);
+
+/* Posterior uncertainty decomposition of the n_sets stored samples on the resident matrix `which`: the uncertainty of a prediction
+ * split into the part the data cannot remove (aleatoric) and the part that comes from the posterior over the weights (epistemic).
+ * The reference has no such function; the predictions are what the loop over RunPredict gives per stored sample
+ * (np_bnn/BNN_lib.py:375-381, 715-748) under the output function of ctx's architecture (out_kind), S = n_sets, float64 throughout:
+ *   NPBNN_OUT_SOFTMAX (SoftMax, :166-171), p_s = softmax(z_s) of a row's pre-output values z_s, C = out_dim:
+ *     out_mean [n_rows][C]   mean_prob = (1/S) sum_s p_s
+ *     out_total [n_rows]     predictive entropy -sum_k m_k log m_k of mean_prob, in nats (a term with m_k = 0 is 0)
+ *     out_aleatoric [n_rows] expected entropy (1/S) sum_s H(p_s), H(p_s) = lse(z_s) - sum_k p_sk z_sk - never log(softmax): a
+ *                            probability that underflows contributes 0
+ *     out_epistemic [n_rows] mutual information max(0, predictive - expected entropy); exactly 0 for one set
+ *     out_totals[3]          the sums over the rows of the three per-row quantities, in that order
+ *   NPBNN_OUT_IDENTITY (RegressTransform, :174-175; T = out_dim, mu_s = z_s) and NPBNN_OUT_SOFTPLUS_HALF (RegressTransformError,
+ *   :177-182; out_dim = 2 T, mu_s = z_s[:T], sigma_s = logaddexp(0, z_s[T:])):
+ *     out_mean [n_rows][T]      mean_s mu_s
+ *     out_epistemic [n_rows][T] (1/S) sum_s (mu_s - mean)^2 (ddof 0: the law of total variance of the mixture), from sums shifted by
+ *                               the first set's mu; exactly 0 for one set
+ *     out_aleatoric [n_rows][T] (1/S) sum_s sigma_s^2, and out_total [n_rows][T] = epistemic + aleatoric: NPBNN_OUT_SOFTPLUS_HALF only.
+ *                               The identity output predicts no sigma - the caller adds the mean of its samples' squared error
+ *                               parameters, which does not depend on the row - and both pointers must be NULL under it.
+ *     out_totals[4][T]          the sums over the rows of mean, total, aleatoric, epistemic per target (total and aleatoric: 0 under
+ *                               NPBNN_OUT_IDENTITY)
+ * Every pointwise output may be NULL (it is then not copied from the device); out_totals is required.  No labels or targets are read.
+ * The sets replay as in npbnn_predict_sets_lppd, the pre-output values left on the device in float32 and widened before any exp or
+ * log; each group is folded into float64 per-row accumulators in set order, and every cross-row sum is made of per-workgroup float64
+ * partials added in a fixed order: two calls return the same bits, however the sets are grouped.  Before any launch: NPBNN_E_ARG for
+ * n_sets < 1, NULL W_sets or out_totals, `which` not 0 or 1, an odd out_dim under NPBNN_OUT_SOFTPLUS_HALF, out_total or out_aleatoric
+ * given under NPBNN_OUT_IDENTITY; NPBNN_E_STATE without npbnn_set_arch or without data on `which`.  NPBNN_E_ARG after the passes: a
+ * prediction that is NaN. */
+int npbnn_predict_sets_uncertainty(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
+                                   double* out_mean, double* out_total, double* out_aleatoric, double* out_epistemic, double* out_totals);
 
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events

@@ -34,6 +34,7 @@ INFO_PDP_ROUTE = 13
 INFO_PERMUTE_NS, INFO_SUMMARY_PASS_NS, INFO_SUMMARY_ACC_NS, INFO_SUMMARY_FINAL_NS = 14, 15, 16, 17
 INFO_SUPPORT_FINAL_NS = 18
 INFO_LPPD_FINAL_NS = 19
+INFO_UNCERTAINTY_FINAL_NS = 20
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
 E_STATE = -2
@@ -150,6 +151,7 @@ SIGNATURES = {
                                              _DP, C.c_int32, _DP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _DP,
                                              C.POINTER(C.c_uint8)]),
     "npbnn_predict_sets_lppd": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "npbnn_predict_sets_uncertainty": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, _DP, _DP, _DP, _DP, _DP]),
     "npbnn_time_eval": (C.c_int, [_P, _DP, C.c_int, _DP, _DP]),
     "npbnn_time_pass": (C.c_int, [_P, _DP, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
     "npbnn_time_wide": (C.c_int, [_P, _DP, C.c_int, _DP, _DP, C.POINTER(C.c_int)]),

@@ -440,6 +440,52 @@ class HipContext:
         return dict(lppd=float(totals[0]), mean_log_lik=float(totals[1]), p_waic=float(totals[2]), log_lik_sample=trace,
                     lppd_i=point[0], mean_log_lik_i=point[1], p_waic_i=point[2])
 
+    def predict_sets_uncertainty(self, weight_sets, act_prm_sets=None, which=capi.TRAIN, pointwise=True):
+        """Uncertainty decomposition of several weight sets' predictions on the resident matrix (npbnn_predict_sets_uncertainty); the
+        kind follows the architecture's output function, and no labels or targets are read.  Softmax: a dict with ``mean_prob``
+        [n_rows, n_out], ``predicted_class`` (its first argmax), ``predictive_entropy_i``, ``expected_entropy_i``,
+        ``mutual_information_i`` [n_rows] and their means over the rows ``predictive_entropy``, ``expected_entropy``,
+        ``mutual_information``.  Regression (T targets: n_out under OUT_IDENTITY, n_out / 2 under OUT_SOFTPLUS_HALF): ``mean``,
+        ``epistemic_var``, ``aleatoric_var``, ``total_var`` [n_rows, T] and their means over the rows ``mean_avg``, ... [T];
+        OUT_IDENTITY predicts no sigma, and its ``aleatoric_var*`` and ``total_var*`` are None (the caller adds its own).  Without
+        ``pointwise`` every [n_rows, ...] array is None and is not copied from the device.  The sets replay as in
+        ``predict_sets_lppd``; the predictions never leave the device."""
+        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
+            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
+        packed = capi.as_f64(packed)
+        n_sets, n_rows, n_out, kind = packed.shape[0], self.n_rows[which], self.n_out, self.arch.out_kind
+        if n_sets < 1:
+            raise ValueError("predict_sets_uncertainty: no weight sets")
+        if n_rows < 1:
+            raise ValueError("predict_sets_uncertainty: the matrix has no rows")
+        if kind == capi.OUT_SOFTPLUS_HALF and n_out % 2:
+            raise ValueError("predict_sets_uncertainty: OUT_SOFTPLUS_HALF splits the outputs into means and sigmas, and %d is odd" % n_out)
+        ap = None
+        if act_prm_sets is not None and self.arch.n_layers > 1:
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+            if ap.shape[0] != n_sets:
+                raise ValueError("predict_sets_uncertainty: %d slope vectors for %d weight sets" % (ap.shape[0], n_sets))
+        softmax, sigma = kind == capi.OUT_SOFTMAX, kind == capi.OUT_SOFTPLUS_HALF
+        t = 1 if softmax else (n_out // 2 if sigma else n_out)
+        col = (n_rows,) if softmax else (n_rows, t)
+        # mean, total, aleatoric, epistemic
+        point = [None] * 4
+        if pointwise:
+            point = [np.empty((n_rows, n_out if softmax else t), dtype=np.float64), np.empty(col, dtype=np.float64), np.empty(col, dtype=np.float64),
+                     np.empty(col, dtype=np.float64)]
+            if not (softmax or sigma):
+                point[1] = point[2] = None
+        totals = np.zeros(3 if softmax else (4, t), dtype=np.float64)
+        self._chk(self._lib.npbnn_predict_sets_uncertainty(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which, capi.dptr(point[0]),
+                                                           capi.dptr(point[1]), capi.dptr(point[2]), capi.dptr(point[3]), capi.dptr(totals)))
+        avg = totals / n_rows
+        if softmax:
+            return dict(mean_prob=point[0], predicted_class=None if point[0] is None else np.argmax(point[0], axis=1),
+                        predictive_entropy_i=point[1], expected_entropy_i=point[2], mutual_information_i=point[3],
+                        predictive_entropy=float(avg[0]), expected_entropy=float(avg[1]), mutual_information=float(avg[2]))
+        return dict(mean=point[0], total_var=point[1], aleatoric_var=point[2], epistemic_var=point[3], mean_avg=avg[0],
+                    total_var_avg=avg[1] if sigma else None, aleatoric_var_avg=avg[2] if sigma else None, epistemic_var_avg=avg[3])
+
     def predict_pdp(self, weight_sets, focal, grid, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
         prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]

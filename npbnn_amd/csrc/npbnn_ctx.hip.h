@@ -241,10 +241,10 @@ struct npbnn_ctx : npbnn_ctx_streams {
     PinnedBuf<char> h_xbuf;
     bool sync_failed = false;      // a wait timed out once: the schedule stays off for this context
     int debug_sync_skip = -1;      // npbnn_debug_sync_skip_ (diagnostics, not part of the ABI)
-    int fi_ns[6] = {0, 0, 0, 0, 0, 0};   // NPBNN_FI_TIMING: device time of the last npbnn_permute_columns, of the passes / accumulation / final
-                                   // kernel of the last npbnn_predict_sets_summary, and of the last npbnn_predict_sets_support's and
-                                   // npbnn_predict_sets_lppd's final kernels (NPBNN_INFO_PERMUTE_NS ...; a support or lppd call also
-                                   // leaves its passes and accumulation in [1], [2])
+    int fi_ns[7] = {0, 0, 0, 0, 0, 0, 0};   // NPBNN_FI_TIMING: device time of the last npbnn_permute_columns, of the passes / accumulation / final
+                                   // kernel of the last npbnn_predict_sets_summary, and of the last npbnn_predict_sets_support's,
+                                   // npbnn_predict_sets_lppd's and npbnn_predict_sets_uncertainty's final kernels (NPBNN_INFO_PERMUTE_NS ...;
+                                   // a support, lppd or uncertainty call also leaves its passes and accumulation in [1], [2])
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     // weight-streamed path (npbnn_wide.hip): the network does not fit a compute unit's LDS (or NPBNN_OPT_WIDE asks for it)
     bool wide = false;

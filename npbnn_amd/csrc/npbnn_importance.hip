@@ -324,8 +324,9 @@ extern "C" int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* c
 }
 
 int npbnn_api::replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which,
-                                      int apply_out_fn, int mode, double* d_acc, int* d_flag, const ReplayLppd* lppd) {
+                                      int apply_out_fn, int mode, double* d_acc, int* d_flag, const ReplayLppd* lppd, const ReplayUncertainty* unc) {
     if (mode == kReplayLppd && (!lppd || apply_out_fn)) return fail(ctx, NPBNN_E_INTERNAL, "%s: the log-likelihood replay takes pre-output values", who);
+    if (mode == kReplayUncertainty && (!unc || apply_out_fn)) return fail(ctx, NPBNN_E_INTERNAL, "%s: the uncertainty replay takes pre-output values", who);
     Dataset& d = ctx->ds[which];
     const int C = ctx->net.n_out;
     const int n_act = ctx->net.n_layers - 1;
@@ -388,6 +389,8 @@ int npbnn_api::replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const dou
         tm.mark(2, st);
         if (mode == kReplayLppd) {
             launch_lppd_accumulate(st, ctx->d_y.get(), g, s0, n_rows, C, d_acc, *lppd, d_flag);
+        } else if (mode == kReplayUncertainty) {
+            launch_uncertainty_accumulate(st, ctx->d_y.get(), g, s0, n_rows, C, d_acc, *unc, d_flag);
         } else if (mode == kReplayVotes) {
             unsigned* votes = reinterpret_cast<unsigned*>(d_acc);
             if (C % 4 == 0)

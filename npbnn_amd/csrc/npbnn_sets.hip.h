@@ -52,7 +52,7 @@ struct FiTimer {
 };
 
 // What replay_sets_accumulate folds a group's float32 values into
-enum { kReplayVotes = 0, kReplaySums = 1, kReplayLppd = 2 };
+enum { kReplayVotes = 0, kReplaySums = 1, kReplayLppd = 2, kReplayUncertainty = 3 };
 
 constexpr int kLppdAcc = 5;                        // float64 accumulators per row of kReplayLppd, each an array [n_rows]
 
@@ -68,17 +68,30 @@ struct ReplayLppd {
     int n_wg = 0;                     // workgroups of the accumulate launch: grid_for(n_rows)
 };
 
+// What kReplayUncertainty (npbnn_uncertainty.hip) needs beside the accumulator d_acc, which is [C + 1][n_rows] for the softmax output (sum of
+// the sets' probabilities per class, then the sum of their entropies) and [3 or 4][T][n_rows] for regression (K = the first set's mean,
+// sum (mu - K), sum (mu - K)^2, and under NPBNN_OUT_SOFTPLUS_HALF sum sigma^2).
+struct ReplayUncertainty {
+    int out_kind = 0;                 // NPBNN_OUT_SOFTMAX, NPBNN_OUT_IDENTITY or NPBNN_OUT_SOFTPLUS_HALF
+    int n_wg = 0;                     // workgroups of the accumulate launch: grid_for(n_rows)
+};
+
 // The n_sets weight sets against the resident matrix `which`, group after group as npbnn_predict_sets replays them (sets that share
 // their slopes travel together, the float32 retry), each group's float32 predictions folded into d_acc before the next group
 // overwrites them: kReplayVotes uint32 votes [n_rows][C] (d_acc read as unsigned), kReplaySums float64 sums [n_rows][C], in set order;
-// kReplayLppd (with `lppd`, and apply_out_fn 0: the values are the pre-output ones) the per-row log-likelihood accumulators above.  d_acc
-// (n_rows x C doubles, or kLppdAcc x n_rows) and the flag word d_flag are the caller's, zeroed by it in stream order before the call;
+// kReplayLppd (with `lppd`, and apply_out_fn 0: the values are the pre-output ones) the per-row log-likelihood accumulators above;
+// kReplayUncertainty (with `unc`, apply_out_fn 0 likewise) the accumulators of the uncertainty decomposition above.  d_acc
+// (n_rows x C doubles, kLppdAcc x n_rows, or as ReplayUncertainty says) and the flag word d_flag are the caller's, zeroed by it in stream order before the call;
 // kFlagNaN (and kFlagBadLabel, kReplayLppd) is raised there.  `who` names the entry in error messages.  Leaves the pass and accumulation
 // times in ctx->fi_ns[1], [2] (NPBNN_FI_TIMING).  Defined in npbnn_importance.hip.
 int replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which, int apply_out_fn,
-                           int mode, double* d_acc, int* d_flag, const ReplayLppd* lppd = nullptr);
+                           int mode, double* d_acc, int* d_flag, const ReplayLppd* lppd = nullptr, const ReplayUncertainty* unc = nullptr);
 
 // lppd_accumulate_kernel over a group's values y [g][n_rows][C], the sets s0 .. s0 + g - 1.  Defined in npbnn_lppd.hip.
 void launch_lppd_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int C, double* d_acc, const ReplayLppd& a, int* d_flag);
+
+// The accumulate kernel of a.out_kind over a group's values y [g][n_rows][n_out], the sets s0 .. s0 + g - 1.  Defined in npbnn_uncertainty.hip.
+void launch_uncertainty_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int n_out, double* d_acc, const ReplayUncertainty& a,
+                                   int* d_flag);
 
 }  // namespace npbnn_api

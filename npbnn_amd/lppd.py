@@ -79,13 +79,13 @@ def _targets(labels, n_rows, n_out):
     return t
 
 
-def _sample_sigmas(samples, n_out):
+def _sample_sigmas(samples, n_out, who="get_posterior_lppd"):
     if any('error_prm' not in s or len(np.atleast_1d(s['error_prm'])) == 0 for s in samples):
-        raise ValueError("get_posterior_lppd: the checkpoint's samples carry no error_prm (the per-sample sigma of the Gaussian "
-                         "likelihood): the run had no error parameters to store")
+        raise ValueError("%s: the checkpoint's samples carry no error_prm (the per-sample sigma of the Gaussian "
+                         "likelihood): the run had no error parameters to store" % who)
     sig = np.array([np.ones(n_out) * np.asarray(s['error_prm'], dtype=np.float64) for s in samples])
     if not (np.all(np.isfinite(sig)) and np.all(sig > 0)):
-        raise ValueError("get_posterior_lppd: a sample's error_prm is not positive and finite")
+        raise ValueError("%s: a sample's error_prm is not positive and finite" % who)
     return sig
 
 

@@ -135,6 +135,34 @@ class _SamplePredictor:
             ctx.set_targets(labels)
         return ctx.predict_sets_lppd(self._packed, lik_kind, sigma_sets=sigma_sets, act_prm_sets=self._slopes, pointwise=pointwise)
 
+    def uncertainty(self, features, kind, sigma_sets=None, pointwise=True):
+        """``posterior_uncertainty``'s dict (without the counts) for the stored samples on ``features``, ``kind``
+        ``"classification"``, ``"regression"`` (``sigma_sets`` per sample: the device returns mean and epistemic variance, and the
+        mean of the squared sigmas, which does not depend on the row, is added here) or ``"regression-error"``; the stack stays on
+        the device (npbnn_predict_sets_uncertainty), and without ``pointwise`` the [N, ...] arrays are None.  A custom output
+        callable has no device kind: its stack is built on the host and goes through ``posterior_uncertainty``."""
+        from .uncertainty import KINDS, _sigma_sets, posterior_uncertainty
+        if kind not in KINDS:
+            raise ValueError("uncertainty: kind %r; one of %s" % (kind, ", ".join(KINDS)))
+        if self._kind is None and self._out_fn is not None:
+            return posterior_uncertainty(self.predict(features), kind, sigma_sets)
+        want = {"classification": capi.OUT_SOFTMAX, "regression": capi.OUT_IDENTITY, "regression-error": capi.OUT_SOFTPLUS_HALF}[kind]
+        if (capi.OUT_IDENTITY if self._kind is None else self._kind) != want:
+            raise ValueError("uncertainty: kind %r does not go with the model's output function" % (kind,))
+        sig = None
+        if kind == "regression":
+            sig = _sigma_sets(sigma_sets, len(self._packed), self._weights[0][-1].shape[0], "uncertainty")
+        ctx = self._load(features)
+        res = ctx.predict_sets_uncertainty(self._packed, act_prm_sets=self._slopes, pointwise=pointwise)
+        if kind == "regression":
+            aleatoric = np.sum(sig * sig, axis=0) / len(sig)
+            res["aleatoric_var_avg"] = aleatoric
+            res["total_var_avg"] = res["epistemic_var_avg"] + aleatoric
+            if pointwise:
+                res["aleatoric_var"] = np.broadcast_to(aleatoric, res["epistemic_var"].shape).copy()
+                res["total_var"] = res["epistemic_var"] + aleatoric
+        return res
+
     def close(self):
         self._ctx.close()
 
