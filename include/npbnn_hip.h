@@ -186,7 +186,9 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
         * evaluation passes (weight packing included), accumulation launches and final kernel; npbnn_predict_sets_support leaves its
         * passes and accumulation in the same two slots and its own final kernel in NPBNN_INFO_SUPPORT_FINAL_NS; npbnn_predict_sets_lppd
         * does the same with NPBNN_INFO_LPPD_FINAL_NS (and leaves 0 in its three slots when it refuses a call before any launch), and
-        * npbnn_predict_sets_uncertainty with NPBNN_INFO_UNCERTAINTY_FINAL_NS (likewise) */
+        * npbnn_predict_sets_uncertainty with NPBNN_INFO_UNCERTAINTY_FINAL_NS (likewise).  npbnn_predict_sets and npbnn_predict_sets_hpd
+        * run the same replay, so after them NPBNN_INFO_SUMMARY_PASS_NS / _ACC_NS describe that call: its passes, and the copies to the
+        * host (npbnn_predict_sets) or nothing (npbnn_predict_sets_hpd, whose groups write straight into its stack) */
        NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17,
        NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19, NPBNN_INFO_UNCERTAINTY_FINAL_NS = 20 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);

@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <memory>
 #define NPBNN_KERNELS_MAIN
-#include "npbnn_ctx.hip.h"
+#include "npbnn_sets.hip.h"
 
 namespace npbnn_api {
 
@@ -1183,61 +1183,16 @@ int npbnn_predict_sets(npbnn_ctx* ctx, const double* W_sets, const double* act_p
     int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int C = ctx->net.n_out;
-    const int n_act = ctx->net.n_layers - 1;
-    const size_t per_set = (size_t)d.m->n_rows * C;
-    const size_t wn = (size_t)ctx->n_weights;
-    if ((rc = ctx->d_y.reserve(ctx, kMaxCand * per_set))) return rc;
+    const size_t per_set = (size_t)d.m->n_rows * ctx->net.n_out;
     std::vector<float> tmp(kMaxCand * per_set);
-    std::vector<double> wstage(kMaxCand * wn);
-    int s0 = 0;
-    while (s0 < n_sets) {
-        // sets that share their activation slopes travel together, up to kMaxCand per streaming read of X
-        int g = 1;
-        while (s0 + g < n_sets && g < kMaxCand &&
-               (!act_prm_sets || n_act == 0 ||
-                memcmp(act_prm_sets + (size_t)(s0 + g) * n_act, act_prm_sets + (size_t)s0 * n_act, (size_t)n_act * sizeof(double)) == 0))
-            ++g;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            LaunchPlan lp;
-            rc = plan_launch(ctx, which, &lp, attempt, g, true);
-            if (rc) return rc;
-            if (lp.n_cand < g) g = lp.n_cand;          // (fewer images fit the LDS: the rest waits for the next round)
-            memcpy(wstage.data(), W_sets + (size_t)s0 * wn, (size_t)g * wn * sizeof(double));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_wraw, wstage.data(), (size_t)g * wn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            for (int l = 0; l < kMaxLayers; ++l) ctx->net.act_prm[l] = 0.f;
-            if (act_prm_sets)
-                for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), ctx->stream));
-            for (int j = 0; j < g; ++j)         // (the weight-streamed path carries one set per pass: g = 1)
-                launch_pack_weights(ctx, ctx->d_wraw + (size_t)j * wn, nullptr, ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
-            HIP_TRY(ctx, hipGetLastError());
-            EvalParams p = make_params(ctx, d);
-            p.labels = nullptr;
-            p.targets = nullptr;
-            p.net.lik_kind = NPBNN_LIK_NONE;
-            p.y_out = ctx->d_y;
-            p.predict_mode = apply_out_fn ? 2 : 1;
-            p.weight_sets = 1;
-            p.lay = layout_for(ctx, d, true);
-            rc = push_eval_params(ctx, p);
-            if (rc) return rc;
-            rc = launch_plain_eval(ctx, lp, which);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), ctx->d_y, (size_t)g * per_set * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-            int ovf = 0;
-            HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "predict_sets: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is");
-            if (!(ctx->net.l0_f16 && (ovf & kFlagF16Range))) break;
-            if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "predict_sets: a layer-0 weight left the fp16 range");
-        }
-        double* dst = out_y + (size_t)s0 * per_set;
-        for (size_t i = 0; i < (size_t)g * per_set; ++i) dst[i] = (double)tmp[i];
-        s0 += g;
-    }
-    return NPBNN_OK;
+    return replay_sets(ctx, "predict_sets", W_sets, act_prm_sets, n_sets, which, apply_out_fn, nullptr, [&](const SetGroup& grp) {
+        const size_t n = (size_t)grp.g * per_set;
+        HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), grp.y, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        double* dst = out_y + (size_t)grp.s0 * per_set;
+        for (size_t i = 0; i < n; ++i) dst[i] = (double)tmp[i];
+        return (int)NPBNN_OK;
+    });
 }
 
 }  // extern "C"

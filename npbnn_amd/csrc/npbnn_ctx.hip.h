@@ -244,7 +244,7 @@ struct npbnn_ctx : npbnn_ctx_streams {
     int fi_ns[7] = {0, 0, 0, 0, 0, 0, 0};   // NPBNN_FI_TIMING: device time of the last npbnn_permute_columns, of the passes / accumulation / final
                                    // kernel of the last npbnn_predict_sets_summary, and of the last npbnn_predict_sets_support's,
                                    // npbnn_predict_sets_lppd's and npbnn_predict_sets_uncertainty's final kernels (NPBNN_INFO_PERMUTE_NS ...;
-                                   // a support, lppd or uncertainty call also leaves its passes and accumulation in [1], [2])
+                                   // every entry that goes through replay_sets, npbnn_sets.hip.h, leaves its passes and sinks in [1], [2])
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     // weight-streamed path (npbnn_wide.hip): the network does not fit a compute unit's LDS (or NPBNN_OPT_WIDE asks for it)
     bool wide = false;

@@ -9,11 +9,9 @@
 // stack of npbnn_predict_sets_hpd - and a shuffle reduction picks the smallest width, the smallest k among equal ones.  The mean
 // (float64 sum in a fixed order) comes from the same LDS copy.  No atomics but the non-finite flag, no scratch.
 //
-// npbnn_predict_sets_hpd replays the stored sets as npbnn_predict_sets does (np_bnn/BNN_lib.py:375-381, 715-748: groups of sets
-// that share their slopes, up to kMaxCand per read of X on the resident path, one on the weight-streamed path, the float32 retry
-// after the fp16 range flag), each group writing its float32 predictions straight into a device stack [S][rows][C]; one launch of
-// hpd_kernel then reads the stack once.
-#include "npbnn_ctx.hip.h"
+// npbnn_predict_sets_hpd replays the stored sets through replay_sets (npbnn_sets.hip.h), each group writing its float32 predictions
+// straight into a device stack [S][rows][C]; one launch of hpd_kernel then reads the stack once.
+#include "npbnn_sets.hip.h"
 
 #include <climits>
 #include <cmath>
@@ -216,9 +214,7 @@ extern "C" int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, cons
     Dataset& d = ctx->ds[which];
     if ((rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE))) return rc;
     const int C = ctx->net.n_out;
-    const int n_act = ctx->net.n_layers - 1;
     const size_t per_set = (size_t)d.m->n_rows * C;
-    const size_t wn = (size_t)ctx->n_weights;
     size_t budget = kHpdStackBytes;
     if (const char* e = getenv("NPBNN_HPD_STACK_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
     const size_t row_bytes = (size_t)n_sets * C * sizeof(float);
@@ -231,52 +227,7 @@ extern "C" int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, cons
     DevBuf<double> d_res;
     if ((rc = dev_alloc(ctx, stack, (size_t)n_sets * per_set))) return rc;
     if ((rc = dev_alloc(ctx, d_res, 3 * per_set))) return rc;
-    std::vector<double> wstage(kMaxCand * wn);
-    int s0 = 0;
-    while (s0 < n_sets) {
-        // sets that share their activation slopes travel together, up to kMaxCand per streaming read of X (npbnn_predict_sets)
-        int g = 1;
-        while (s0 + g < n_sets && g < kMaxCand &&
-               (!act_prm_sets || n_act == 0 ||
-                memcmp(act_prm_sets + (size_t)(s0 + g) * n_act, act_prm_sets + (size_t)s0 * n_act, (size_t)n_act * sizeof(double)) == 0))
-            ++g;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            LaunchPlan lp;
-            rc = plan_launch(ctx, which, &lp, attempt, g, true);
-            if (rc) return rc;
-            if (lp.n_cand < g) g = lp.n_cand;
-            memcpy(wstage.data(), W_sets + (size_t)s0 * wn, (size_t)g * wn * sizeof(double));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_wraw, wstage.data(), (size_t)g * wn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            for (int l = 0; l < kMaxLayers; ++l) ctx->net.act_prm[l] = 0.f;
-            if (act_prm_sets)
-                for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), ctx->stream));
-            for (int j = 0; j < g; ++j)
-                launch_pack_weights(ctx, ctx->d_wraw + (size_t)j * wn, nullptr, ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
-            HIP_TRY(ctx, hipGetLastError());
-            EvalParams p = make_params(ctx, d);
-            p.labels = nullptr;
-            p.targets = nullptr;
-            p.net.lik_kind = NPBNN_LIK_NONE;
-            p.y_out = stack.get() + (size_t)s0 * per_set;          // sets s0 .. s0 + g - 1 of the stack
-            p.predict_mode = apply_out_fn ? 2 : 1;
-            p.weight_sets = 1;
-            p.lay = layout_for(ctx, d, true);
-            rc = push_eval_params(ctx, p);
-            if (rc) return rc;
-            rc = launch_plain_eval(ctx, lp, which);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipGetLastError());
-            int ovf = 0;
-            HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            // (push_eval_params stages through one pinned slot: the launch that reads it must be in before the next write)
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "predict_sets_hpd: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is");
-            if (!(ctx->net.l0_f16 && (ovf & kFlagF16Range))) break;
-            if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "predict_sets_hpd: a layer-0 weight left the fp16 range");
-        }
-        s0 += g;
-    }
+    if ((rc = replay_sets(ctx, "predict_sets_hpd", W_sets, act_prm_sets, n_sets, which, apply_out_fn, stack.get(), SetSink()))) return rc;
     // bounds from the float32 values with float64 widths: upstream's calcHPD on the float64 array npbnn_predict_sets returns
     double* lo = d_res.get();
     double* hi = lo + per_set;

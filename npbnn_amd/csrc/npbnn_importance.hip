@@ -10,15 +10,14 @@
 // permuted matrix writes, since a column's largest entry - all its scale depends on - does not move with its rows.  Row indices are
 // checked by a kernel of their own before anything is written.
 //
-// npbnn_predict_sets_summary: the sets replay as in npbnn_predict_sets (groups that share their slopes, the float32 retry; the replay
-// is replay_sets_accumulate, which npbnn_predict_sets_support of npbnn_support.hip and, in a mode of its own, npbnn_predict_sets_lppd of
-// npbnn_lppd.hip call too); after each
-// group summary_accumulate_kernel folds the group's float32 predictions [g][rows][C] into uint32 votes (mode 0: per set and row the
-// first class holding the row's maximum - numpy's argmax) or float64 sums (mode 1: set after set - the order np.mean(axis=0) adds a
-// C-contiguous [S, N, C] array in).  Streaming: g x N x C floats in, N x C accumulators in and out, one thread per row (mode 0) or per
-// four (row, class) entries (mode 1), 16-byte accesses where C allows.  summary_final_kernel divides by the number of sets, takes each
-// row's first argmax of the QUOTIENT (a division can turn an inequality into a tie) and counts [label][argmax] in an LDS histogram
-// with integer atomics, one global integer atomic per nonzero cell and workgroup: the table does not depend on the order.
+// npbnn_predict_sets_summary: the sets replay through replay_sets (npbnn_sets.hip.h: groups that share their slopes, the float32
+// retry); after each group launch_summary_accumulate, which npbnn_predict_sets_support of npbnn_support.hip calls too, folds the
+// group's float32 predictions [g][rows][C] into uint32 votes (mode 0: per set and row the first class holding the row's maximum -
+// numpy's argmax) or float64 sums (mode 1: set after set - the order np.mean(axis=0) adds a C-contiguous [S, N, C] array in).
+// Streaming: g x N x C floats in, N x C accumulators in and out, one thread per row (mode 0) or per four (row, class) entries (mode 1),
+// 16-byte accesses where C allows.  summary_final_kernel divides by the number of sets, takes each row's first argmax of the QUOTIENT
+// (a division can turn an inequality into a tie) and counts [label][argmax] in an LDS histogram with integer atomics, one global
+// integer atomic per nonzero cell and workgroup: the table does not depend on the order.
 #include "npbnn_sets.hip.h"
 
 #include <vector>
@@ -222,6 +221,19 @@ __global__ __launch_bounds__(kFiThreads) void summary_final_kernel(const ACC* __
 
 }  // namespace
 
+void launch_summary_accumulate(hipStream_t st, const float* y, int g, long long n_rows, int C, int mode, double* d_acc, int* d_flag) {
+    const dim3 block(kFiThreads);
+    const long long per_set = n_rows * C;
+    if (mode == 0) {
+        unsigned* votes = reinterpret_cast<unsigned*>(d_acc);
+        if (C % 4 == 0) hipLaunchKernelGGL(summary_votes_kernel<true>, dim3(grid_for(n_rows)), block, 0, st, y, g, n_rows, C, votes, d_flag);
+        else hipLaunchKernelGGL(summary_votes_kernel<false>, dim3(grid_for(n_rows)), block, 0, st, y, g, n_rows, C, votes, d_flag);
+    } else {
+        if (per_set % 4 == 0) hipLaunchKernelGGL(summary_sums_kernel<true>, dim3(grid_for(per_set / 4)), block, 0, st, y, g, per_set, d_acc, d_flag);
+        else hipLaunchKernelGGL(summary_sums_kernel<false>, dim3(grid_for(per_set)), block, 0, st, y, g, per_set, d_acc, d_flag);
+    }
+}
+
 }  // namespace npbnn_api
 
 using namespace npbnn_api;
@@ -323,101 +335,6 @@ extern "C" int npbnn_permute_columns(npbnn_ctx* ctx, int which, const int32_t* c
     return NPBNN_OK;
 }
 
-int npbnn_api::replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which,
-                                      int apply_out_fn, int mode, double* d_acc, int* d_flag, const ReplayLppd* lppd, const ReplayUncertainty* unc) {
-    if (mode == kReplayLppd && (!lppd || apply_out_fn)) return fail(ctx, NPBNN_E_INTERNAL, "%s: the log-likelihood replay takes pre-output values", who);
-    if (mode == kReplayUncertainty && (!unc || apply_out_fn)) return fail(ctx, NPBNN_E_INTERNAL, "%s: the uncertainty replay takes pre-output values", who);
-    Dataset& d = ctx->ds[which];
-    const int C = ctx->net.n_out;
-    const int n_act = ctx->net.n_layers - 1;
-    const long long n_rows = d.m->n_rows;
-    const size_t per_set = (size_t)n_rows * C;
-    const size_t wn = (size_t)ctx->n_weights;
-    hipStream_t st = ctx->stream;
-    int rc;
-    if ((rc = ctx->d_y.reserve(ctx, kMaxCand * per_set))) return rc;
-    FiTimer tm;
-    double pass_ns = 0.0, acc_ns = 0.0;
-    std::vector<double> wstage(kMaxCand * wn);
-    int s0 = 0;
-    while (s0 < n_sets) {
-        // sets that share their activation slopes travel together, up to kMaxCand per streaming read of X (npbnn_predict_sets)
-        int g = 1;
-        while (s0 + g < n_sets && g < kMaxCand &&
-               (!act_prm_sets || n_act == 0 ||
-                memcmp(act_prm_sets + (size_t)(s0 + g) * n_act, act_prm_sets + (size_t)s0 * n_act, (size_t)n_act * sizeof(double)) == 0))
-            ++g;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            LaunchPlan lp;
-            rc = plan_launch(ctx, which, &lp, attempt, g, true);
-            if (rc) return rc;
-            if (lp.n_cand < g) g = lp.n_cand;
-            memcpy(wstage.data(), W_sets + (size_t)s0 * wn, (size_t)g * wn * sizeof(double));
-            tm.mark(0, st);
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_wraw, wstage.data(), (size_t)g * wn * sizeof(double), hipMemcpyHostToDevice, st));
-            for (int l = 0; l < kMaxLayers; ++l) ctx->net.act_prm[l] = 0.f;
-            if (act_prm_sets)
-                for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), st));
-            for (int j = 0; j < g; ++j)
-                launch_pack_weights(ctx, ctx->d_wraw + (size_t)j * wn, nullptr, ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
-            HIP_TRY(ctx, hipGetLastError());
-            EvalParams p = make_params(ctx, d);
-            p.labels = nullptr;
-            p.targets = nullptr;
-            p.net.lik_kind = NPBNN_LIK_NONE;
-            p.y_out = ctx->d_y;
-            p.predict_mode = apply_out_fn ? 2 : 1;
-            p.weight_sets = 1;
-            p.lay = layout_for(ctx, d, true);
-            rc = push_eval_params(ctx, p);
-            if (rc) return rc;
-            rc = launch_plain_eval(ctx, lp, which);
-            if (rc) return rc;
-            HIP_TRY(ctx, hipGetLastError());
-            tm.mark(1, st);
-            int ovf = 0;
-            HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, st));
-            // (push_eval_params stages through one pinned slot: the launch that reads it must be in before the next write)
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            pass_ns += tm.ns(0, 1);
-            if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "%s: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is", who);
-            if (!(ctx->net.l0_f16 && (ovf & kFlagF16Range))) break;
-            if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "%s: a layer-0 weight left the fp16 range", who);
-        }
-        // the group's predictions [g][rows][C] into the accumulator, before the next group overwrites them
-        tm.mark(2, st);
-        if (mode == kReplayLppd) {
-            launch_lppd_accumulate(st, ctx->d_y.get(), g, s0, n_rows, C, d_acc, *lppd, d_flag);
-        } else if (mode == kReplayUncertainty) {
-            launch_uncertainty_accumulate(st, ctx->d_y.get(), g, s0, n_rows, C, d_acc, *unc, d_flag);
-        } else if (mode == kReplayVotes) {
-            unsigned* votes = reinterpret_cast<unsigned*>(d_acc);
-            if (C % 4 == 0)
-                hipLaunchKernelGGL(summary_votes_kernel<true>, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g, n_rows, C, votes, d_flag);
-            else
-                hipLaunchKernelGGL(summary_votes_kernel<false>, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g, n_rows, C, votes, d_flag);
-        } else {
-            if (per_set % 4 == 0)
-                hipLaunchKernelGGL(summary_sums_kernel<true>, dim3(grid_for((long long)(per_set / 4))), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g,
-                                   (long long)per_set, d_acc, d_flag);
-            else
-                hipLaunchKernelGGL(summary_sums_kernel<false>, dim3(grid_for((long long)per_set)), dim3(kFiThreads), 0, st, (const float*)ctx->d_y.get(), g,
-                                   (long long)per_set, d_acc, d_flag);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-        tm.mark(3, st);
-        if (tm.on) {
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            acc_ns += tm.ns(2, 3);
-        }
-        s0 += g;
-    }
-    ctx->fi_ns[1] = pass_ns > (double)INT_MAX ? INT_MAX : (int)pass_ns;
-    ctx->fi_ns[2] = acc_ns > (double)INT_MAX ? INT_MAX : (int)acc_ns;
-    return NPBNN_OK;
-}
-
 extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
                                           int apply_out_fn, int mode, const int64_t* labels, double* out_summary, int64_t* out_confusion) {
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
@@ -450,7 +367,10 @@ extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, 
     }
     HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, per_set * sizeof(double), st));
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    rc = replay_sets_accumulate(ctx, "predict_sets_summary", W_sets, act_prm_sets, n_sets, which, apply_out_fn, mode, d_acc.get(), d_flag.get());
+    rc = replay_sets(ctx, "predict_sets_summary", W_sets, act_prm_sets, n_sets, which, apply_out_fn, nullptr, [&](const SetGroup& grp) {
+        launch_summary_accumulate(st, grp.y, grp.g, n_rows, C, mode, d_acc.get(), d_flag.get());
+        return NPBNN_OK;
+    });
     if (rc) return rc;
     FiTimer tm;
     tm.mark(0, st);

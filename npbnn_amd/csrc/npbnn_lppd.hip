@@ -4,7 +4,7 @@
 // regression.  From that [S][N] matrix, which is never built:
 //   lppd_i = logsumexp_s ll[s][i] - log S,  mean_ll_i = mean_s ll[s][i],  p_waic_i = var_s ll[s][i] (ddof 1),  ll_sample[s] = sum_i ll[s][i].
 //
-// The sets replay through replay_sets_accumulate (npbnn_sets.hip.h) in mode kReplayLppd with apply_out_fn = 0: a group's d_y holds the
+// The sets replay through replay_sets (npbnn_sets.hip.h), the entries' shared driver, with apply_out_fn = 0: a group's d_y holds the
 // float32 pre-output values (logits, or the means of identity-output regression).  lppd_accumulate_kernel, one thread per row, takes
 // each set of the group in set order, widens the row's C values to float64 and forms ll - categorical as z[label] - (max + log sum
 // exp(z - max)), never log(softmax): a probability that underflows in float32 stays a finite log - then updates the row's five float64
@@ -25,43 +25,19 @@ namespace npbnn_api {
 
 namespace {
 
-constexpr int kLppdWaves = kFiThreads / 64;
+constexpr int kLppdAcc = 5;                        // float64 accumulators per row, each an array [n_rows]
 
-// The workgroup's sum of v in a fixed order: lanes by shuffles, then the waves in wave order.  Every thread of the workgroup calls it;
-// thread 0 returns the sum.
-__device__ inline double block_sum(double v, double* lds) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();                                 // (lds may still be read from the previous call)
-    if (lane == 0) lds[wave] = v;
-    __syncthreads();
-    double s = lds[0];
-    for (int w = 1; w < kLppdWaves; ++w) s += lds[w];
-    return s;
-}
-
-// the maximum of a row of C float32 values, widened; nan: one of them is NaN
-template <bool VEC>
-__device__ inline double row_max(const float* __restrict__ row, int C, bool& nan) {
-    double mx = -INFINITY;
-    if (VEC) {
-        for (int k = 0; k < C; k += 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(row + k);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                nan = nan || (v[q] != v[q]);
-                mx = fmax(mx, (double)v[q]);
-            }
-        }
-    } else {
-        for (int k = 0; k < C; ++k) {
-            const float v = row[k];
-            nan = nan || (v != v);
-            mx = fmax(mx, (double)v);
-        }
-    }
-    return mx;
-}
+// What lppd_accumulate_kernel needs beside a group's values, all on the device.  The accumulator acc is [kLppdAcc][n_rows]: the running
+// maximum m of the row's log-likelihoods, sum exp(ll - m), K (the row's ll under the first set), sum (ll - K), sum (ll - K)^2.
+struct LppdArgs {
+    int lik_kind = 0;                 // NPBNN_LIK_CATEGORICAL or NPBNN_LIK_GAUSS
+    const int* labels = nullptr;      // [n_rows] (categorical)
+    const float* targets = nullptr;   // [n_rows][C] (Gaussian)
+    const double* lconst = nullptr;   // [n_sets][C] -0.5 log(2 pi) - log(sigma) (Gaussian)
+    const double* isigma = nullptr;   // [n_sets][C] 1 / sigma (Gaussian)
+    double* part = nullptr;           // [n_sets][n_wg]: every workgroup's sum of its rows' ll under a set
+    int n_wg = 0;                     // workgroups of the accumulate launch: grid_for(n_rows)
+};
 
 // sum_k exp(z[k] - mx), in class order
 template <bool VEC>
@@ -82,8 +58,8 @@ __device__ inline double row_sum_exp(const float* __restrict__ row, int C, doubl
 // GAUSS: the likelihood is Gaussian (else categorical).  VEC: C is a multiple of 4, rows are read as float4.
 template <bool GAUSS, bool VEC>
 __global__ __launch_bounds__(kFiThreads) void lppd_accumulate_kernel(const float* __restrict__ y, int g, int s0, long long n_rows, int C,
-                                                                     double* __restrict__ acc, ReplayLppd a, int* __restrict__ flag) {
-    __shared__ double red[kLppdWaves];
+                                                                     double* __restrict__ acc, LppdArgs a, int* __restrict__ flag) {
+    __shared__ double red[kFiWaves];
     bool nan = false, bad = false;
     const long long per_set = n_rows * C;
     double tot[kMaxCand];
@@ -162,7 +138,7 @@ __global__ __launch_bounds__(kFiThreads) void lppd_accumulate_kernel(const float
 // lppd_i, mean_ll_i, p_waic_i (each output array may be nullptr) and the workgroup's partials of their totals, part[3][gridDim.x]
 __global__ __launch_bounds__(kFiThreads) void lppd_final_kernel(const double* __restrict__ acc, long long n_rows, int n_sets, double* __restrict__ out_lppd,
                                                                 double* __restrict__ out_mean, double* __restrict__ out_pwaic, double* __restrict__ part) {
-    __shared__ double red[kLppdWaves];
+    __shared__ double red[kFiWaves];
     const double S = (double)n_sets, log_s = log(S);
     double t0 = 0.0, t1 = 0.0, t2 = 0.0;
     for (long long r = (long long)blockIdx.x * kFiThreads + threadIdx.x; r < n_rows; r += (long long)gridDim.x * kFiThreads) {
@@ -196,9 +172,8 @@ __global__ __launch_bounds__(kFiThreads) void lppd_label_check_kernel(const int*
     if (bad) atomicOr(flag, kFlagBadLabel);
 }
 
-}  // namespace
-
-void launch_lppd_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int C, double* d_acc, const ReplayLppd& a, int* d_flag) {
+// lppd_accumulate_kernel over a group's values y [g][n_rows][C], the sets s0 .. s0 + g - 1
+void lppd_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int C, double* d_acc, const LppdArgs& a, int* d_flag) {
     const dim3 grid((unsigned)a.n_wg), block(kFiThreads);
     const bool vec = C % 4 == 0;
     if (a.lik_kind == NPBNN_LIK_GAUSS) {
@@ -209,6 +184,8 @@ void launch_lppd_accumulate(hipStream_t st, const float* y, int g, int s0, long 
         else hipLaunchKernelGGL((lppd_accumulate_kernel<false, false>), grid, block, 0, st, y, g, s0, n_rows, C, d_acc, a, d_flag);
     }
 }
+
+}  // namespace
 
 }  // namespace npbnn_api
 
@@ -259,7 +236,7 @@ extern "C" int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, con
     if ((rc = d_part.reserve(ctx, (size_t)(n_sets + 3) * n_wg))) return rc;
     if (n_out_arr && (rc = d_point.reserve(ctx, (size_t)n_out_arr * n_rows))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    ReplayLppd a;
+    LppdArgs a;
     a.lik_kind = lik_kind;
     a.part = d_part.get();
     a.n_wg = n_wg;
@@ -287,7 +264,10 @@ extern "C" int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, con
         if (bad) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: a label lies outside [0, %d)", C);
     }
     // (the first set of a row writes every accumulator: d_acc needs no zeroing)
-    rc = replay_sets_accumulate(ctx, "predict_sets_lppd", W_sets, act_prm_sets, n_sets, which, 0, kReplayLppd, d_acc.get(), d_flag.get(), &a);
+    rc = replay_sets(ctx, "predict_sets_lppd", W_sets, act_prm_sets, n_sets, which, 0, nullptr, [&](const SetGroup& grp) {
+        lppd_accumulate(st, grp.y, grp.g, grp.s0, n_rows, C, d_acc.get(), a, d_flag.get());
+        return NPBNN_OK;
+    });
     if (rc) return rc;
     FiTimer tm;
     tm.mark(0, st);
@@ -303,20 +283,13 @@ extern "C" int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, con
     HIP_TRY(ctx, hipGetLastError());
     tm.mark(1, st);
     int flags = 0;
-    std::vector<double> h_part((size_t)(n_sets + 3) * n_wg);
-    HIP_TRY(ctx, hipMemcpyAsync(&flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(h_part.data(), d_part, h_part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::vector<double> sums;          // every set's ll total, then the three totals
+    if ((rc = fetch_flags_and_totals(ctx, d_flag.get(), d_part.get(), (size_t)n_sets + 3, n_wg, &flags, &sums))) return rc;
     ctx->fi_ns[5] = tm.ns(0, 1);
     if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: a prediction is NaN");
     if (flags & kFlagBadLabel) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: a label lies outside [0, %d)", C);
-    // a set's (a total's) partials in workgroup order
-    for (int s = 0; s < n_sets + 3; ++s) {
-        double t = 0.0;
-        for (int w = 0; w < n_wg; ++w) t += h_part[(size_t)s * n_wg + w];
-        if (s < n_sets) { if (out_ll_sample) out_ll_sample[s] = t; }
-        else out_totals[s - n_sets] = t;
-    }
+    if (out_ll_sample) memcpy(out_ll_sample, sums.data(), (size_t)n_sets * sizeof(double));
+    memcpy(out_totals, sums.data() + n_sets, 3 * sizeof(double));
     if (out_lppd_i) HIP_TRY(ctx, hipMemcpyAsync(out_lppd_i, o_lppd, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
     if (out_mean_ll_i) HIP_TRY(ctx, hipMemcpyAsync(out_mean_ll_i, o_mean, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
     if (out_pwaic_i) HIP_TRY(ctx, hipMemcpyAsync(out_pwaic_i, o_pw, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -11,7 +11,7 @@
 // Route 2, per grid point: the grid values (and data_transform's columns) go into col_override, which the weight pack folds into
 // layer 0's bias; the evaluation kernels of npbnn_predict_sets run once per (grid point, group of sets) on either path, and
 // pdp_add_kernel adds their predictions into the same accumulator.
-#include "npbnn_ctx.hip.h"
+#include "npbnn_sets.hip.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -419,27 +419,13 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
                 int s0 = 0;
                 while (s0 < n_sets) {
                     // sets that share their activation slopes travel together, as many as one pass carries
-                    int ng = 1;
-                    while (s0 + ng < n_sets && ng < lp.n_cand &&
-                           (!act_prm_sets || n_act == 0 ||
-                            memcmp(act_prm_sets + (size_t)(s0 + ng) * n_act, act_prm_sets + (size_t)s0 * n_act, (size_t)n_act * sizeof(double)) == 0))
-                        ++ng;
-                    for (int l = 0; l < kMaxLayers; ++l) ctx->net.act_prm[l] = 0.f;
-                    if (act_prm_sets)
-                        for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
+                    const int ng = slope_group_len(act_prm_sets, n_act, s0, n_sets, lp.n_cand);
+                    load_group_slopes(ctx, act_prm_sets, n_act, s0);
                     for (int j = 0; j < ng; ++j)
                         launch_pack_weights(ctx, d_w.get() + (size_t)(s0 + j) * wn, d_cog,
                                             ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
                     HIP_TRY(ctx, hipGetLastError());
-                    EvalParams p = make_params(ctx, d);
-                    p.labels = nullptr;
-                    p.targets = nullptr;
-                    p.net.lik_kind = NPBNN_LIK_NONE;
-                    p.y_out = ctx->d_y;
-                    p.predict_mode = apply_out_fn ? 2 : 1;
-                    p.weight_sets = 1;
-                    p.lay = layout_for(ctx, d, true);
-                    rc = push_eval_params(ctx, p);
+                    rc = push_eval_params(ctx, predict_params(ctx, d, ctx->d_y, apply_out_fn));
                     if (rc) return rc;
                     rc = launch_plain_eval(ctx, lp, which);
                     if (rc) return rc;

@@ -1,0 +1,109 @@
+// The replay of stored weight sets over a resident table (npbnn_sets.hip.h): the one loop behind npbnn_predict_sets and the entries
+// that summarise its predictions on the device (np_bnn/BNN_lib.py:375-381, 715-748 run one RunPredict per stored sample).  Sets that
+// share their activation slopes travel together, up to kMaxCand per streaming read of X on the resident path and one on the
+// weight-streamed path; a group whose scaled layer-0 weights leave the fp16 range repeats on the exact float32 path.  What an entry does
+// with a group's float32 predictions is its sink.
+#include "npbnn_sets.hip.h"
+
+namespace npbnn_api {
+
+int slope_group_len(const double* act_prm_sets, int n_act, int s0, int n_sets, int cap) {
+    int g = 1;
+    while (s0 + g < n_sets && g < cap &&
+           (!act_prm_sets || n_act == 0 ||
+            memcmp(act_prm_sets + (size_t)(s0 + g) * n_act, act_prm_sets + (size_t)s0 * n_act, (size_t)n_act * sizeof(double)) == 0))
+        ++g;
+    return g;
+}
+
+void load_group_slopes(npbnn_ctx* ctx, const double* act_prm_sets, int n_act, int s0) {
+    for (int l = 0; l < kMaxLayers; ++l) ctx->net.act_prm[l] = 0.f;
+    if (act_prm_sets)
+        for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
+}
+
+EvalParams predict_params(npbnn_ctx* ctx, const Dataset& d, float* y_out, int apply_out_fn) {
+    EvalParams p = make_params(ctx, d);
+    p.labels = nullptr;
+    p.targets = nullptr;
+    p.net.lik_kind = NPBNN_LIK_NONE;
+    p.y_out = y_out;
+    p.predict_mode = apply_out_fn ? 2 : 1;
+    p.weight_sets = 1;
+    p.lay = layout_for(ctx, d, true);
+    return p;
+}
+
+int replay_sets(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which, int apply_out_fn,
+                float* y_stack, const SetSink& sink) {
+    Dataset& d = ctx->ds[which];
+    const int n_act = ctx->net.n_layers - 1;
+    const size_t per_set = (size_t)d.m->n_rows * ctx->net.n_out;
+    const size_t wn = (size_t)ctx->n_weights;
+    hipStream_t st = ctx->stream;
+    int rc;
+    if (!y_stack && (rc = ctx->d_y.reserve(ctx, kMaxCand * per_set))) return rc;
+    FiTimer tm;
+    double pass_ns = 0.0, sink_ns = 0.0;
+    std::vector<double> wstage(kMaxCand * wn);
+    int s0 = 0;
+    while (s0 < n_sets) {
+        int g = slope_group_len(act_prm_sets, n_act, s0, n_sets, kMaxCand);
+        float* y = y_stack ? y_stack + (size_t)s0 * per_set : ctx->d_y.get();
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            LaunchPlan lp;
+            rc = plan_launch(ctx, which, &lp, attempt, g, true);
+            if (rc) return rc;
+            if (lp.n_cand < g) g = lp.n_cand;          // (fewer images fit the LDS, or the weight-streamed path's one: the rest waits for the next round)
+            memcpy(wstage.data(), W_sets + (size_t)s0 * wn, (size_t)g * wn * sizeof(double));
+            tm.mark(0, st);
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_wraw, wstage.data(), (size_t)g * wn * sizeof(double), hipMemcpyHostToDevice, st));
+            load_group_slopes(ctx, act_prm_sets, n_act, s0);
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), st));
+            for (int j = 0; j < g; ++j)
+                launch_pack_weights(ctx, ctx->d_wraw + (size_t)j * wn, nullptr, ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
+            HIP_TRY(ctx, hipGetLastError());
+            rc = push_eval_params(ctx, predict_params(ctx, d, y, apply_out_fn));
+            if (rc) return rc;
+            rc = launch_plain_eval(ctx, lp, which);
+            if (rc) return rc;
+            HIP_TRY(ctx, hipGetLastError());
+            tm.mark(1, st);
+            int ovf = 0;
+            HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, st));
+            // (push_eval_params stages through one pinned slot: the launch that reads it must be in before the next write)
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            pass_ns += tm.ns(0, 1);
+            if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "%s: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is", who);
+            if (!(ctx->net.l0_f16 && (ovf & kFlagF16Range))) break;
+            if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "%s: a layer-0 weight left the fp16 range", who);
+        }
+        // the group's predictions [g][rows][C] to the entry, before the next group overwrites them
+        tm.mark(2, st);
+        if (sink && (rc = sink(SetGroup{s0, g, y}))) return rc;
+        HIP_TRY(ctx, hipGetLastError());
+        tm.mark(3, st);
+        if (tm.on) {
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            sink_ns += tm.ns(2, 3);
+        }
+        s0 += g;
+    }
+    ctx->fi_ns[1] = pass_ns > (double)INT_MAX ? INT_MAX : (int)pass_ns;
+    ctx->fi_ns[2] = sink_ns > (double)INT_MAX ? INT_MAX : (int)sink_ns;
+    return NPBNN_OK;
+}
+
+int fetch_flags_and_totals(npbnn_ctx* ctx, const int* d_flag, const double* d_part, size_t n_q, int n_wg, int* flags, std::vector<double>* totals) {
+    hipStream_t st = ctx->stream;
+    std::vector<double> h_part(n_q * n_wg);
+    HIP_TRY(ctx, hipMemcpyAsync(flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(h_part.data(), d_part, h_part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    totals->assign(n_q, 0.0);
+    for (size_t q = 0; q < n_q; ++q)
+        for (int w = 0; w < n_wg; ++w) (*totals)[q] += h_part[q * n_wg + w];
+    return NPBNN_OK;
+}
+
+}  // namespace npbnn_api

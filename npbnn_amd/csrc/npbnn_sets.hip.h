@@ -1,16 +1,21 @@
-// What the entries that summarise stored weight sets on the device share (npbnn_importance.hip: npbnn_predict_sets_summary;
-// npbnn_support.hip: npbnn_predict_sets_support): the replay of the sets into an accumulator, the flag word's bits, the launch shape of
-// the streaming kernels and the HIP-event timer behind NPBNN_FI_TIMING.  Not part of the ABI.
+// What the entries that run stored weight sets over a resident table share (npbnn_capi.hip: npbnn_predict_sets; npbnn_hpd.hip;
+// npbnn_importance.hip: npbnn_predict_sets_summary; npbnn_support.hip; npbnn_lppd.hip; npbnn_uncertainty.hip; npbnn_pdp.hip, route 2):
+// the replay of the sets group after group (replay_sets, npbnn_sets.hip) and the host helpers it is built from, the flag word's bits,
+// the launch shape of the streaming kernels, the HIP-event timer behind NPBNN_FI_TIMING, the fixed-order workgroup sum and the host
+// tail that adds its partials.  Nothing here belongs to a single entry.  Not part of the ABI.
 #pragma once
 #include "npbnn_ctx.hip.h"
 
 #include <climits>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <vector>
 
 namespace npbnn_api {
 
 constexpr int kFiThreads = 256;
+constexpr int kFiWaves = kFiThreads / 64;
 constexpr int kFiMaxBlocks = 2048;                 // memory-bound kernels: grid-stride beyond this many workgroups
 
 constexpr int kFlagBadRow = 1;                     // permutation index outside [0, n_rows)
@@ -51,47 +56,83 @@ struct FiTimer {
     }
 };
 
-// What replay_sets_accumulate folds a group's float32 values into
-enum { kReplayVotes = 0, kReplaySums = 1, kReplayLppd = 2, kReplayUncertainty = 3 };
+// ---- device helpers (this header is compiled under each unit's default fp contraction, whatever pragma follows the include: only
+// helpers with no product feeding a sum live here)
 
-constexpr int kLppdAcc = 5;                        // float64 accumulators per row of kReplayLppd, each an array [n_rows]
+// The sum of v over a workgroup of kFiThreads threads in a fixed order: lanes by shuffles, then the waves in wave order through
+// lds [kFiWaves].  Every thread of the workgroup calls it; thread 0 returns the sum.
+__device__ inline double block_sum(double v, double* lds) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();                                 // (lds may still be read from the previous call)
+    if (lane == 0) lds[wave] = v;
+    __syncthreads();
+    double s = lds[0];
+    for (int w = 1; w < kFiWaves; ++w) s += lds[w];
+    return s;
+}
 
-// The extra pointers of kReplayLppd (npbnn_lppd.hip), all on the device.  The accumulator d_acc is [kLppdAcc][n_rows]: the running
-// maximum m of the row's log-likelihoods, sum exp(ll - m), K (the row's ll under the first set), sum (ll - K), sum (ll - K)^2.
-struct ReplayLppd {
-    int lik_kind = 0;                 // NPBNN_LIK_CATEGORICAL or NPBNN_LIK_GAUSS
-    const int* labels = nullptr;      // [n_rows] (categorical)
-    const float* targets = nullptr;   // [n_rows][C] (Gaussian)
-    const double* lconst = nullptr;   // [n_sets][C] -0.5 log(2 pi) - log(sigma) (Gaussian)
-    const double* isigma = nullptr;   // [n_sets][C] 1 / sigma (Gaussian)
-    double* part = nullptr;           // [n_sets][n_wg]: every workgroup's sum of its rows' ll under a set
-    int n_wg = 0;                     // workgroups of the accumulate launch: grid_for(n_rows)
+// the maximum of a row of C float32 values, widened; nan: one of them is NaN.  VEC: C is a multiple of 4, the row is read as float4.
+template <bool VEC>
+__device__ inline double row_max(const float* __restrict__ row, int C, bool& nan) {
+    double mx = -INFINITY;
+    if (VEC) {
+        for (int k = 0; k < C; k += 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(row + k);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                nan = nan || (v[q] != v[q]);
+                mx = fmax(mx, (double)v[q]);
+            }
+        }
+    } else {
+        for (int k = 0; k < C; ++k) {
+            const float v = row[k];
+            nan = nan || (v != v);
+            mx = fmax(mx, (double)v);
+        }
+    }
+    return mx;
+}
+
+// ---- host helpers of a replay (npbnn_sets.hip)
+
+// How many of the sets s0, s0 + 1, ... share set s0's activation slopes [n_sets][n_act] (all of them when there are none), cap at most:
+// they travel together in one streaming read of X.
+int slope_group_len(const double* act_prm_sets, int n_act, int s0, int n_sets, int cap);
+
+// set s0's slopes (zeros when there are none) into ctx->net.act_prm
+void load_group_slopes(npbnn_ctx* ctx, const double* act_prm_sets, int n_act, int s0);
+
+// make_params turned into a prediction pass of packed weight images: no labels or targets, no likelihood, float32 values into y_out -
+// pre-output ones unless apply_out_fn
+EvalParams predict_params(npbnn_ctx* ctx, const Dataset& d, float* y_out, int apply_out_fn);
+
+// The sets s0 .. s0 + g - 1 and their float32 predictions y [g][n_rows][C] on the device; the pass that wrote them is complete.
+struct SetGroup {
+    int s0, g;
+    const float* y;
 };
+// What an entry does with a group: returns an NPBNN_* code; may enqueue on ctx->stream.
+using SetSink = std::function<int(const SetGroup&)>;
 
-// What kReplayUncertainty (npbnn_uncertainty.hip) needs beside the accumulator d_acc, which is [C + 1][n_rows] for the softmax output (sum of
-// the sets' probabilities per class, then the sum of their entropies) and [3 or 4][T][n_rows] for regression (K = the first set's mean,
-// sum (mu - K), sum (mu - K)^2, and under NPBNN_OUT_SOFTPLUS_HALF sum sigma^2).
-struct ReplayUncertainty {
-    int out_kind = 0;                 // NPBNN_OUT_SOFTMAX, NPBNN_OUT_IDENTITY or NPBNN_OUT_SOFTPLUS_HALF
-    int n_wg = 0;                     // workgroups of the accumulate launch: grid_for(n_rows)
-};
+// The n_sets weight sets against the resident matrix `which`, group after group: sets that share their slopes travel together, up to
+// kMaxCand per streaming read of X and as many as the launch plan carries (one on the weight-streamed path), and a group whose layer-0
+// weights leave the fp16 range repeats on the float32 path.  Without y_stack every group writes to ctx->d_y, so `sink` has to be
+// through with (or have enqueued its reads of) the values when it returns; with y_stack, [n_sets][n_rows][C] on the device, group s0
+// writes to its place in it.  `sink` (may be empty) runs once per group, after the group's pass has succeeded: never for an attempt
+// that is retried.  `who` names the entry in error messages.  Leaves the time of the passes (weight packing included) and of the sinks
+// in ctx->fi_ns[1], [2] (NPBNN_FI_TIMING).
+int replay_sets(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which, int apply_out_fn,
+                float* y_stack, const SetSink& sink);
 
-// The n_sets weight sets against the resident matrix `which`, group after group as npbnn_predict_sets replays them (sets that share
-// their slopes travel together, the float32 retry), each group's float32 predictions folded into d_acc before the next group
-// overwrites them: kReplayVotes uint32 votes [n_rows][C] (d_acc read as unsigned), kReplaySums float64 sums [n_rows][C], in set order;
-// kReplayLppd (with `lppd`, and apply_out_fn 0: the values are the pre-output ones) the per-row log-likelihood accumulators above;
-// kReplayUncertainty (with `unc`, apply_out_fn 0 likewise) the accumulators of the uncertainty decomposition above.  d_acc
-// (n_rows x C doubles, kLppdAcc x n_rows, or as ReplayUncertainty says) and the flag word d_flag are the caller's, zeroed by it in stream order before the call;
-// kFlagNaN (and kFlagBadLabel, kReplayLppd) is raised there.  `who` names the entry in error messages.  Leaves the pass and accumulation
-// times in ctx->fi_ns[1], [2] (NPBNN_FI_TIMING).  Defined in npbnn_importance.hip.
-int replay_sets_accumulate(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which, int apply_out_fn,
-                           int mode, double* d_acc, int* d_flag, const ReplayLppd* lppd = nullptr, const ReplayUncertainty* unc = nullptr);
+// A group's predictions y [g][n_rows][C] folded into d_acc [n_rows][C]: mode 0 uint32 votes (d_acc read as unsigned), mode 1 float64
+// sums in set order.  d_acc and the flag word are zeroed by the caller in stream order; kFlagNaN is raised there.  Defined next to its
+// kernels in npbnn_importance.hip.
+void launch_summary_accumulate(hipStream_t st, const float* y, int g, long long n_rows, int C, int mode, double* d_acc, int* d_flag);
 
-// lppd_accumulate_kernel over a group's values y [g][n_rows][C], the sets s0 .. s0 + g - 1.  Defined in npbnn_lppd.hip.
-void launch_lppd_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int C, double* d_acc, const ReplayLppd& a, int* d_flag);
-
-// The accumulate kernel of a.out_kind over a group's values y [g][n_rows][n_out], the sets s0 .. s0 + g - 1.  Defined in npbnn_uncertainty.hip.
-void launch_uncertainty_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int n_out, double* d_acc, const ReplayUncertainty& a,
-                                   int* d_flag);
+// The end of an entry on ctx->stream: the flag word into *flags and the partials d_part [n_q][n_wg] back, the stream
+// synchronised, and each quantity's partials added in workgroup order into (*totals)[n_q].
+int fetch_flags_and_totals(npbnn_ctx* ctx, const int* d_flag, const double* d_part, size_t n_q, int n_wg, int* flags, std::vector<double>* totals);
 
 }  // namespace npbnn_api

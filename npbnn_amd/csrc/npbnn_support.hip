@@ -2,7 +2,7 @@
 // get_posterior_threshold's sweep of 99 thresholds (np_bnn/BNN_lib.py:640-671, one get_accuracy_threshold with a cross-tabulation per
 // threshold, :627-637), CalcTP / CalcFP / CalcTP_BF / CalcFP_BF (:305-337) and turn_low_pp_instances_to_nan (:674-679) ask of the summary
 // over the stored samples, in one pass over the accumulator npbnn_predict_sets_summary's replay leaves in HBM
-// (replay_sets_accumulate, npbnn_sets.hip.h: the two entries share it, so their quotients are the same bits).
+// (replay_sets with launch_summary_accumulate, npbnn_sets.hip.h: the two entries share both, so their quotients are the same bits).
 //
 // support_final_kernel, one thread per row as summary_final_kernel: q[k] = (double)acc[k] / n_sets, k* the first class holding the
 // largest q, p = q[k*].  The row then counts once in cube[b][label][k*], b = the number of thresholds strictly below p (bisection
@@ -186,7 +186,10 @@ extern "C" int npbnn_predict_sets_support(npbnn_ctx* ctx, const double* W_sets, 
     HIP_TRY(ctx, hipMemsetAsync(d_tables, 0, (cells + bf_cells) * sizeof(unsigned long long), st));
     HIP_TRY(ctx, hipMemsetAsync(d_acc, 0, per_set * sizeof(double), st));
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    rc = replay_sets_accumulate(ctx, "predict_sets_support", W_sets, act_prm_sets, n_sets, which, apply_out_fn, mode, d_acc.get(), d_flag.get());
+    rc = replay_sets(ctx, "predict_sets_support", W_sets, act_prm_sets, n_sets, which, apply_out_fn, nullptr, [&](const SetGroup& grp) {
+        launch_summary_accumulate(st, grp.y, grp.g, n_rows, C, mode, d_acc.get(), d_flag.get());
+        return NPBNN_OK;
+    });
     if (rc) return rc;
 
     SupportArgs a;

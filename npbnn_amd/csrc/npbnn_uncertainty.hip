@@ -8,7 +8,7 @@
 //     mean_t = mean_s mu_st;  epistemic_t = var_s mu_st (ddof 0);  aleatoric_t = mean_s sigma_st^2 (RegressTransformError only: the
 //     sigma of RegressTransform is the caller's);  total = epistemic + aleatoric.
 //
-// The sets replay through replay_sets_accumulate (npbnn_sets.hip.h) in mode kReplayUncertainty with apply_out_fn = 0: a group's d_y
+// The sets replay through replay_sets (npbnn_sets.hip.h), the driver all stored-sets entries share, with apply_out_fn = 0: a group's d_y
 // holds the float32 pre-output values.  The accumulate kernels, one thread per row, take each set of the group in set order and widen
 // the row's values to float64 before any exp or log.  Softmax: the row is read for its maximum, again for sum exp(z - max) and
 // sum exp(z - max) (z - max) - H = log(sum) - that sum / sum, never log(softmax): a probability that underflows contributes 0 - and a
@@ -33,20 +33,6 @@ namespace npbnn_api {
 
 namespace {
 
-constexpr int kUncWaves = kFiThreads / 64;
-
-// The workgroup's sum of v in a fixed order (as npbnn_lppd.hip's): every thread of the workgroup calls it; thread 0 returns the sum.
-__device__ inline double block_sum(double v, double* lds) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();                                 // (lds may still be read from the previous call)
-    if (lane == 0) lds[wave] = v;
-    __syncthreads();
-    double s = lds[0];
-    for (int w = 1; w < kUncWaves; ++w) s += lds[w];
-    return s;
-}
-
 // softplus as np.logaddexp(0, z) (RegressTransformError): max(z, 0) + log1p(exp(-|z|))
 __device__ inline double softplus_f64(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
 
@@ -65,23 +51,7 @@ __global__ __launch_bounds__(kFiThreads) void unc_softmax_accumulate_kernel(cons
             se[j] = 1.0;
             if (j >= g) continue;
             const float* row = y + (long long)j * per_set + r * C;
-            double m = -INFINITY;
-            if (VEC) {
-                for (int k = 0; k < C; k += 4) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(row + k);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        nan = nan || (v[q] != v[q]);
-                        m = fmax(m, (double)v[q]);
-                    }
-                }
-            } else {
-                for (int k = 0; k < C; ++k) {
-                    const float v = row[k];
-                    nan = nan || (v != v);
-                    m = fmax(m, (double)v);
-                }
-            }
+            const double m = row_max<VEC>(row, C, nan);
             double e = 0.0, ez = 0.0;                 // sum exp(z - m), sum exp(z - m) (z - m), in class order
             if (VEC) {
                 for (int k = 0; k < C; k += 4) {
@@ -218,7 +188,7 @@ __global__ __launch_bounds__(kFiThreads) void unc_regress_accumulate_kernel(cons
 __global__ __launch_bounds__(kFiThreads) void unc_softmax_final_kernel(const double* __restrict__ acc, long long n_rows, int C, int n_sets,
                                                                        double* __restrict__ out_mean, double* __restrict__ out_pred, double* __restrict__ out_exp,
                                                                        double* __restrict__ out_mi, double* __restrict__ part, int* __restrict__ flag) {
-    __shared__ double red[kUncWaves];
+    __shared__ double red[kFiWaves];
     const double S = (double)n_sets;
     double t0 = 0.0, t1 = 0.0, t2 = 0.0;
     bool nan = false;
@@ -255,7 +225,7 @@ template <bool SP>
 __global__ __launch_bounds__(kFiThreads) void unc_regress_final_kernel(const double* __restrict__ acc, long long n_rows, int T, int n_sets,
                                                                        double* __restrict__ out_mean, double* __restrict__ out_total, double* __restrict__ out_alea,
                                                                        double* __restrict__ out_epi, double* __restrict__ part, int* __restrict__ flag) {
-    __shared__ double red[kUncWaves];
+    __shared__ double red[kFiWaves];
     const double S = (double)n_sets;
     const long long tn = (long long)T * n_rows;
     bool nan = false;
@@ -288,16 +258,16 @@ __global__ __launch_bounds__(kFiThreads) void unc_regress_final_kernel(const dou
     if (nan) atomicOr(flag, kFlagNaN);
 }
 
-}  // namespace
-
-void launch_uncertainty_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int n_out, double* d_acc, const ReplayUncertainty& a,
-                                   int* d_flag) {
-    const dim3 grid((unsigned)a.n_wg), block(kFiThreads);
+// The accumulate kernel of out_kind over a group's values y [g][n_rows][n_out], the sets s0 .. s0 + g - 1, on n_wg workgroups.  The
+// accumulator d_acc is [C + 1][n_rows] for the softmax output and [3 or 4][T][n_rows] for regression (above).
+void uncertainty_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int n_out, double* d_acc, int out_kind, int n_wg,
+                            int* d_flag) {
+    const dim3 grid((unsigned)n_wg), block(kFiThreads);
     const bool vec = n_out % 4 == 0;
-    if (a.out_kind == NPBNN_OUT_SOFTMAX) {
+    if (out_kind == NPBNN_OUT_SOFTMAX) {
         if (vec) hipLaunchKernelGGL(unc_softmax_accumulate_kernel<true>, grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
         else hipLaunchKernelGGL(unc_softmax_accumulate_kernel<false>, grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
-    } else if (a.out_kind == NPBNN_OUT_SOFTPLUS_HALF) {
+    } else if (out_kind == NPBNN_OUT_SOFTPLUS_HALF) {
         if (vec) hipLaunchKernelGGL((unc_regress_accumulate_kernel<true, true>), grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
         else hipLaunchKernelGGL((unc_regress_accumulate_kernel<true, false>), grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
     } else {
@@ -305,6 +275,8 @@ void launch_uncertainty_accumulate(hipStream_t st, const float* y, int g, int s0
         else hipLaunchKernelGGL((unc_regress_accumulate_kernel<false, false>), grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
     }
 }
+
+}  // namespace
 
 }  // namespace npbnn_api
 
@@ -348,12 +320,11 @@ extern "C" int npbnn_predict_sets_uncertainty(npbnn_ctx* ctx, const double* W_se
     if ((rc = d_part.reserve(ctx, n_part))) return rc;
     if (n_point && (rc = d_point.reserve(ctx, n_point))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
-    ReplayUncertainty a;
-    a.out_kind = kind;
-    a.n_wg = n_wg;
     // (the first set of a row writes every accumulator: d_acc needs no zeroing)
-    rc = replay_sets_accumulate(ctx, "predict_sets_uncertainty", W_sets, act_prm_sets, n_sets, which, 0, kReplayUncertainty, d_acc.get(), d_flag.get(), nullptr,
-                                &a);
+    rc = replay_sets(ctx, "predict_sets_uncertainty", W_sets, act_prm_sets, n_sets, which, 0, nullptr, [&](const SetGroup& grp) {
+        uncertainty_accumulate(st, grp.y, grp.g, grp.s0, n_rows, n_out, d_acc.get(), kind, n_wg, d_flag.get());
+        return NPBNN_OK;
+    });
     if (rc) return rc;
     FiTimer tm;
     tm.mark(0, st);
@@ -374,18 +345,11 @@ extern "C" int npbnn_predict_sets_uncertainty(npbnn_ctx* ctx, const double* W_se
     HIP_TRY(ctx, hipGetLastError());
     tm.mark(1, st);
     int flags = 0;
-    std::vector<double> h_part(n_part);
-    HIP_TRY(ctx, hipMemcpyAsync(&flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(h_part.data(), d_part, n_part * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::vector<double> totals;
+    if ((rc = fetch_flags_and_totals(ctx, d_flag.get(), d_part.get(), n_part / n_wg, n_wg, &flags, &totals))) return rc;
     ctx->fi_ns[6] = tm.ns(0, 1);
     if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "predict_sets_uncertainty: a prediction is NaN");
-    // a total's partials in workgroup order
-    for (size_t q = 0; q < n_part / n_wg; ++q) {
-        double t = 0.0;
-        for (int w = 0; w < n_wg; ++w) t += h_part[q * n_wg + w];
-        out_totals[q] = t;
-    }
+    memcpy(out_totals, totals.data(), totals.size() * sizeof(double));
     for (int i = 0; i < 4; ++i)
         if (outs[i]) HIP_TRY(ctx, hipMemcpyAsync(outs[i], dev[i], (i == 0 ? n_mean : n_col) * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));

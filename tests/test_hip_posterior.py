@@ -9,6 +9,7 @@ import contextlib
 import io
 
 import cases
+import hpd_cases
 import npbnn_amd as bn
 import oracle as orc
 
@@ -72,6 +73,58 @@ def test_predict_sets_groups_and_single_predict_agree():
         ref = orc.forward(x.astype(np.float32).astype(np.float64), w, orc.Act("tanh"), orc.out_softmax)
         np.testing.assert_allclose(y[i], ref, atol=TOL, rtol=0)
     ctx.close()
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["resident", "streamed"])
+def test_a_group_repeated_in_float32_leaves_the_other_groups_alone(wide, monkeypatch):
+    """Seven sets with the same slopes over 999 rows (a partly filled last workgroup): groups of three, three and one on the
+    resident path, seven of one on the streamed path.  Set 4 holds a layer-0 weight that leaves the fp16 range after column
+    scaling, so its group alone repeats on the float32 path - as a whole: on the resident path sets 3 and 5 travel with it.
+    Every set must equal its own single prediction bit for bit on the path its group ended on (the fp16-split path, or float32
+    for the repeated group; set 4's single prediction repeats by itself, so it is held to both), the summary's mean must be
+    the host's mean of that stack, and the HPD entry's bounds and mean the restatement's."""
+    from npbnn_amd import HipContext, _capi as capi, posterior
+    if wide:
+        monkeypatch.setenv("NPBNN_FORCE_WIDE", "1")
+    rs = np.random.default_rng(11)
+    n, f, c = 999, 6, 3
+    x = rs.standard_normal((n, f))
+    shapes = cases.layer_shapes(f, [5, 4], c, 2)
+    sets = [[rs.normal(0, 0.5, s) for s in shapes] for _ in range(7)]
+    sets[4][0][0, 3] = 3e5
+    repeated = (4,) if wide else (3, 4, 5)
+    ctx = HipContext(0)
+    try:
+        ctx.set_data(x)
+        ctx.set_arch_from_weights(sets[0], f, capi.ACT_TANH, capi.OUT_SOFTMAX, capi.LIK_NONE)
+        assert ctx.is_wide() == wide
+        y = ctx.predict_sets(sets)
+        assert y.shape == (7, n, c) and np.all(np.isfinite(y))
+        single = []
+        for i, w in enumerate(sets):
+            single.append(ctx.predict(w))
+            assert ctx.l0_mode() == ("f32" if i == 4 else "f16-split")       # (set 4, and only set 4, leaves the range)
+        ctx.set_l0_precision("f32")
+        single_f32 = {i: ctx.predict(sets[i]) for i in repeated}
+        ctx.set_l0_precision("auto")
+        for i in range(7):
+            print("set %d: max |predict_sets - predict| = %g%s" % (i, np.max(np.abs(y[i] - single[i])), "" if i not in repeated else
+                  ", against the float32 path's %g" % np.max(np.abs(y[i] - single_f32[i]))))
+        for i in range(7):
+            np.testing.assert_array_equal(y[i], single_f32[i] if i in repeated else single[i], err_msg="set %d" % i)
+        np.testing.assert_array_equal(y[4], single[4])
+        summary, _ = ctx.predict_sets_summary(sets, 1)
+        want = posterior._summarise(y, 1)
+        err = np.max(np.abs(summary - want))
+        print("summary: max |device - host| = %g" % err)
+        assert err <= len(sets) * 2.0 ** -53            # (as test_summary_is_the_hosts: any order of float64 addition of S values in [0, 1])
+        np.testing.assert_array_equal(summary, want)
+        mean, lo, hi = ctx.predict_sets_hpd(sets, 0.8)
+        want_lo, want_hi = hpd_cases.hpd_columns(y, 0.8)
+        assert np.array_equal(lo, want_lo) and np.array_equal(hi, want_hi)
+        np.testing.assert_allclose(mean, np.mean(y, axis=0), rtol=1e-12, atol=0)
+    finally:
+        ctx.close()
 
 
 def test_predictbnn_writes_the_reference_files(tmp_path):
