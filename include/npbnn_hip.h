@@ -186,11 +186,13 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
         * evaluation passes (weight packing included), accumulation launches and final kernel; npbnn_predict_sets_support leaves its
         * passes and accumulation in the same two slots and its own final kernel in NPBNN_INFO_SUPPORT_FINAL_NS; npbnn_predict_sets_lppd
         * does the same with NPBNN_INFO_LPPD_FINAL_NS (and leaves 0 in its three slots when it refuses a call before any launch), and
-        * npbnn_predict_sets_uncertainty with NPBNN_INFO_UNCERTAINTY_FINAL_NS (likewise).  npbnn_predict_sets and npbnn_predict_sets_hpd
+        * npbnn_predict_sets_uncertainty with NPBNN_INFO_UNCERTAINTY_FINAL_NS (likewise), and npbnn_predict_sets_convergence with
+        * NPBNN_INFO_CONVERGENCE_FINAL_NS (its diagnostic and summary kernels; likewise).  npbnn_predict_sets and npbnn_predict_sets_hpd
         * run the same replay, so after them NPBNN_INFO_SUMMARY_PASS_NS / _ACC_NS describe that call: its passes, and the copies to the
         * host (npbnn_predict_sets) or nothing (npbnn_predict_sets_hpd, whose groups write straight into its stack) */
        NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17,
-       NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19, NPBNN_INFO_UNCERTAINTY_FINAL_NS = 20 };
+       NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19, NPBNN_INFO_UNCERTAINTY_FINAL_NS = 20,
+       NPBNN_INFO_CONVERGENCE_FINAL_NS = 21 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -351,6 +353,27 @@ int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, const double* 
  * prediction that is NaN. */
 int npbnn_predict_sets_uncertainty(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
                                    double* out_mean, double* out_total, double* out_aleatoric, double* out_epistemic, double* out_totals);
+
+/* Convergence diagnostics of the n_sets stored samples in function space: split R-hat and effective sample size of every (row, output)
+ * of their predictions on the resident matrix `which`.  The reference leaves convergence to a trace viewer on the logged weights; for
+ * a network those are the wrong quantity (hidden units permute and rescale without changing the function).  The sets are n_chains
+ * chains of N = n_sets / n_chains draws each, chain-major (set s = j * N + t); npbnn_op_convergence (below) has the definition.  The sets
+ * replay as in npbnn_predict_sets_hpd into a float32 device stack [n_sets][n_rows][out_dim] that never leaves the device, under the
+ * same byte budget (1 GiB; NPBNN_HPD_STACK_BYTES in the environment overrides it; NPBNN_E_NOMEM names the largest row count that fits);
+ * one diagnostic launch then reads it once, float64 from the float32 values: the results are the definition's on the float64 array
+ * npbnn_predict_sets returns.  The grid depends on n_rows * out_dim alone: however the replay groups the sets, two calls return the
+ * same bits.
+ *   out_rhat / out_ess  [n_rows][out_dim], or NULL: they then never leave the device
+ *   out_summary         [out_dim][4] (required), per output over the rows: the largest rhat, the smallest ess, the number of columns
+ *                       with rhat > rhat_threshold, the number of constant columns - reduced on the device in a fixed order.  NaNs
+ *                       (constant columns) take no part in the largest / smallest, which are NaN when every column is constant.
+ * NPBNN_E_ARG before any launch: NULL W_sets or out_summary, `which` not 0 or 1, a NaN threshold, n_sets not a multiple of n_chains,
+ * n_chains outside [1, 64], fewer than 8 draws per chain, more than 16384 sets; NPBNN_E_STATE without npbnn_set_arch or without data
+ * on `which`.  NPBNN_E_ARG after the passes: a prediction that is NaN or infinite.  A call refused before any launch leaves 0 in its
+ * three timing slots. */
+int npbnn_predict_sets_convergence(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int32_t n_chains,
+                                   int which, int apply_out_fn, double rhat_threshold, double* out_rhat, double* out_ess,
+                                   double* out_summary);
 
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events
@@ -534,6 +557,23 @@ int npbnn_op_sse(int device, const double* pred, const double* targets, int64_t 
 #define NPBNN_VALUE_F32 1
 int npbnn_op_hpd(int device, const void* values, int value_type, int64_t n_samples, int64_t n_cols, int64_t col_stride, double level,
                  double* out_lo, double* out_hi);
+
+/* npbnn_op_convergence: split R-hat and effective sample size of each of n_cols columns, column c's values at
+ * values[s * col_stride + c] (value_type NPBNN_VALUE_F64 or NPBNN_VALUE_F32).  All arithmetic is float64.  A column is M = n_chains
+ * chains of N = n_draws draws each, chain-major: sample s = j * N + t; 1 <= M <= 64, N >= 8, M * N <= 16384.  Each chain is split
+ * into halves of n = N / 2 draws (rounded down), t in [0, n) and t in [N - n, N): the middle draw of an odd N is dropped; m = 2 M
+ * split chains.  For each split chain k:
+ *   mu_k = (1/n) sum x          d = x - mu_k          acov_k(t) = (1/n) sum_{i < n - t} d_i d_{i+t}          s2_k = acov_k(0) n / (n - 1)
+ * (two passes, mean then centred sums: never the one-pass sum-of-squares form).  Over the split chains:
+ *   W = mean_k s2_k       Bn = sum_k (mu_k - mean mu)^2 / (m - 1)       varp = W (n - 1) / n + Bn       rhat = sqrt(varp / W)
+ *   rho(0) = 1            rho(t) = 1 - (W - mean_k acov_k(t)) / varp
+ * Effective sample size: P_0 = rho(0) + rho(1); for k = 1, 2, ... while 2k + 1 <= n - 1: P_k = rho(2k) + rho(2k + 1), stop at the
+ * first P_k < 0 (that pair is not added), otherwise P_k = min(P_k, P_{k-1}) is added;
+ *   tau = max(-1 + 2 sum P_k, 1 / log10(m n))          ess = m n / tau
+ * No rank normalisation, no tail ESS, no lag cap.  out_rhat / out_ess [n_cols].  A column with W == 0 (every split chain constant)
+ * has rhat = ess = NaN; this is not an error.  NPBNN_E_ARG: the limits above, or a value that is NaN or infinite. */
+int npbnn_op_convergence(int device, const void* values, int value_type, int32_t n_chains, int32_t n_draws, int64_t n_cols,
+                         int64_t col_stride, double* out_rhat, double* out_ess);
 
 /* ---- MC3 temperature-swap exchange over RCCL (xGMI inside a node): replaces the multiprocessing pool
  * round trip of whole pickled chains in MC3.run_mcmc (np_bnn/BNN_mc3.py:94-112), of which the swap

@@ -35,6 +35,7 @@ INFO_PERMUTE_NS, INFO_SUMMARY_PASS_NS, INFO_SUMMARY_ACC_NS, INFO_SUMMARY_FINAL_N
 INFO_SUPPORT_FINAL_NS = 18
 INFO_LPPD_FINAL_NS = 19
 INFO_UNCERTAINTY_FINAL_NS = 20
+INFO_CONVERGENCE_FINAL_NS = 21
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
 E_STATE = -2
@@ -152,6 +153,7 @@ SIGNATURES = {
                                              C.POINTER(C.c_uint8)]),
     "npbnn_predict_sets_lppd": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
     "npbnn_predict_sets_uncertainty": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, _DP, _DP, _DP, _DP, _DP]),
+    "npbnn_predict_sets_convergence": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
     "npbnn_time_eval": (C.c_int, [_P, _DP, C.c_int, _DP, _DP]),
     "npbnn_time_pass": (C.c_int, [_P, _DP, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
     "npbnn_time_wide": (C.c_int, [_P, _DP, C.c_int, _DP, _DP, C.POINTER(C.c_int)]),
@@ -174,6 +176,7 @@ SIGNATURES = {
                                      C.POINTER(C.c_int64)]),
     "npbnn_op_sse": (C.c_int, [C.c_int, _DP, _DP, C.c_int64, C.c_int32, C.c_int32, C.c_int, _DP]),
     "npbnn_op_hpd": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _DP, _DP]),
+    "npbnn_op_convergence": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _DP, _DP]),
     "npbnn_comm_unique_id": (C.c_int, [C.c_char * 128]),
     "npbnn_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char * 128, C.POINTER(_P)]),
     "npbnn_comm_allgather_f64": (C.c_int, [_P, _DP, C.c_int, _DP]),

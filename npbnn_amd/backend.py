@@ -486,6 +486,34 @@ class HipContext:
         return dict(mean=point[0], total_var=point[1], aleatoric_var=point[2], epistemic_var=point[3], mean_avg=avg[0],
                     total_var_avg=avg[1] if sigma else None, aleatoric_var_avg=avg[2] if sigma else None, epistemic_var_avg=avg[3])
 
+    def predict_sets_convergence(self, weight_sets, n_chains=1, rhat_threshold=1.01, act_prm_sets=None, which=capi.TRAIN, apply_out_fn=True,
+                                 pointwise=True):
+        """Split R-hat and effective sample size of several weight sets' predictions on the resident matrix, per (row, output)
+        (npbnn_predict_sets_convergence): the sets are ``n_chains`` chains of equal length, chain-major.  Returns
+        ``posterior_convergence``'s dict; without ``pointwise`` ``rhat`` and ``ess`` are None and never leave the device.  The sets
+        replay as in ``predict_sets_hpd`` into a float32 stack that stays on the device; the results are the definition's on the
+        float64 array ``predict_sets`` returns."""
+        from .convergence import check_shape, result_dict
+        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
+            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
+        packed = capi.as_f64(packed)
+        n_sets, n_rows, n_out = packed.shape[0], self.n_rows[which], self.n_out
+        n_draws = check_shape("predict_sets_convergence", n_sets, n_chains)
+        if n_rows < 1:
+            raise ValueError("predict_sets_convergence: the matrix has no rows")
+        ap = None
+        if act_prm_sets is not None and self.arch.n_layers > 1:
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+            if ap.shape[0] != n_sets:
+                raise ValueError("predict_sets_convergence: %d slope vectors for %d weight sets" % (ap.shape[0], n_sets))
+        rhat = np.empty((n_rows, n_out)) if pointwise else None
+        ess = np.empty((n_rows, n_out)) if pointwise else None
+        summary = np.zeros((n_out, 4))
+        self._chk(self._lib.npbnn_predict_sets_convergence(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, int(n_chains), which,
+                                                           1 if apply_out_fn else 0, float(rhat_threshold), capi.dptr(rhat), capi.dptr(ess),
+                                                           capi.dptr(summary)))
+        return result_dict(rhat, ess, summary, n_rows, n_chains, n_draws)
+
     def predict_pdp(self, weight_sets, focal, grid, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
         prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]

@@ -1019,7 +1019,7 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     if (what == NPBNN_INFO_F16_MOVED_COLUMNS) { *out = ctx->store->f16_shifted_cols; return NPBNN_OK; }
     if (what == NPBNN_INFO_F16_MAX_MOVE) { *out = ctx->store->f16_max_shift; return NPBNN_OK; }
     if (what == NPBNN_INFO_PDP_ROUTE) { *out = ctx->pdp_route; return NPBNN_OK; }
-    if (what >= NPBNN_INFO_PERMUTE_NS && what <= NPBNN_INFO_UNCERTAINTY_FINAL_NS) { *out = ctx->fi_ns[what - NPBNN_INFO_PERMUTE_NS]; return NPBNN_OK; }
+    if (what >= NPBNN_INFO_PERMUTE_NS && what <= NPBNN_INFO_CONVERGENCE_FINAL_NS) { *out = ctx->fi_ns[what - NPBNN_INFO_PERMUTE_NS]; return NPBNN_OK; }
     if (ctx->arch_set && ctx->wide && (what == NPBNN_INFO_WAVES_PER_BLOCK || what == NPBNN_INFO_MAX_CANDIDATES || what == NPBNN_INFO_FAST_TAILS)) {
         *out = what == NPBNN_INFO_WAVES_PER_BLOCK ? 4 : what == NPBNN_INFO_MAX_CANDIDATES ? 1 : 0;      // (group passes and prediction sets: one weight set per pass)
         return NPBNN_OK;

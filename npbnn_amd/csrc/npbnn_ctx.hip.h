@@ -241,9 +241,9 @@ struct npbnn_ctx : npbnn_ctx_streams {
     PinnedBuf<char> h_xbuf;
     bool sync_failed = false;      // a wait timed out once: the schedule stays off for this context
     int debug_sync_skip = -1;      // npbnn_debug_sync_skip_ (diagnostics, not part of the ABI)
-    int fi_ns[7] = {0, 0, 0, 0, 0, 0, 0};   // NPBNN_FI_TIMING: device time of the last npbnn_permute_columns, of the passes / accumulation / final
+    int fi_ns[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // NPBNN_FI_TIMING: device time of the last npbnn_permute_columns, of the passes / accumulation / final
                                    // kernel of the last npbnn_predict_sets_summary, and of the last npbnn_predict_sets_support's,
-                                   // npbnn_predict_sets_lppd's and npbnn_predict_sets_uncertainty's final kernels (NPBNN_INFO_PERMUTE_NS ...;
+                                   // npbnn_predict_sets_lppd's, npbnn_predict_sets_uncertainty's and npbnn_predict_sets_convergence's final kernels (NPBNN_INFO_PERMUTE_NS ...;
                                    // every entry that goes through replay_sets, npbnn_sets.hip.h, leaves its passes and sinks in [1], [2])
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     // weight-streamed path (npbnn_wide.hip): the network does not fit a compute unit's LDS (or NPBNN_OPT_WIDE asks for it)

@@ -23,11 +23,10 @@ namespace npbnn_api {
 
 namespace {
 
-constexpr int kHpdThreads = 256;
-constexpr int kHpdMaxSamples = 16384;
-constexpr int kHpdMaxTile = 64;                        // columns of a workgroup at most
-constexpr size_t kHpdTileLds = 80 * 1024;              // LDS a tile may take when it holds more than one column (two per CU)
-constexpr size_t kHpdStackBytes = 1ull << 30;          // default budget of npbnn_predict_sets_hpd's float32 stack
+constexpr int kHpdThreads = kStackThreads;
+constexpr int kHpdMaxSamples = kStackMaxSamples;
+constexpr int kHpdMaxTile = kStackMaxTile;
+constexpr size_t kHpdTileLds = kStackTileLds;
 
 struct HpdParams {
     const void* values;       // values[s * col_stride + c]
@@ -107,17 +106,6 @@ __global__ __launch_bounds__(kHpdThreads) void hpd_kernel(HpdParams p) {
             if (p.mean) p.mean[c0 + c] = sum / (double)p.S;
         }
     }
-}
-
-template <class T>
-int dev_alloc(npbnn_ctx* ctx, DevBuf<T>& b, size_t n) {
-    return b.reserve(ctx, n ? n : 16 / sizeof(T));
-}
-
-int ilog2(long long v) {
-    int r = 0;
-    while ((1ll << r) < v) ++r;
-    return r;
 }
 
 // nIn of calcHPD, or an error through fail(ctx, ...)
@@ -215,13 +203,7 @@ extern "C" int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, cons
     if ((rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE))) return rc;
     const int C = ctx->net.n_out;
     const size_t per_set = (size_t)d.m->n_rows * C;
-    size_t budget = kHpdStackBytes;
-    if (const char* e = getenv("NPBNN_HPD_STACK_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-    const size_t row_bytes = (size_t)n_sets * C * sizeof(float);
-    if ((size_t)d.m->n_rows * row_bytes > budget)
-        return fail(ctx, NPBNN_E_NOMEM, "predict_sets_hpd: the [%d][%lld][%d] float32 stack takes %zu bytes, over the budget of %zu "
-                    "(NPBNN_HPD_STACK_BYTES); at most %zu rows fit", n_sets, (long long)d.m->n_rows, C, (size_t)d.m->n_rows * row_bytes,
-                    budget, budget / row_bytes);
+    if ((rc = check_stack_budget(ctx, "predict_sets_hpd", n_sets, (long long)d.m->n_rows, C))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf<float> stack;
     DevBuf<double> d_res;

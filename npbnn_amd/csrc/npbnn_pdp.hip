@@ -268,12 +268,6 @@ __global__ __launch_bounds__(256) void pdp_add_kernel(const float* y, int n, lon
     acc[i] = a;
 }
 
-// a device allocation that lives for one call: n elements, 16 bytes when there are none
-template <class T>
-int dev_alloc(npbnn_ctx* ctx, DevBuf<T>& b, size_t n) {
-    return b.reserve(ctx, n ? n : 16 / sizeof(T));
-}
-
 bool env_on(const char* name) {
     const char* e = getenv(name);
     return e && *e && strcmp(e, "0") != 0;

@@ -22,6 +22,17 @@ void load_group_slopes(npbnn_ctx* ctx, const double* act_prm_sets, int n_act, in
         for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
 }
 
+int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_rows, int C) {
+    size_t budget = kStackBytes;
+    if (const char* e = getenv("NPBNN_HPD_STACK_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+    const size_t row_bytes = (size_t)n_sets * C * sizeof(float);
+    if ((size_t)n_rows * row_bytes > budget)
+        return fail(ctx, NPBNN_E_NOMEM, "%s: the [%d][%lld][%d] float32 stack takes %zu bytes, over the budget of %zu "
+                    "(NPBNN_HPD_STACK_BYTES); at most %zu rows fit", who, n_sets, n_rows, C, (size_t)n_rows * row_bytes, budget,
+                    budget / row_bytes);
+    return NPBNN_OK;
+}
+
 EvalParams predict_params(npbnn_ctx* ctx, const Dataset& d, float* y_out, int apply_out_fn) {
     EvalParams p = make_params(ctx, d);
     p.labels = nullptr;

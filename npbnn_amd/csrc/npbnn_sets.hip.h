@@ -1,5 +1,6 @@
 // What the entries that run stored weight sets over a resident table share (npbnn_capi.hip: npbnn_predict_sets; npbnn_hpd.hip;
-// npbnn_importance.hip: npbnn_predict_sets_summary; npbnn_support.hip; npbnn_lppd.hip; npbnn_uncertainty.hip; npbnn_pdp.hip, route 2):
+// npbnn_importance.hip: npbnn_predict_sets_summary; npbnn_support.hip; npbnn_lppd.hip; npbnn_uncertainty.hip; npbnn_convergence.hip;
+// npbnn_pdp.hip, route 2):
 // the replay of the sets group after group (replay_sets, npbnn_sets.hip) and the host helpers it is built from, the flag word's bits,
 // the launch shape of the streaming kernels, the HIP-event timer behind NPBNN_FI_TIMING, the fixed-order workgroup sum and the host
 // tail that adds its partials.  Nothing here belongs to a single entry.  Not part of the ABI.
@@ -21,6 +22,14 @@ constexpr int kFiMaxBlocks = 2048;                 // memory-bound kernels: grid
 constexpr int kFlagBadRow = 1;                     // permutation index outside [0, n_rows)
 constexpr int kFlagNaN = 2;                        // a prediction is NaN
 constexpr int kFlagBadLabel = 4;                   // a label outside [0, C)
+
+// The column kernels over a sample stack [S][n_cols] (npbnn_hpd.hip, npbnn_convergence.hip): a workgroup of kStackThreads threads takes
+// a tile of adjacent columns into LDS.
+constexpr int kStackThreads = 256;
+constexpr int kStackMaxSamples = 16384;
+constexpr int kStackMaxTile = 64;                      // columns of a workgroup at most
+constexpr size_t kStackTileLds = 80 * 1024;            // LDS a tile may take when it holds more than one column (two per CU)
+constexpr size_t kStackBytes = 1ull << 30;             // default budget of a float32 device stack [n_sets][n_rows][out_dim]
 
 inline unsigned grid_for(long long items) {
     long long b = (items + kFiThreads - 1) / kFiThreads;
@@ -96,6 +105,23 @@ __device__ inline double row_max(const float* __restrict__ row, int C, bool& nan
 }
 
 // ---- host helpers of a replay (npbnn_sets.hip)
+
+// room for n elements, and for one vector access when n is 0
+template <class T>
+int dev_alloc(npbnn_ctx* ctx, DevBuf<T>& b, size_t n) {
+    return b.reserve(ctx, n ? n : 16 / sizeof(T));
+}
+
+// the smallest r with 2^r >= v
+inline int ilog2(long long v) {
+    int r = 0;
+    while ((1ll << r) < v) ++r;
+    return r;
+}
+
+// NPBNN_E_NOMEM through fail(ctx, ...) when the float32 stack [n_sets][n_rows][C] of `who` is over its byte budget: kStackBytes, or
+// NPBNN_HPD_STACK_BYTES from the environment.  The message names the largest row count that fits.
+int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_rows, int C);
 
 // How many of the sets s0, s0 + 1, ... share set s0's activation slopes [n_sets][n_act] (all of them when there are none), cap at most:
 // they travel together in one streaming read of X.

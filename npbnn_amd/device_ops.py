@@ -174,3 +174,23 @@ def statistic(kind, y, lab):
         sse, n = _sse(y, lab, 1 if kind == "mse_exp_col0" else 2, True)
         return float(sse[0] / n)
     raise ValueError(kind)
+
+
+def convergence(values, n_chains=1):
+    """npbnn_op_convergence on a [S, n_cols] array, ``n_chains`` chains of S / n_chains draws in chain-major order: (rhat, ess) as
+    float64 [n_cols], NaN in a constant column (npbnn_amd/convergence.py has the definition).  float32 stays float32 on its way to
+    the device, anything else is taken as float64; the arithmetic is float64 either way."""
+    from .convergence import check_shape
+    a = np.asarray(values)
+    if a.ndim != 2:
+        raise ValueError("convergence: values must be [samples, columns], got shape %s" % (a.shape,))
+    v = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    n_draws = check_shape("convergence", v.shape[0], n_chains)
+    n_cols = v.shape[1]
+    rhat, ess = np.empty(n_cols), np.empty(n_cols)
+    if n_cols == 0:
+        return rhat, ess
+    lib, dev = _lib()
+    kind = capi.VALUE_F32 if v.dtype == np.float32 else capi.VALUE_F64
+    _chk(lib, lib.npbnn_op_convergence(dev, v.ctypes.data, kind, int(n_chains), n_draws, n_cols, n_cols, capi.dptr(rhat), capi.dptr(ess)))
+    return rhat, ess

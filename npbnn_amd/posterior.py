@@ -163,6 +163,19 @@ class _SamplePredictor:
                 res["total_var"] = res["epistemic_var"] + aleatoric
         return res
 
+    def convergence(self, features, n_chains, rhat_threshold=1.01, pointwise=True):
+        """``posterior_convergence``'s dict for the stored samples - ``n_chains`` chains of equal length, chain-major - on
+        ``features``, predictions post-output; the stack stays on the device (npbnn_predict_sets_convergence), and without
+        ``pointwise`` ``rhat`` and ``ess`` are None.  A custom output callable has no device kind: its stack is built on the host
+        and goes through ``posterior_convergence``."""
+        if self._kind is None and self._out_fn is not None:
+            from .convergence import posterior_convergence
+            res = posterior_convergence(self.predict(features), n_chains, rhat_threshold)
+            return res if pointwise else dict(res, rhat=None, ess=None)
+        ctx = self._load(features)
+        return ctx.predict_sets_convergence(self._packed, n_chains, rhat_threshold, act_prm_sets=self._slopes,
+                                            apply_out_fn=self._kind is not None, pointwise=pointwise)
+
     def close(self):
         self._ctx.close()
 
