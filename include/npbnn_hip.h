@@ -176,7 +176,11 @@ enum { NPBNN_L0_AUTO = 0, NPBNN_L0_F32 = 1, NPBNN_L0_F16 = 2 };
  * batch cost on each of them - the figure NPBNN_SCHED_AUTO compares, kept apart for batches of fewer than 256 iterations (reported
  * here when measured) and longer ones.  NPBNN_INFO_MAX_CANDIDATES: weight sets one pass over the
  * data can carry for this network (1-3: what fits a compute unit's LDS, and two from three layer-0 output tiles on) - the
- * candidates of a speculative chain pass, the chains of a group pass (npbnn_chains_run_batched), the sets of npbnn_predict_sets. */
+ * candidates of a speculative chain pass, the chains of a group pass (npbnn_chains_run_batched), the sets of npbnn_predict_sets.  On the
+ * weight-streamed path it answers 1 (the group pass carries one chain there), while a replay of stored sets carries up to three per
+ * read of X wherever the first layer's product takes the rest of the pass along (at most 64 nodes, one K-slice) and one elsewhere:
+ * NPBNN_INFO_REPLAY_PASSES: passes over X the last replay of stored sets launched (npbnn_predict_sets and the entries that summarise
+ * it), float32 repeats included; NPBNN_INFO_REPLAY_MAX_GROUP: the most sets one of those passes carried.  Both paths write them. */
 enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 3, NPBNN_INFO_FAST_TAILS = 4,
        NPBNN_INFO_TURN_NS_OVERLAPPED = 5, NPBNN_INFO_TURN_NS_BETWEEN = 6, NPBNN_INFO_MAX_CANDIDATES = 7,
        NPBNN_INFO_IT_NS_OVERLAPPED = 8, NPBNN_INFO_IT_NS_BETWEEN = 9, NPBNN_INFO_WIDE = 10,
@@ -192,7 +196,8 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
         * host (npbnn_predict_sets) or nothing (npbnn_predict_sets_hpd, whose groups write straight into its stack) */
        NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17,
        NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19, NPBNN_INFO_UNCERTAINTY_FINAL_NS = 20,
-       NPBNN_INFO_CONVERGENCE_FINAL_NS = 21 };
+       NPBNN_INFO_CONVERGENCE_FINAL_NS = 21,
+       NPBNN_INFO_REPLAY_PASSES = 22, NPBNN_INFO_REPLAY_MAX_GROUP = 23 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 

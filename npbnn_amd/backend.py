@@ -152,6 +152,11 @@ class HipContext:
         self._chk(self._lib.npbnn_get_info(self._ctx, what, C.byref(out)))
         return out.value
 
+    def replay_info(self):
+        """(passes over the data the last replay of stored weight sets launched, float32 repeats included; the most sets one of
+        them carried): predict_sets and every entry that summarises it."""
+        return self.info(capi.INFO_REPLAY_PASSES), self.info(capi.INFO_REPLAY_MAX_GROUP)
+
     def l0_mode(self):
         """Layer-0 path of the most recent launch: 'f16-split' or 'f32'."""
         return "f16-split" if self.info(capi.INFO_L0_F16) else "f32"

@@ -451,7 +451,7 @@ int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32, int wa
         int rc0 = rebuild_net(ctx, want_f16);
         if (rc0) return rc0;
     }
-    if (ctx->wide) return wide_plan(ctx, which, lp, (predict_only || !lik_only) ? 1 : want_cand);
+    if (ctx->wide) return wide_plan(ctx, which, lp, (predict_only || lik_only) ? want_cand : 1, predict_only);
     lp->wide = false;
     size_t lds = 0;
     // speculative passes: as many candidates as still leave >= 8 waves per workgroup (only the MTI = 1 builds have them)
@@ -753,9 +753,21 @@ void launch_pack_weights(npbnn_ctx* ctx, const double* d_w, const double* d_col_
 }
 
 int launch_plain_eval(npbnn_ctx* ctx, const LaunchPlan& lp, int which) {
+    if (lp.wide && lp.n_cand > 1) return wide_forward(ctx, which, ctx->d_wide_cand, false, false, nullptr, lp.n_cand);
     if (lp.wide) return wide_forward(ctx, which, ctx->d_image, false);
     hipLaunchKernelGGL(lp.fn, dim3(lp.grid), dim3(lp.wpb * 64), lp.lds, ctx->stream, (const EvalParams*)ctx->d_eparams, 0, 1);
     return NPBNN_OK;
+}
+
+float* pass_image(npbnn_ctx* ctx, const LaunchPlan& lp, int j) {
+    if (!lp.wide) return ctx->d_image + (size_t)j * ctx->net.image_floats;
+    return lp.n_cand > 1 ? ctx->d_wide_cand + (size_t)j * ctx->wmeta.image_floats : ctx->d_image.get();
+}
+
+void launch_pack_group(npbnn_ctx* ctx, const LaunchPlan& lp, const double* d_w, const double* d_col_override, int g) {
+    if (lp.wide) { wide_pack(ctx, d_w, d_col_override, pass_image(ctx, lp, 0), ctx->d_overflow + 1, g); return; }
+    for (int j = 0; j < g; ++j)
+        launch_pack_weights(ctx, d_w + (size_t)j * ctx->n_weights, d_col_override, pass_image(ctx, lp, j), ctx->d_overflow);
 }
 
 // confusion counts: device and pinned host buffers for n_classes x n_classes
@@ -814,7 +826,7 @@ int npbnn_create(int device_id, npbnn_ctx** out) {
     // all of them in one copy
     const size_t params_bytes = sizeof(EvalParams) + sizeof(FinalizeParams) + sizeof(ChainParams);
     int rc;
-    if ((rc = ensure_conf(c.get(), kResidentMaxWidth)) || (rc = c->d_out.reserve(nullptr, 1)) || (rc = c->d_overflow.reserve(nullptr, 1)) ||
+    if ((rc = ensure_conf(c.get(), kResidentMaxWidth)) || (rc = c->d_out.reserve(nullptr, 1)) || (rc = c->d_overflow.reserve(nullptr, 1 + kSetFlags)) ||
         (rc = c->d_params.reserve(nullptr, params_bytes)) || (rc = c->h_params.reserve(nullptr, params_bytes)) || (rc = c->h_out.reserve(nullptr, 1)))
         return rc;
     c->d_eparams = reinterpret_cast<EvalParams*>(c->d_params.get());
@@ -1019,9 +1031,11 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     if (what == NPBNN_INFO_F16_MOVED_COLUMNS) { *out = ctx->store->f16_shifted_cols; return NPBNN_OK; }
     if (what == NPBNN_INFO_F16_MAX_MOVE) { *out = ctx->store->f16_max_shift; return NPBNN_OK; }
     if (what == NPBNN_INFO_PDP_ROUTE) { *out = ctx->pdp_route; return NPBNN_OK; }
+    if (what == NPBNN_INFO_REPLAY_PASSES) { *out = ctx->replay_passes; return NPBNN_OK; }
+    if (what == NPBNN_INFO_REPLAY_MAX_GROUP) { *out = ctx->replay_max_group; return NPBNN_OK; }
     if (what >= NPBNN_INFO_PERMUTE_NS && what <= NPBNN_INFO_CONVERGENCE_FINAL_NS) { *out = ctx->fi_ns[what - NPBNN_INFO_PERMUTE_NS]; return NPBNN_OK; }
     if (ctx->arch_set && ctx->wide && (what == NPBNN_INFO_WAVES_PER_BLOCK || what == NPBNN_INFO_MAX_CANDIDATES || what == NPBNN_INFO_FAST_TAILS)) {
-        *out = what == NPBNN_INFO_WAVES_PER_BLOCK ? 4 : what == NPBNN_INFO_MAX_CANDIDATES ? 1 : 0;      // (group passes and prediction sets: one weight set per pass)
+        *out = what == NPBNN_INFO_WAVES_PER_BLOCK ? 4 : what == NPBNN_INFO_MAX_CANDIDATES ? 1 : 0;      // (group passes: one chain per pass; what a replay of stored sets carried: NPBNN_INFO_REPLAY_MAX_GROUP)
         return NPBNN_OK;
     }
     if (what == NPBNN_INFO_WAVES_PER_BLOCK) { size_t lds = 0; *out = pick_waves_per_block(ctx, &lds, 1, layout_for(ctx, ctx->ds[0])); return NPBNN_OK; }

@@ -165,7 +165,7 @@ struct npbnn_ctx : npbnn_ctx_streams {
     // layer-0 block structure (npbnn_set_layer_mask): which (16-node tile, 16-feature group) blocks of the mask hold a nonzero;
     // empty = dense
     std::vector<unsigned char> l0_blocks;      // [mt][ceil(in_dim / 16)]
-    DevBuf<int> d_overflow;
+    DevBuf<int> d_overflow;         // [1 + kSetFlags]: the flag word of a launch, then one per weight set of a replay group
     // parameter blocks of the kernels: device copies (kernels take a pointer) + pinned host staging, both laid out
     // EvalParams | FinalizeParams | ChainParams
     DevBuf<char> d_params;
@@ -245,6 +245,7 @@ struct npbnn_ctx : npbnn_ctx_streams {
                                    // kernel of the last npbnn_predict_sets_summary, and of the last npbnn_predict_sets_support's,
                                    // npbnn_predict_sets_lppd's, npbnn_predict_sets_uncertainty's and npbnn_predict_sets_convergence's final kernels (NPBNN_INFO_PERMUTE_NS ...;
                                    // every entry that goes through replay_sets, npbnn_sets.hip.h, leaves its passes and sinks in [1], [2])
+    int replay_passes = 0, replay_max_group = 0;   // the last replay_sets: passes over X (float32 repeats included), most sets in one (NPBNN_INFO_REPLAY_*)
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     // weight-streamed path (npbnn_wide.hip): the network does not fit a compute unit's LDS (or NPBNN_OPT_WIDE asks for it)
     bool wide = false;
@@ -282,6 +283,8 @@ constexpr int kTurnFirstProbeBatches = 4;       // batches on one persistent for
 constexpr int kTurnReprobeBatches = 48;         // batches on one persistent form before the other's measured turn time is refreshed
 constexpr int kPersistSerialMaxWidth = 640;     // ... and the widest proposal (weights perturbed per iteration) it is picked for
 constexpr int kWideMaxCand = 3;                // weight sets a fused pass of the weight-streamed path carries at most
+static_assert(kWideMaxCand <= kMaxCand, "d_y, the staged weights and the per-set flag words are sized for kMaxCand sets per pass");
+constexpr int kSetFlags = kMaxCand;            // per-set flag words behind ctx->d_overflow[0] (launch_pack_group)
 constexpr int kMinResidentWaves = 4;           // fewer waves than this beside the weight image: the network runs on the weight-streamed path
 constexpr int kWideStepPatchMax = 2048;      // widest proposal whose candidate image the step workgroup keeps by itself (weight-streamed path)
 constexpr size_t kChainMinCapacity = 2048;    // iterations the per-batch chain buffers are sized for at least (allocation is slow)
@@ -313,8 +316,10 @@ struct LaunchPlan {
 bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16);
 int wide_build(npbnn_ctx* ctx, bool f16);
 void wide_free(npbnn_ctx* ctx);
-int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand = 1);
-void wide_pack(npbnn_ctx* ctx, const double* d_w, const double* d_col_override, float* image, int* flags);
+// predict: a predicting launch - its weight sets are independent (stored samples that share their slopes), not a chain's candidates
+int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand = 1, bool predict = false);
+// n_sets > 1: the sets d_w + j * n_weights into the images image + j * wmeta.image_floats, what set j reports into flags[j]
+void wide_pack(npbnn_ctx* ctx, const double* d_w, const double* d_col_override, float* image, int* flags, int n_sets = 1);
 // the forward pass + likelihood of the weights in `image` on the ctx stream; the launch's EvalParams must be in ctx->d_eparams.
 // chain_pass: a pass of a device chain (the kernels leave at once when the chain's batch is through; candidate slopes from the chain)
 // only_layer0: stop behind the first layer's product (timing hook); info: that product's geometry, or nullptr
@@ -322,8 +327,16 @@ int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass,
 int wide_cand_begin(npbnn_ctx* ctx);     // start of a chain batch: candidate image = committed image, nothing patched
 void wide_cand_sync(npbnn_ctx* ctx, int M, int n_cand, bool make_them);   // before a pass of a chain with wide proposals: candidate image = committed image + the pending proposal
 int ensure_conf(npbnn_ctx* ctx, int n_classes);
-// one evaluation launch of a plan on the ctx stream (resident: the plan's kernel; weight-streamed: wide_forward on the committed image)
+// one evaluation launch of a plan on the ctx stream (resident: the plan's kernel; weight-streamed: wide_forward on the committed image,
+// or on the lp.n_cand images of pass_image when the plan carries several sets)
 int launch_plain_eval(npbnn_ctx* ctx, const LaunchPlan& lp, int which);
+// The weight image of set j of a pass of independent weight sets (EvalParams::weight_sets): resident path d_image + j * net.image_floats;
+// weight-streamed path the candidate images, or the committed image when the plan carries one set.
+float* pass_image(npbnn_ctx* ctx, const LaunchPlan& lp, int j);
+// The g sets d_w + j * n_weights (device, float64) packed into the images of a pass (on the weight-streamed path lp.n_cand == g).  Flags:
+// resident path all sets into ctx->d_overflow[0]; weight-streamed path set j into ctx->d_overflow[1 + j] (kSetFlags words: a set out of
+// the fp16 range repeats alone).  The caller zeroes them.
+void launch_pack_group(npbnn_ctx* ctx, const LaunchPlan& lp, const double* d_w, const double* d_col_override, int g);
 
 int max_inner_tiles(const NetMeta& net);
 WaveLayout layout_for(const npbnn_ctx* ctx, const Dataset& d, bool predict_only = false);

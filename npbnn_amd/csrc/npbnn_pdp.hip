@@ -404,7 +404,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
         LaunchPlan lp;
         rc = plan_launch(ctx, which, &lp, attempt, kMaxCand, true);
         if (rc) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, (1 + kSetFlags) * sizeof(int), ctx->stream));
         bool redo = false;
         for (int g0 = 0; g0 < n_grid && !redo; g0 += g_chunk) {
             const int n_g = std::min(g_chunk, n_grid - g0);
@@ -415,13 +415,13 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
                     // sets that share their activation slopes travel together, as many as one pass carries
                     const int ng = slope_group_len(act_prm_sets, n_act, s0, n_sets, lp.n_cand);
                     load_group_slopes(ctx, act_prm_sets, n_act, s0);
-                    for (int j = 0; j < ng; ++j)
-                        launch_pack_weights(ctx, d_w.get() + (size_t)(s0 + j) * wn, d_cog,
-                                            ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
+                    LaunchPlan lpg = lp;
+                    if (lp.wide) lpg.n_cand = ng;      // (the weight-streamed pass has a build per number of sets)
+                    launch_pack_group(ctx, lpg, d_w.get() + (size_t)s0 * wn, d_cog, ng);
                     HIP_TRY(ctx, hipGetLastError());
                     rc = push_eval_params(ctx, predict_params(ctx, d, ctx->d_y, apply_out_fn));
                     if (rc) return rc;
-                    rc = launch_plain_eval(ctx, lp, which);
+                    rc = launch_plain_eval(ctx, lpg, which);
                     if (rc) return rc;
                     hipLaunchKernelGGL(pdp_add_kernel, dim3(add_blocks), dim3(256), 0, ctx->stream, (const float*)ctx->d_y, ng,
                                        (long long)per_set, d_acc.get() + (size_t)gi * per_set, s0 > 0 ? 1 : 0);
@@ -431,9 +431,10 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
                     s0 += ng;
                 }
             }
-            int ovf = 0;
-            HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            int flags[1 + kSetFlags] = {0}, ovf = 0;      // (the weight-streamed path's packing reports per set: any of them restarts the call)
+            HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->d_overflow, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            for (int j = 0; j <= kSetFlags; ++j) ovf |= flags[j];
             if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "predict_pdp: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is");
             if (ctx->net.l0_f16 && (ovf & kFlagF16Range)) {
                 if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "predict_pdp: a layer-0 weight left the fp16 range");

@@ -1,8 +1,10 @@
 // The replay of stored weight sets over a resident table (npbnn_sets.hip.h): the one loop behind npbnn_predict_sets and the entries
 // that summarise its predictions on the device (np_bnn/BNN_lib.py:375-381, 715-748 run one RunPredict per stored sample).  Sets that
-// share their activation slopes travel together, up to kMaxCand per streaming read of X on the resident path and one on the
-// weight-streamed path; a group whose scaled layer-0 weights leave the fp16 range repeats on the exact float32 path.  What an entry does
-// with a group's float32 predictions is its sink.
+// share their activation slopes travel together, up to kMaxCand per streaming read of X: as many as the resident kernel holds images
+// for, and on the weight-streamed path up to kWideMaxCand where the first layer's product is the fused one (one set per pass where it
+// is not: more than 64 nodes, a contraction cut into K-slices).  A group whose scaled layer-0 weights leave the fp16 range repeats on the
+// exact float32 path - on the weight-streamed path, where the packing reports per set, only the set that left it.  What an entry does
+// with a group's float32 predictions is its sink.  NPBNN_INFO_REPLAY_PASSES / _MAX_GROUP: what the last replay launched.
 #include "npbnn_sets.hip.h"
 
 namespace npbnn_api {
@@ -57,22 +59,26 @@ int replay_sets(npbnn_ctx* ctx, const char* who, const double* W_sets, const dou
     FiTimer tm;
     double pass_ns = 0.0, sink_ns = 0.0;
     std::vector<double> wstage(kMaxCand * wn);
+    ctx->replay_passes = 0;
+    ctx->replay_max_group = 0;
     int s0 = 0;
+    bool alone_f32 = false;        // set s0 left the fp16 range in the pass before (weight-streamed path): it runs alone, on the float32 path
     while (s0 < n_sets) {
-        int g = slope_group_len(act_prm_sets, n_act, s0, n_sets, kMaxCand);
+        int g = alone_f32 ? 1 : slope_group_len(act_prm_sets, n_act, s0, n_sets, kMaxCand);
         float* y = y_stack ? y_stack + (size_t)s0 * per_set : ctx->d_y.get();
-        for (int attempt = 0; attempt < 2; ++attempt) {
+        for (int attempt = alone_f32 ? 1 : 0; attempt < 2; ++attempt) {
+            alone_f32 = false;
             LaunchPlan lp;
             rc = plan_launch(ctx, which, &lp, attempt, g, true);
             if (rc) return rc;
-            if (lp.n_cand < g) g = lp.n_cand;          // (fewer images fit the LDS, or the weight-streamed path's one: the rest waits for the next round)
+            if (lp.n_cand < g) g = lp.n_cand;          // (fewer images fit the LDS, or the product is not the fused one: the rest waits for the next round)
+            if (lp.wide) lp.n_cand = g;
             memcpy(wstage.data(), W_sets + (size_t)s0 * wn, (size_t)g * wn * sizeof(double));
             tm.mark(0, st);
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_wraw, wstage.data(), (size_t)g * wn * sizeof(double), hipMemcpyHostToDevice, st));
             load_group_slopes(ctx, act_prm_sets, n_act, s0);
-            HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, sizeof(int), st));
-            for (int j = 0; j < g; ++j)
-                launch_pack_weights(ctx, ctx->d_wraw + (size_t)j * wn, nullptr, ctx->d_image + (size_t)j * ctx->net.image_floats, ctx->d_overflow);
+            HIP_TRY(ctx, hipMemsetAsync(ctx->d_overflow, 0, (1 + kSetFlags) * sizeof(int), st));
+            launch_pack_group(ctx, lp, ctx->d_wraw, nullptr, g);
             HIP_TRY(ctx, hipGetLastError());
             rc = push_eval_params(ctx, predict_params(ctx, d, y, apply_out_fn));
             if (rc) return rc;
@@ -80,14 +86,25 @@ int replay_sets(npbnn_ctx* ctx, const char* who, const double* W_sets, const dou
             if (rc) return rc;
             HIP_TRY(ctx, hipGetLastError());
             tm.mark(1, st);
-            int ovf = 0;
-            HIP_TRY(ctx, hipMemcpyAsync(&ovf, ctx->d_overflow, sizeof(int), hipMemcpyDeviceToHost, st));
+            int flags[1 + kSetFlags] = {0};
+            HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->d_overflow, sizeof(flags), hipMemcpyDeviceToHost, st));
             // (push_eval_params stages through one pinned slot: the launch that reads it must be in before the next write)
             HIP_TRY(ctx, hipStreamSynchronize(st));
             pass_ns += tm.ns(0, 1);
+            ++ctx->replay_passes;
+            if (g > ctx->replay_max_group) ctx->replay_max_group = g;
+            int ovf = flags[0], bad = -1;              // bad: the first set of the group out of the fp16 range (resident path: one word for the group)
+            for (int j = g - 1; j >= 0; --j) {
+                ovf |= flags[1 + j];
+                if ((lp.wide ? flags[1 + j] : flags[0]) & kFlagF16Range) bad = j;
+            }
             if (ovf & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "%s: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is", who);
-            if (!(ctx->net.l0_f16 && (ovf & kFlagF16Range))) break;
+            if (!ctx->net.l0_f16 || bad < 0) break;
             if (ctx->l0_option == NPBNN_L0_F16) return fail(ctx, NPBNN_E_RANGE, "%s: a layer-0 weight left the fp16 range", who);
+            if (!lp.wide) continue;                    // resident path: the whole group again on the float32 path
+            // weight-streamed path: the sets before it are delivered as computed, it repeats alone, a fresh group follows it
+            if (bad > 0) { g = bad; alone_f32 = true; break; }
+            g = 1;
         }
         // the group's predictions [g][rows][C] to the entry, before the next group overwrites them
         tm.mark(2, st);

@@ -143,12 +143,13 @@ struct SetGroup {
 using SetSink = std::function<int(const SetGroup&)>;
 
 // The n_sets weight sets against the resident matrix `which`, group after group: sets that share their slopes travel together, up to
-// kMaxCand per streaming read of X and as many as the launch plan carries (one on the weight-streamed path), and a group whose layer-0
-// weights leave the fp16 range repeats on the float32 path.  Without y_stack every group writes to ctx->d_y, so `sink` has to be
+// kMaxCand per streaming read of X and as many as the launch plan carries (weight-streamed path: up to kWideMaxCand where the pass is
+// the fused one, else one), and a group whose layer-0 weights leave the fp16 range repeats on the float32 path - on the
+// weight-streamed path only the set that left it, alone; the sets before it are delivered as computed and a fresh group follows it.  Without y_stack every group writes to ctx->d_y, so `sink` has to be
 // through with (or have enqueued its reads of) the values when it returns; with y_stack, [n_sets][n_rows][C] on the device, group s0
 // writes to its place in it.  `sink` (may be empty) runs once per group, after the group's pass has succeeded: never for an attempt
 // that is retried.  `who` names the entry in error messages.  Leaves the time of the passes (weight packing included) and of the sinks
-// in ctx->fi_ns[1], [2] (NPBNN_FI_TIMING).
+// in ctx->fi_ns[1], [2] (NPBNN_FI_TIMING), and the passes it launched and the most sets one carried in ctx->replay_passes, replay_max_group.
 int replay_sets(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which, int apply_out_fn,
                 float* y_stack, const SetSink& sink);
 

@@ -276,7 +276,7 @@ int wide_build(npbnn_ctx* ctx, bool f16) {
     return NPBNN_OK;
 }
 
-int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand) {
+int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand, bool predict) {
     Dataset& d = ctx->ds[which];
     const WideMeta& m = ctx->wmeta;
     int max_ld = 16;
@@ -314,19 +314,23 @@ int wide_plan(npbnn_ctx* ctx, int which, LaunchPlan* lp, int want_cand) {
         // two candidates per pass where the fused product has a build for them: its intake of X, not its arithmetic, bounds it
         static const bool one = getenv("NPBNN_WIDE_ONE_CAND") != nullptr;
         const GemmCfg& cf = cfg_for(m.L[0].mt, d.m->n_tiles, ctx->n_cu);
-        if (want_cand >= 2 && !one && cf.f16_d2 != nullptr && !ctx->slopes_option) lp->n_cand = 2;
+        // (trainable slopes: a chain's candidates differ in them, and the pass takes ONE set of slopes from the launch; the stored sets of
+        // a predicting launch travel together only where they share theirs - slope_group_len - and no slope lives in the image)
+        const bool slopes_ok = predict || !ctx->slopes_option;
+        if (want_cand >= 2 && !one && cf.f16_d2 != nullptr && slopes_ok) lp->n_cand = 2;
         static const int cap = getenv("NPBNN_WIDE_MAX_CAND") ? atoi(getenv("NPBNN_WIDE_MAX_CAND")) : kWideMaxCand;
-        if (want_cand >= 3 && !one && cf.f16_d3 != nullptr && !ctx->slopes_option && cap >= 3) lp->n_cand = 3;
+        if (want_cand >= 3 && !one && cf.f16_d3 != nullptr && slopes_ok && cap >= 3) lp->n_cand = 3;
     }
     lp->grid = grid;             // workgroups that write a partial record each (wide_lik_kernel's, or the fused product's row blocks)
     lp->n_waves = grid;
     return NPBNN_OK;
 }
 
-void wide_pack(npbnn_ctx* ctx, const double* d_w, const double* d_col_override, float* image, int* flags) {
+void wide_pack(npbnn_ctx* ctx, const double* d_w, const double* d_col_override, float* image, int* flags, int n_sets) {
     const long long total = wide_item_count(ctx->wmeta);
-    hipLaunchKernelGGL(wide_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, d_w, d_col_override,
-                       ctx->n_classw ? ctx->d_classw : nullptr, image, ctx->wmeta, ctx->wmeta.L[0].f16 ? ctx->store->wscale : nullptr, flags);
+    hipLaunchKernelGGL(wide_pack_kernel, dim3((unsigned)((total + 255) / 256), (unsigned)n_sets), dim3(256), 0, ctx->stream, d_w, d_col_override,
+                       ctx->n_classw ? ctx->d_classw : nullptr, image, ctx->wmeta, ctx->wmeta.L[0].f16 ? ctx->store->wscale : nullptr, flags,
+                       (long long)ctx->n_weights, ctx->wmeta.image_floats);
 }
 
 int wide_forward(npbnn_ctx* ctx, int which, const float* image, bool chain_pass, bool only_layer0, int* info, int n_cand) {

@@ -56,9 +56,15 @@ __host__ __device__ inline long long wide_item_count(const WideMeta& m) {
 }
 
 #ifdef NPBNN_KERNELS_WIDE
+// grid.y = weight set: set j's packed weights w + j * w_stride go to the image j * image_stride floats behind `image`, and what it has to
+// report to the j-th flag word (the sets of a replay group - each its own word, so that one set out of the fp16 range repeats alone;
+// one set: the caller's word itself)
 __global__ void __launch_bounds__(256) wide_pack_kernel(const double* __restrict__ w, const double* __restrict__ col_override,
                                                         const double* __restrict__ class_w, float* __restrict__ image, const WideMeta m,
-                                                        const float* __restrict__ w_scale, int* overflow) {
+                                                        const float* __restrict__ w_scale, int* overflow, long long w_stride, long long image_stride) {
+    w += (long long)blockIdx.y * w_stride;
+    image += (long long)blockIdx.y * image_stride;
+    if (overflow) overflow += blockIdx.y;
     long long piece = (long long)blockIdx.x * 256 + threadIdx.x;
     for (int l = 0; l < m.n_layers; ++l) {
         const WideLayer& L = m.L[l];
@@ -334,8 +340,10 @@ __device__ __forceinline__ WideRowAux wide_row_aux(const EvalParams& p, long lon
     }
     return x;
 }
+// jc: the weight set of the launch these values belong to - independent sets (EvalParams::weight_sets, a replay of stored samples) write
+// their predictions one behind the other; the candidates of a chain pass are not asked for predictions
 __device__ __forceinline__ void wide_row_terms_lean(const EvalParams& p, const float* z, long long row, const float* image, long long classw_off,
-                                                    float final_prm, const WideRowAux& aux, WideRowAccLean& A) {
+                                                    float final_prm, const WideRowAux& aux, WideRowAccLean& A, int jc) {
     const NetMeta& net = p.net;
     const int C = net.n_out, lik_kind = net.lik_kind, k = net.k_targets;
     const int act_kind = net.act_kind;
@@ -376,7 +384,7 @@ __device__ __forceinline__ void wide_row_terms_lean(const EvalParams& p, const f
             }
     }
     if (p.predict_mode && p.y_out != nullptr) {
-        float* yo = p.y_out + row * C;
+        float* yo = p.y_out + ((p.weight_sets != 0 ? (long long)jc * p.n_rows : 0ll) + row) * C;
         for (int o = 0; o < C; ++o) {
             float v = val(o);
             if (p.predict_mode == 2) {
@@ -721,7 +729,7 @@ __global__ void __launch_bounds__(WR * WC * 64) wide_gemm_kernel(const WideGemmA
                             for (int i = 0; i < 4; ++i) zs[n * ldz + 16 * mt + 4 * kq + i] = h[mt][i];
                         }
                     if (lane < 16 && row < p.n_rows)
-                        wide_row_terms_lean(p, zs + lane * ldz, row, a.image + (long long)jc * a.cand_stride, a.classw_off, fprm, aux, A);
+                        wide_row_terms_lean(p, zs + lane * ldz, row, a.image + (long long)jc * a.cand_stride, a.classw_off, fprm, aux, A, jc);
                 }
                 if (p.partials != nullptr) {
                     __syncthreads();                              // (the sums' scratch: free of the candidate before)
