@@ -404,6 +404,24 @@ int ensure_x16(npbnn_ctx* ctx, int which, int* usable) {
                 if (ratio[(size_t)c] > d.m->f16_worst_ratio) { d.m->f16_worst_ratio = ratio[(size_t)c]; d.m->f16_worst_col = c; }
             if (d.m->f16_worst_ratio > 1.0 && !getenv("NPBNN_F16_NO_QUALITY_CHECK")) d.m->f16_state = -2;   // heavy-tailed column(s) past what a moved scale holds
         }
+        d.m->f16_floor_sum = 0.0;
+        if (d.m->f16_state > 0 && which != 0) {     // not the table the scales came from: can a weight's floor show? (kF16FloorSum)
+            const int Fs = std::min(d.m->F, ctx->store->scale_F);
+            DevBuf<unsigned> d_max;
+            if (int rc1 = d_max.reserve(ctx, (size_t)d.m->Fp)) return rc1;
+            HIP_TRY(ctx, hipMemsetAsync(d_max, 0, (size_t)d.m->Fp * sizeof(unsigned), ctx->stream));
+            hipLaunchKernelGGL(col_absmax_kernel, dim3((d.m->Fp + 255) / 256, (unsigned)((d.m->n_rows + 1023) / 1024)), dim3(256), 0, ctx->stream,
+                               (const float*)d.m->X, (long long)d.m->n_rows, d.m->Fp, d_max.get());
+            std::vector<float> h_max((size_t)d.m->Fp), h_scale((size_t)Fs);
+            HIP_TRY(ctx, hipMemcpyAsync(h_max.data(), d_max, h_max.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(h_scale.data(), ctx->store->xscale, h_scale.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            for (int c = 0; c < Fs; ++c) {
+                const double scaled = (double)h_max[(size_t)c] * (double)h_scale[(size_t)c];
+                if (scaled > 1.0) d.m->f16_floor_sum += scaled - 1.0;
+            }
+            if (d.m->f16_floor_sum > kF16FloorSum && !getenv("NPBNN_F16_NO_FLOOR_CHECK")) d.m->f16_state = -3;
+        }
         if (d.m->f16_state < 0) d.m->X16.reset();      // (nobody will read it)
     }
     *usable = d.m->f16_state > 0 ? 1 : 0;
@@ -443,6 +461,11 @@ int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32, int wa
                 return fail(ctx, NPBNN_E_RANGE, "fp16-split layer 0 was requested but column %d spans too many powers of two for a pair of fp16 "
                                                 "numbers, even with its scale moved as far as fp16 allows (largest entry error %.1f x the bound: 2^-17 of the column's mean, "
                                                 "2^-12 of its typical |value|)", d.m->f16_worst_col, d.m->f16_worst_ratio);
+            if (d.m->f16_state == -3)
+                return fail(ctx, NPBNN_E_RANGE, "fp16-split layer 0 was requested but this table's entries are too large under the training table's "
+                                                "column scales: its scaled column maxima exceed 1 by %.1f in all, and past %.1f a weight's absolute "
+                                                "error of 2^-25 as a pair of fp16 numbers can leave the prediction tolerance", d.m->f16_floor_sum,
+                            kF16FloorSum);
             return fail(ctx, NPBNN_E_RANGE, "fp16-split layer 0 was requested but the data cannot be represented in it");
         }
         want_f16 = usable != 0;

@@ -80,9 +80,12 @@ struct FeatureTable {
     DevBuf<float> X16;         // fp16-split copy, row stride Fp16 floats
     int Fp16 = 0;
     int f16_state = 0;         // 0 not built, 1 usable, -1 not representable (inf/NaN or outside the fp16 range), -2 representable but
-                               // too coarse for some column: its entries span too many powers of two for a pair of fp16 numbers
+                               // too coarse for some column: its entries span too many powers of two for a pair of fp16 numbers,
+                               // -3 a table under another table's scales whose scaled entries are large enough for a weight's
+                               // absolute floor to show (ensure_x16, kF16FloorSum)
     int f16_worst_col = -1;    // column with the largest (max entry error / mean |entry|) of the fp16 pair, and that ratio
     double f16_worst_ratio = 0.0;
+    double f16_floor_sum = 0.0;    // sum over columns of what the scaled column maximum exceeds 1 by (a table that did not give the scales: ensure_x16)
     DevBuf<float> X16w;        // the fp16-split copy in the weight-streamed path's piece order (split_x_tiled_kernel), built when a
                                // network on that path first asks for it
 };

@@ -251,6 +251,18 @@ constexpr float kF16QualityTol = 7.62939453125e-06f;        // 2^-17 of the colu
 constexpr float kF16TypicalTol = 2.44140625e-04f;           // 2^-12 of the column's typical |value|
 constexpr float kF16PairRel = 4.76837158203125e-07f;        // 2^-21: an error within this x |entry| is the pair's own 22-bit rounding
 constexpr int kF16MaxShift = 12;                            // scaled entries stay below 2^12 (fp16: 65504)
+// A table split under ANOTHER table's scales (a test table: the scales are the training table's) has no such cap on its scaled entries:
+// kF16Safe alone lets them reach 60000.  The pair holds a scaled weight w' below 2^-3 with an absolute error of up to 2^-25 (half of
+// fp16's subnormal spacing: the low part is subnormal there), however small w' is, and on a row that error is multiplied by |x'_c|
+// and the columns add up: a layer-0 sum is off by up to 2^-25 * sum_c |x'_c| - whatever the weights, and in full when the weights on
+// the large columns are small, as they are when the sums stay O(1).  The X side's quality check cannot see it.  A table of the
+// training table's own range has every scaled column maximum at or below 1 and gives 2^-25 * sum_c min(m_c, 1), F * 2^-25 at the most:
+// the path's own floor.  What a table adds to that, 2^-25 * E with E = sum_c max(m_c - 1, 0) over its scaled column maxima m_c, must
+// leave the prediction bar (2e-5 on an O(1) value) three quarters of its room: 2^-25 * E <= 2e-5 / 4,
+// E <= 167.77.  Past it the table runs on the float32 layer 0 (ensure_x16, state -3).  (The excess, not the sum of the maxima above 1:
+// of a wide table drawn like its training table a fifth of the columns exceed 1 by a few per cent - 1024 columns reach 200 as a sum
+// and 10 as an excess.)  E is a sum over columns of column maxima: shuffling a column's rows (npbnn_permute_columns) leaves it alone.
+constexpr double kF16FloorSum = 2e-5 / 4 * 33554432.0;      // (2^25)
 #ifdef NPBNN_KERNELS_MAIN
 __global__ void __launch_bounds__(256) split_quality_kernel(const float* __restrict__ X, long long n_rows, int Fp, const float* __restrict__ x_scale,
                                                             unsigned* __restrict__ max_err, unsigned long long* __restrict__ sum_abs,
