@@ -149,6 +149,27 @@ def _sse(y, lab, link, first_col_only):
     return out, pred.shape[0]
 
 
+_SSE_KINDS = {"mse": (0, False), "label_mse": (0, False), "mse_exp": (1, False), "mse_exp_col0": (1, True), "mse_pow10_col0": (2, True)}
+
+
+def statistic_sums(kind, y, lab):
+    """What a squared-error statistic is made of, as a vector that adds over rows (a row-sharded chain adds it over its ranks):
+    [rows, squared error per column]; None for every other kind."""
+    if kind not in _SSE_KINDS:
+        return None
+    sse, n = _sse(y, lab, *_SSE_KINDS[kind])
+    return np.concatenate([[float(n)], sse])
+
+
+def statistic_of_sums(kind, sums):
+    n, sse = sums[0], np.asarray(sums[1:], dtype=float)
+    if kind == "label_mse":
+        return sse / n
+    if kind in ("mse", "mse_exp"):
+        return float(np.sum(sse) / (n * len(sse)))
+    return float(sse[0] / n)
+
+
 def statistic(kind, y, lab):
     """The accuracy helpers of the reference on an explicit prediction matrix (BNN_lib.py:195-233, BNN_lik.py:81-99)."""
     if kind == "acc":
@@ -164,15 +185,9 @@ def statistic(kind, y, lab):
     if kind == "label_freq":
         _, counts = _confusion(y, None)
         return counts / np.shape(y)[0]
-    if kind in ("mse", "label_mse"):
-        sse, n = _sse(y, lab, 0, False)
-        return float(np.sum(sse) / (n * len(sse))) if kind == "mse" else sse / n
-    if kind == "mse_exp":
-        sse, n = _sse(y, lab, 1, False)
-        return float(np.sum(sse) / (n * len(sse)))
-    if kind in ("mse_exp_col0", "mse_pow10_col0"):
-        sse, n = _sse(y, lab, 1 if kind == "mse_exp_col0" else 2, True)
-        return float(sse[0] / n)
+    sums = statistic_sums(kind, y, lab)
+    if sums is not None:
+        return statistic_of_sums(kind, sums)
     raise ValueError(kind)
 
 

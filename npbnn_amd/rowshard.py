@@ -17,7 +17,10 @@ communication.
 
 What a sharded sampler does not run on the device: the general chain (indicators, other proposal functions) and MC3's
 exchange run - those fall back to ``mh_step``, which is sharded through ``evaluate``.  Predictions (``_y``, ``predict``) are
-the LOCAL rows' predictions.
+the LOCAL rows' predictions.  The accuracies (``_accuracy``, ``_label_acc``, ``_test_accuracy``) are those of ALL rows for the
+package's own callables - the confusion counts (classification), the squared errors and row counts (regression, the count
+likelihoods' and the predicted-sigma accuracies) added over the ranks, which makes reading them a collective: every rank reads
+them, or none.  An accuracy callable the package does not recognise is given the local predictions and stays local.
 """
 
 import numpy as np
@@ -111,6 +114,10 @@ class RowShardedBackend:
     def rccl_handle(self):
         """The communicator's npbnn_comm* when it is an RcclComm on this context's GPU, else None."""
         return getattr(self._comm, "_comm", None) if type(self._comm).__name__ == "RcclComm" else None
+
+    def sum_over_ranks(self, vec):
+        """A vector of local sums added over the ranks, in rank order: the same bits on every rank."""
+        return _rank_order_sum(self._comm.allgather_f64(np.asarray(vec, dtype=np.float64)))
 
     # -- single evaluations ------------------------------------------------------------------------------------------------
     def evaluate(self, weights, slopes=None, col_override=None, lik_temp=1.0, sigma=None, which=capi.TRAIN, want_confusion=False):

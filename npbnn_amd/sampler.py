@@ -480,8 +480,20 @@ class MCMC():
             self._lazy.update(_accuracy=float(np.mean(mse_col)), _label_acc=mse_col)
             return
         y = self._y
-        self._lazy.update(_accuracy=self._accuracy_f(y, bnn_obj._labels),
-                          _label_acc=self._accuracy_lab_f(y, bnn_obj._labels))
+        self._lazy.update(_accuracy=self._statistic(self._accuracy_f, y, bnn_obj._labels),
+                          _label_acc=self._statistic(self._accuracy_lab_f, y, bnn_obj._labels))
+
+    def _statistic(self, fn, y, lab):
+        """``fn(y, lab)``.  On a row-sharded chain ``y`` and ``lab`` are this rank's rows: the package's squared-error statistics
+        (the regression, count and predicted-sigma accuracies) are formed from the squared errors and row counts of ALL ranks,
+        added in rank order (a collective: every rank asks); any other callable sees the local rows."""
+        kind = stat_kind(fn)
+        if kind is not None and getattr(self._backend, "row_sharded", False):
+            from . import device_ops
+            sums = device_ops.statistic_sums(kind, y, lab)
+            if sums is not None:
+                return device_ops.statistic_of_sums(kind, self._backend.sum_over_ranks(sums))
+        return fn(y, lab)
 
     def _compute_lazy(self, name):
         bnn_obj = self._bnn
@@ -506,7 +518,7 @@ class MCMC():
                 r = self._backend.evaluate(fw, slopes=self._accepted_slopes(bnn_obj), col_override=self._accepted_override,
                                            which=capi.TEST, sigma=np.ones(bnn_obj._labels.shape[1]))
                 return float(np.mean(r["sum_r2"] / r["n_rows"]))
-            return self._accuracy_f(self._y_test, bnn_obj._test_labels)
+            return self._statistic(self._accuracy_f, self._y_test, bnn_obj._test_labels)
         if name == "_label_freq":
             if "_label_freq" not in self._lazy:
                 self._train_stats()

@@ -19,6 +19,10 @@ class OracleBackend:
 
     @property
     def lik_kind(self):
+        from npbnn_amd.likelihoods import likelihood_kind
+        kind = likelihood_kind(getattr(self, "_lik_f", None))          # (capi.LIK_*; set by npbnn_amd.sampler.get_backend)
+        if kind is not None:
+            return kind
         return 0 if self.bnn._estimation_mode == "classification" else 1        # (capi.LIK_CATEGORICAL / LIK_GAUSS)
 
     @property

@@ -3,6 +3,7 @@
     python tests/rank_worker.py mc3 <tmpdir> <backend: oracle|hip> <comm: socket|rccl> <device_exchange: 0|1|none> [fail=<rank>:<mode>]
     python tests/rank_worker.py idle <seconds> [fail=<rank>:<mode>]
     python tests/rank_worker.py rowshard <backend: oracle|hip> <comm: socket|rccl> <case: cls|clsw|reg|regsig>
+    python tests/rank_worker.py rowshard64 <backend: oracle|hip> <comm: socket|rccl> <case,case,...: names of rowshard_cases.CASES>
 
 ``mc3``: the reference's golden MC3 run (tests/golden/mc3.npz: 4 chains, swaps every 20 iterations) with chain i on rank
 i % world.  oracle backend (CPU stand-in, float64): the golden swap sequence, final states and log rows exactly; hip backend
@@ -191,6 +192,124 @@ def run_rowshard(argv):
     print("RANK %d OK" % rank, flush=True)
 
 
+def run_rowshard64(argv):
+    """rowshard64 <backend: oracle|hip> <comm: socket|rccl> <case,case,...>: for every named case of rowshard_cases.CASES, ONE chain
+    whose rows are split over the ranks, advanced in short dispatches and held after every one of them to float64 ON ALL ROWS with
+    the chain's own weights (test_hip_chain_oracle.check_state_on, its bars; 1e-10 on the float64 stand-in) - log-likelihood, prior,
+    accuracies, sigma.  Rank 0 also runs the unsharded float64 twin on all rows and compares the accept / reject sequences; then
+    all ranks must hold the same weights.  Every case prints its worst relative log-likelihood error."""
+    import numpy as np
+    import oracle as orc
+    import npbnn_amd as bn
+    import rowshard_cases as rc
+    import test_hip_chain_oracle as tco
+    from npbnn_amd.rowshard import shard_rows
+    backend, comm_kind, names = argv[0], argv[1], argv[2].split(",")
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    comm = make_comm(comm_kind, rank, world)
+    hip = backend == "hip"
+    if not hip:
+        from oracle_backend import OracleChainBackend, serve_from_oracle
+        serve_from_oracle(lambda b: OracleChainBackend(b, {"classification": 0, "regression-error": 2}.get(b._estimation_mode, 1)))
+    bars = {} if hip else dict(ll_rtol=1e-10, lp_rtol=1e-12, acc_tol=1e-10)
+    sigma_tol = tco.ACC_TOL if hip else 1e-10         # (sigma^2 is the mean squared residual less the squared mean: the accuracy's bar)
+    for name in names:
+        case = rc.CASES[name]
+        assert comm_kind == "rccl" or case["world"] == world, (name, world)       # (over RCCL: one rank per GPU, however many there are)
+        lik, extra, rows = case["lik"], case["extra"], case["rows"]
+        if case["l0"]:
+            os.environ["NPBNN_L0"] = case["l0"]
+        else:
+            os.environ.pop("NPBNN_L0", None)
+        dat = rc.case_data(case, world)
+        x, lab, x_t, lab_t = dat["data"], dat["labels"], dat["test_data"], dat["test_labels"]
+        slopes = extra.get("slopes")
+
+        def build(data, **kw):
+            model = dict(extra.get("model", {}))
+            if slopes:
+                model["actFun"] = bn.ActFun(fun="genReLU", prm=np.array(slopes, dtype=float), trainable=True)
+            bnn, mcmc = tco.make_chain(bn, lik, data, case["widths"], model_kw=model, **dict(extra.get("mcmc", {}), **kw))
+            mcmc.n_candidates, mcmc.SUB_BATCH = case["d"], 16
+            return bnn, mcmc
+        bnn, mcmc = build(shard_rows(dat, rank, world), row_comm=comm)
+        assert mcmc._backend.row_sharded and mcmc._backend.n_rows_total == rows and len(bnn._data) < rows
+        class_w = ()
+        if extra.get("model", {}).get("use_class_weights"):          # balanced weights from the labels of ALL rows (BNN_env.py:98-102)
+            counts = np.bincount(lab, minlength=rc.N_CLASSES).astype(float)
+            class_w = (counts.max() / counts) / np.mean(counts.max() / counts)
+            np.testing.assert_allclose(bnn._class_w, class_w, rtol=1e-14)
+        moved = [False]
+
+        def check(accuracy):
+            act = orc.Act("genReLU", prm=np.array(bnn._act_fun._acc_prm, dtype=float), trainable=True) if slopes else None
+            prior_extra = np.log(10.0) * -np.sum(bnn._act_fun._acc_prm) * 10.0 if slopes and mcmc._slope_term_in_prior else 0.0
+            sig2 = None
+            if extra.get("sigma") == "estimated":
+                sig2 = np.ones(case["k"]) * bnn._error_prm             # the chain's own values
+            elif extra.get("sigma") == "empirical" and moved[0]:       # (until the first accepted proposal sigma is the initial 1)
+                y = orc.forward(x, bnn._w_layers, orc.Act("tanh"), orc.out_identity)
+                sig2 = np.std(y - lab, axis=0)
+                np.testing.assert_allclose(bnn._error_prm, sig2, rtol=sigma_tol)
+            tco.check_state_on(lik, bnn, mcmc, x, lab, x_t, lab_t, worst=errs, accuracy=accuracy, act=act, sig2=sig2, class_w=class_w,
+                               prior_extra=prior_extra, rowwise_accuracy=hip, min_abs=0.1 * rows, **bars)
+            if accuracy and (hip or lik in ("cat", "gauss")):
+                stats = np.array([float(mcmc._accuracy), float(mcmc._test_accuracy)])
+                allv = np.asarray(comm.allgather_f64(stats)).reshape(world, 2)
+                assert np.all(allv == allv[0]), ("ranks disagree on the accuracies", allv.tolist())
+                if lik != "cat":              # (check_state_on holds the test accuracy of a classification only)
+                    y_t = orc.forward(x_t, bnn._w_layers, orc.Act("tanh"), tco._out_fn(lik))
+                    kk = lab_t.shape[1] if lik in ("gauss", "err", "nb2d") else 1
+                    mean = y_t[:, :kk] if lik in ("gauss", "err") else (10.0 ** y_t[:, :kk] if lik == "nb10" else np.exp(y_t[:, :kk]))
+                    want = float(np.mean((mean - lab_t[:, :kk]) ** 2))
+                    tol = bars.get("acc_tol", tco.ACC_TOL)
+                    assert abs(stats[1] - want) <= tol * max(1.0, want), ("test mse", stats[1], want)
+                    if lik == "pois":         # (poi_acc: check_state_on leaves it out)
+                        want = float(np.mean((np.exp(orc.forward(x, bnn._w_layers, orc.Act("tanh"), orc.out_identity)[:, 0]) - lab[:, 0]) ** 2))
+                        assert abs(stats[0] - want) <= tol * max(1.0, want), ("poisson mse", stats[0], want)
+
+        errs, decisions = [], []
+        check(True)
+        sizes = tco.dispatch_sizes(rc.N_ITER)
+        for j, k in enumerate(sizes):
+            mcmc.run_steps(bnn, k)
+            decisions += list(mcmc._last_accepted_mem[-k:])
+            moved[0] = moved[0] or sum(decisions) > 0
+            check(j % 2 == 1 or j + 1 == len(sizes))
+        assert mcmc._current_iteration == rc.N_ITER
+        if extra.get("sigma") == "estimated":
+            assert mcmc._current_iteration > mcmc._estimate_error and not np.all(bnn._error_prm == 1), "no sigma proposal was accepted"
+        if hip:
+            ctx = mcmc._backend.ctx
+            assert mcmc._device_iterations == rc.N_ITER, "the batches did not run on the device (%d iterations did)" % mcmc._device_iterations
+            assert mcmc._device_schedule_used == 1, "a row-sharded batch runs on kernel boundaries (schedule %r)" % mcmc._device_schedule_used
+            if case["d"] > 1:
+                assert mcmc._device_passes < rc.N_ITER, "the extra candidate slots were launched and thrown away"
+            assert bool(ctx.is_wide()) == bool(extra.get("wide")), "the case did not take the path it names"
+            if case["l0"]:
+                from npbnn_amd import _capi
+                assert ctx.info(_capi.INFO_L0_F16) == (0 if case["l0"] == "f32" else 1)
+        if rank == 0:
+            rb, rm = tco.oracle_twin(lik, lambda: build(dat))
+            ref = []
+            for k in sizes:
+                rm.run_steps(rb, k)
+                ref += list(rm._last_accepted_mem[-k:])
+            prefix = tco.assert_trajectory(decisions, ref)
+            assert hip or decisions == ref, "the sharded float64 chain left the float64 chain on all rows"
+            assert sum(decisions) >= 5, "a chain that hardly moves proves nothing (%d accepted)" % sum(decisions)
+            print("[rowshard64] %-10s %-11s world %d  worst logLik rel err %.3e  common prefix %d of %d  accepted %d"
+                  % (extra["family"], name, world, max(errs), prefix, len(ref), sum(decisions)), flush=True)
+        mine = np.concatenate([w.ravel() for w in bnn._w_layers])
+        allw = comm.allgather_f64(mine)
+        assert np.all(allw == allw[0]), "ranks disagree on the chain"
+        if hip:
+            mcmc._backend.ctx.close()
+    comm.barrier()
+    comm.close()
+    print("RANK %d OK" % rank, flush=True)
+
+
 def run_idle(argv):
     fail_rank, fail_mode = planted(argv)
     rank = int(os.environ["RANK"])
@@ -202,4 +321,4 @@ def run_idle(argv):
 
 
 if __name__ == "__main__":
-    {"mc3": run_mc3, "idle": run_idle, "rowshard": run_rowshard}[sys.argv[1]](sys.argv[2:])
+    {"mc3": run_mc3, "idle": run_idle, "rowshard": run_rowshard, "rowshard64": run_rowshard64}[sys.argv[1]](sys.argv[2:])

@@ -133,9 +133,10 @@ def make_data(lik, n, f, n_test=0, seed=5, x_kind="normal", k=2):
     return dat
 
 
-def make_chain(bn, lik, dat, widths, seed=1234, mask_blocks=0, fun="tanh", **mcmc_kw):
+def make_chain(bn, lik, dat, widths, seed=1234, mask_blocks=0, fun="tanh", model_kw=None, **mcmc_kw):
     """npBNN + MCMC on ``dat``; ``mask_blocks``: a block-structured first layer (config-5 like: that many equal blocks of inputs,
-    each feeding its own share of the first layer's nodes)."""
+    each feeding its own share of the first layer's nodes); ``model_kw``: further arguments of npBNN (they win over this
+    function's own)."""
     extra, mk = {}, dict(update_f=[0.05] * 3, update_ws=[0.075] * 3, n_iteration=100000)
     if lik == "gauss":
         extra = dict(estimation_mode="regression", empirical_error=False)
@@ -152,8 +153,10 @@ def make_chain(bn, lik, dat, widths, seed=1234, mask_blocks=0, fun="tanh", **mcm
         extra = dict(estimation_mode="regression-error", output_act_fun=bn.RegressTransformError)
     mk.update(mcmc_kw)
     np.random.seed(seed)
-    bnn = quiet(bn.npBNN, dat, n_nodes=list(widths), actFun=bn.ActFun(fun=fun), use_bias_node=2, prior_f=1, p_scale=1, seed=seed,
-                init_std=0.1, **extra)
+    model = dict(dict(n_nodes=list(widths), actFun=bn.ActFun(fun=fun), use_bias_node=2, prior_f=1, p_scale=1, seed=seed, init_std=0.1),
+                 **extra)
+    model.update(model_kw or {})
+    bnn = quiet(bn.npBNN, dat, **model)
     if mask_blocks:
         f = dat["data"].shape[1]
         w0 = widths[0]
@@ -190,21 +193,23 @@ def generic_addends(lik, y, labels):
         return float(np.sum(np.abs(g(c + n)) + np.abs(g(c + 1)) + np.abs(g(n)) + np.abs(n * np.log(p)) + np.abs(c * np.log1p(-p))))
 
 
-def _accuracy_ok(got, y64, labels):
+def _accuracy_ok(got, y64, labels, tol=ACC_TOL):
     want = orc.acc_classification(y64, labels)
     top2 = np.sort(y64, axis=1)[:, -2:]
     near_ties = int(np.sum(top2[:, -1] - top2[:, 0] < 1e-5)) if y64.shape[1] > 1 else 0
     n = len(labels)
-    return abs(got - want) <= ACC_TOL + near_ties / n, (got, want, near_ties)
+    return abs(got - want) <= tol + near_ties / n, (got, want, near_ties)
 
 
-def oracle_loglik(lik, x, labels, weights, fun="tanh"):
-    y = orc.forward(x, weights, orc.Act(fun), _out_fn(lik))
+def oracle_loglik(lik, x, labels, weights, fun="tanh", act=None, sig2=None, class_w=()):
+    """float64 log-likelihood and predictions; ``act``: an orc.Act in place of ``fun``, ``sig2``: the Gaussian's sigma per column
+    (1 without), ``class_w``: class weights of the categorical."""
+    y = orc.forward(x, weights, act or orc.Act(fun), _out_fn(lik))
     if lik == "cat":
         with np.errstate(divide="ignore"):
-            return orc.lik_categorical(y, labels, np.arange(len(x))), y
+            return orc.lik_categorical(y, labels, np.arange(len(x)), class_weight=class_w), y
     if lik == "gauss":
-        return orc.lik_gaussian(y, labels, None, sig2=np.ones(labels.shape[1])), y
+        return orc.lik_gaussian(y, labels, None, sig2=np.ones(labels.shape[1]) if sig2 is None else sig2), y
     if lik == "err":
         return orc.lik_gaussian_error(y, labels, None), y
     return {"pois": orc.lik_poisson, "nb": orc.lik_negbin, "nb10": orc.lik_negbin_base10, "nb2d": orc.lik_negbin2d}[lik](y, labels), y
@@ -213,30 +218,43 @@ def oracle_loglik(lik, x, labels, weights, fun="tanh"):
 def check_state(lik, bnn, mcmc, worst=None, accuracy=True):
     """The chain's current state against float64: the log-likelihood and prior of the host's weights, and the accuracies.
     Returns the relative log-likelihood error."""
+    return check_state_on(lik, bnn, mcmc, bnn._data, bnn._labels, bnn._test_data, bnn._test_labels, worst=worst, accuracy=accuracy)
+
+
+def check_state_on(lik, bnn, mcmc, data, labels, test_data, test_labels, worst=None, accuracy=True, act=None, sig2=None, class_w=(),
+                   prior_extra=0.0, ll_rtol=LL_RTOL, lp_rtol=LP_RTOL, acc_tol=ACC_TOL, rowwise_accuracy=True, min_abs=None):
+    """check_state on explicit tables (a row-sharded chain holds a share of the rows and answers for all of them).  ``act``,
+    ``sig2``, ``class_w``: see oracle_loglik; ``prior_extra``: what the chain's log prior holds beside the weights' (the slopes'
+    term); the bars default to this module's and may only be tightened (the float64 stand-in); ``rowwise_accuracy`` False leaves
+    out the accuracies whose callables run on the device; ``min_abs``: the least |logLik| at which the relative bar means
+    something - asserted."""
     w = bnn._w_layers
-    want, y = oracle_loglik(lik, bnn._data, bnn._labels, w)
+    act = act or orc.Act("tanh")
+    want, y = oracle_loglik(lik, data, labels, w, act=act, sig2=sig2, class_w=class_w)
     if lik in GENERIC and lik != "pois":         # (relative to S: test_hip_generic_lik's forward bar)
-        err = abs(mcmc._logLik - want) / generic_addends(lik, y, bnn._labels)
+        err = abs(mcmc._logLik - want) / generic_addends(lik, y, labels)
     else:
+        if min_abs is not None:
+            assert abs(want) >= min_abs, ("logLik too near zero for a relative bar", want, min_abs)
         err = abs(mcmc._logLik - want) / max(abs(want), 1e-300)      # (one row of one class: both are 0 exactly)
-    assert err <= LL_RTOL, ("logLik", mcmc._logLik, want, err)
-    lp = orc.log_prior(w, bnn._prior_kind() if bnn._prior else 0, bnn._prior_scale)
-    assert abs(mcmc._logPrior - lp) <= LP_RTOL * max(1.0, abs(lp)), ("logPrior", mcmc._logPrior, lp)
+    assert err <= ll_rtol, ("logLik", mcmc._logLik, want, err)
+    lp = orc.log_prior(w, bnn._prior_kind() if bnn._prior else 0, bnn._prior_scale) + prior_extra
+    assert abs(mcmc._logPrior - lp) <= lp_rtol * max(1.0, abs(lp)), ("logPrior", mcmc._logPrior, lp)
     if accuracy and lik == "cat":
-        ok, info = _accuracy_ok(mcmc._accuracy, y, bnn._labels)
+        ok, info = _accuracy_ok(mcmc._accuracy, y, labels, acc_tol)
         assert ok, ("accuracy", info)
-        if len(bnn._test_data):
-            y_t = orc.forward(bnn._test_data, w, orc.Act("tanh"), orc.out_softmax)
-            ok, info = _accuracy_ok(mcmc._test_accuracy, y_t, bnn._test_labels)
+        if len(test_data):
+            y_t = orc.forward(test_data, w, act, orc.out_softmax)
+            ok, info = _accuracy_ok(mcmc._test_accuracy, y_t, test_labels, acc_tol)
             assert ok, ("test accuracy", info)
-    elif accuracy and lik in ("gauss", "err"):
-        want_mse = float(np.mean(orc.mse_per_column(y, bnn._labels)))
-        assert abs(mcmc._accuracy - want_mse) <= ACC_TOL * max(1.0, want_mse), ("mse", mcmc._accuracy, want_mse)
-    elif accuracy and lik in GENERIC and lik != "pois":       # negbin_acc / negbin_acc_base10 / negbin2d_acc (BNN_lik.py:81-91)
-        kk = bnn._labels.shape[1] if lik == "nb2d" else 1
+    elif accuracy and lik == "gauss" or accuracy and lik == "err" and rowwise_accuracy:
+        want_mse = float(np.mean(orc.mse_per_column(y, labels)))
+        assert abs(mcmc._accuracy - want_mse) <= acc_tol * max(1.0, want_mse), ("mse", mcmc._accuracy, want_mse)
+    elif accuracy and rowwise_accuracy and lik in GENERIC and lik != "pois":       # negbin_acc / negbin_acc_base10 / negbin2d_acc (BNN_lik.py:81-91)
+        kk = labels.shape[1] if lik == "nb2d" else 1
         mean = 10.0 ** y[:, :kk] if lik == "nb10" else np.exp(y[:, :kk])
-        want_mse = float(np.mean((mean - bnn._labels[:, :kk]) ** 2))
-        assert abs(mcmc._accuracy - want_mse) <= ACC_TOL * max(1.0, want_mse), ("count mse", mcmc._accuracy, want_mse)
+        want_mse = float(np.mean((mean - labels[:, :kk]) ** 2))
+        assert abs(mcmc._accuracy - want_mse) <= acc_tol * max(1.0, want_mse), ("count mse", mcmc._accuracy, want_mse)
     if worst is not None:
         worst.append(err)
     return err
@@ -272,7 +290,7 @@ def oracle_twin(lik, build, backend_cls=None):
     from npbnn_amd import sampler
     real = sampler._make_backend
     cls = backend_cls or oracle_backend.OracleChainBackend
-    oracle_backend.serve_from_oracle(lambda b: cls(b, out_kind=0 if lik == "cat" else 1))
+    oracle_backend.serve_from_oracle(lambda b: cls(b, out_kind={"cat": 0, "err": 2}.get(lik, 1)))
     try:
         return build()
     finally:
