@@ -180,7 +180,9 @@ enum { NPBNN_L0_AUTO = 0, NPBNN_L0_F32 = 1, NPBNN_L0_F16 = 2 };
  * weight-streamed path it answers 1 (the group pass carries one chain there), while a replay of stored sets carries up to three per
  * read of X wherever the first layer's product takes the rest of the pass along (at most 64 nodes, one K-slice) and one elsewhere:
  * NPBNN_INFO_REPLAY_PASSES: passes over X the last replay of stored sets launched (npbnn_predict_sets and the entries that summarise
- * it), float32 repeats included; NPBNN_INFO_REPLAY_MAX_GROUP: the most sets one of those passes carried.  Both paths write them. */
+ * it), float32 repeats included; NPBNN_INFO_REPLAY_MAX_GROUP: the most sets one of those passes carried.  Both paths write them.
+ * NPBNN_INFO_L0_OPTION: the NPBNN_OPT_L0_PRECISION in force (NPBNN_L0_*).  A caller that repeats a chain batch after NPBNN_E_RANGE
+ * with cfg->force_f32 = 1 asks it first: under NPBNN_L0_F16 the error stands, as it does for npbnn_eval and npbnn_chain_run_general. */
 enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 3, NPBNN_INFO_FAST_TAILS = 4,
        NPBNN_INFO_TURN_NS_OVERLAPPED = 5, NPBNN_INFO_TURN_NS_BETWEEN = 6, NPBNN_INFO_MAX_CANDIDATES = 7,
        NPBNN_INFO_IT_NS_OVERLAPPED = 8, NPBNN_INFO_IT_NS_BETWEEN = 9, NPBNN_INFO_WIDE = 10,
@@ -197,7 +199,7 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
        NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17,
        NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19, NPBNN_INFO_UNCERTAINTY_FINAL_NS = 20,
        NPBNN_INFO_CONVERGENCE_FINAL_NS = 21,
-       NPBNN_INFO_REPLAY_PASSES = 22, NPBNN_INFO_REPLAY_MAX_GROUP = 23 };
+       NPBNN_INFO_REPLAY_PASSES = 22, NPBNN_INFO_REPLAY_MAX_GROUP = 23, NPBNN_INFO_L0_OPTION = 24 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 

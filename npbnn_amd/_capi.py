@@ -37,6 +37,7 @@ INFO_LPPD_FINAL_NS = 19
 INFO_UNCERTAINTY_FINAL_NS = 20
 INFO_CONVERGENCE_FINAL_NS = 21
 INFO_REPLAY_PASSES, INFO_REPLAY_MAX_GROUP = 22, 23
+INFO_L0_OPTION = 24
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
 E_STATE = -2

@@ -108,9 +108,16 @@ class HipContext:
 
     # -- options ----------------------------------------------------------------------
     def set_l0_precision(self, mode):
-        """'auto' (default): fp16-split first layer when the data allows, else float32; 'f32'; 'f16'."""
+        """'auto' (default): fp16-split first layer when the data allows, else float32 - a launch whose weights leave the fp16 range
+        is repeated on float32; 'f32'; 'f16': the fp16 pair and nothing else - data it cannot hold, or a weight that leaves its range
+        in an evaluation, a replay or a chain batch (``chain_run``, ``chains_run_batched``, and with them ``MCMC.run_steps``), raises
+        NPBNN_E_RANGE instead of repeating."""
         value = {"auto": capi.L0_AUTO, "f32": capi.L0_F32, "f16": capi.L0_F16}[mode]
         self._chk(self._lib.npbnn_set_option(self._ctx, capi.OPT_L0_PRECISION, value))
+
+    def l0_option(self):
+        """The layer-0 precision asked for (the library's own record): 'auto', 'f32' or 'f16'."""
+        return {capi.L0_AUTO: "auto", capi.L0_F32: "f32", capi.L0_F16: "f16"}[self.info(capi.INFO_L0_OPTION)]
 
     def set_fast_tails(self, on):
         """Shape-specialised builds of the evaluation kernel for likelihood-only launches (default on; same results)."""
@@ -681,7 +688,8 @@ class HipContext:
             rc = run(self._ctx, C.byref(cfg), addr[0], addr[1], K, M, addr[2], addr[3], addr[4], addr[5], addr[6], addr[7], addr[8],
                      C.byref(res))
             self.seconds_in_chain_run += _now() - t_in          # (what a dispatch spends inside the library: tools/profile_dispatch.py)
-            if rc == capi.E_RANGE and attempt == 0:
+            # ('f16' asked for the fp16 pair and nothing else: there the error stands, as it does for eval and predict)
+            if rc == capi.E_RANGE and attempt == 0 and self.l0_option() != "f16":
                 attempt = 1
                 continue        # a weight left the fp16 range: same batch again on the float32 path (state untouched)
             if rc == capi.E_SYNC and not sync_retried:
@@ -910,7 +918,7 @@ def chains_run_batched(jobs, K):
             keep.append((w, idx, cnt, delta, log_u, m, cfg, res))
             outs.append(dict(w=w, accepted=acc, loglik_prop=llp, logprior_prop=lpp, _res=res, _ctx=ctx))
         rc = lib.npbnn_chains_run_batched(arr, len(jobs), K)
-        if rc == capi.E_RANGE and attempt == 0:
+        if rc == capi.E_RANGE and attempt == 0 and all(job["ctx"].l0_option() != "f16" for job in jobs):
             continue
         capi.check(lib, jobs[0]["ctx"]._ctx, rc)
         break

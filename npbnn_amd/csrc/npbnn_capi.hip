@@ -1050,6 +1050,7 @@ int npbnn_set_option(npbnn_ctx* ctx, int option, int value) {
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     if (!ctx || !out) return fail(ctx, NPBNN_E_ARG, "get_info: bad arguments");
     if (what == NPBNN_INFO_L0_F16) { *out = ctx->net.l0_f16; return NPBNN_OK; }
+    if (what == NPBNN_INFO_L0_OPTION) { *out = ctx->l0_option; return NPBNN_OK; }
     if (what == NPBNN_INFO_WIDE) { *out = (ctx->arch_set && ctx->wide) ? 1 : 0; return NPBNN_OK; }
     if (what == NPBNN_INFO_F16_MOVED_COLUMNS) { *out = ctx->store->f16_shifted_cols; return NPBNN_OK; }
     if (what == NPBNN_INFO_F16_MAX_MOVE) { *out = ctx->store->f16_max_shift; return NPBNN_OK; }

@@ -4,6 +4,7 @@
     python tests/rank_worker.py idle <seconds> [fail=<rank>:<mode>]
     python tests/rank_worker.py rowshard <backend: oracle|hip> <comm: socket|rccl> <case: cls|clsw|reg|regsig>
     python tests/rank_worker.py rowshard64 <backend: oracle|hip> <comm: socket|rccl> <case,case,...: names of rowshard_cases.CASES>
+    python tests/rank_worker.py rowshard_range <backend: oracle|hip> <comm: socket|rccl>
 
 ``mc3``: the reference's golden MC3 run (tests/golden/mc3.npz: 4 chains, swaps every 20 iterations) with chain i on rank
 i % world.  oracle backend (CPU stand-in, float64): the golden swap sequence, final states and log rows exactly; hip backend
@@ -310,6 +311,72 @@ def run_rowshard64(argv):
     print("RANK %d OK" % rank, flush=True)
 
 
+def run_rowshard_range(argv):
+    """rowshard_range <backend: oracle|hip> <comm: socket|rccl>: rowshard_cases.RANGE_CASE - ONE chain whose rows are split over
+    the ranks takes planted draws (range_cases.serve_draws; planned in float64 on ALL rows, the same on every rank) whose
+    iteration RANGE_T_STAR puts a layer-0 weight outside fp16: every rank abandons that batch and repeats it on float32
+    (``l0_mode()``), the flags and weights are the float64 stand-in's on every rank, the state is float64's on all rows."""
+    import numpy as np
+    import npbnn_amd as bn
+    import range_cases as rg
+    import rowshard_cases as rc
+    import test_hip_chain_oracle as tco
+    from npbnn_amd.rowshard import shard_rows
+    backend, comm_kind = argv[:2]
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    comm = make_comm(comm_kind, rank, world)
+    hip = backend == "hip"
+    if not hip:
+        from oracle_backend import OracleChainBackend, serve_from_oracle
+        serve_from_oracle(lambda b: OracleChainBackend(b, 0))
+    os.environ["NPBNN_NO_FAST_DISPATCH"] = "1"           # (the kept dispatch draws for itself)
+    os.environ.pop("NPBNN_L0", None)
+    case = rc.RANGE_CASE
+    assert case["world"] == world
+    dat = rc.case_data(case, world)
+    bnn, mcmc = tco.make_chain(bn, "cat", shard_rows(dat, rank, world), case["widths"], row_comm=comm)
+    mcmc.n_candidates, mcmc.SUB_BATCH = case["d"], 64
+    assert mcmc._backend.row_sharded and len(bnn._data) < case["rows"]
+    assert bnn._prior_kind() == rg.PRIOR_NORMAL and bnn._w_bound == np.inf
+    p = dict(rg.problem_of(bnn), x=np.asarray(dat["data"], dtype=np.float64), labels=np.asarray(dat["labels"]))
+    K = sum(rc.RANGE_DISPATCHES)
+    plant = rg.plant_index(p, np.random.default_rng(9))
+    with np.errstate(over="ignore"):
+        plan = rg.build_batches(p, 97, [(K, rc.RANGE_T_STAR, plant, False, 0, "mid")])[0]
+    rg.serve_draws(mcmc, plan)
+    bars = {} if hip else dict(ll_rtol=1e-10, lp_rtol=1e-12, acc_tol=1e-10)
+    modes, done = [], 0
+    if hip:            # the layer-0 path of every device batch, read before the dispatch's own evaluations (accuracies) follow it
+        ctx = mcmc._backend.ctx
+        real_chain_run = ctx.chain_run
+
+        def chain_run(*a, **kw):
+            out = real_chain_run(*a, **kw)
+            modes.append(ctx.l0_mode())
+            return out
+        ctx.chain_run = chain_run
+    with np.errstate(over="ignore"):
+        for k in rc.RANGE_DISPATCHES:
+            mcmc.run_steps(bnn, k)
+            done += k
+            assert list(mcmc._last_accepted_mem[-k:]) == [int(a) for a in plan["want"]["acc"][done - k:done]], "left the stand-in's decisions"
+            tco.check_state_on("cat", bnn, mcmc, dat["data"], dat["labels"], dat["test_data"], dat["test_labels"], min_abs=0.1 * case["rows"], **bars)
+    assert done - rc.RANGE_DISPATCHES[-1] > rc.RANGE_T_STAR >= rc.RANGE_DISPATCHES[0]
+    assert rg.pack(bnn._w_layers).tobytes() == plan["want"]["w"].tobytes(), "the weights are not the stand-in's"
+    if hip:
+        assert modes == ["f16-split", "f32", "f16-split"], modes
+        assert mcmc._device_iterations == K and mcmc._device_schedule_used == 1
+    allw = comm.allgather_f64(rg.pack(bnn._w_layers))
+    assert np.all(allw == allw[0]), "ranks disagree on the chain"
+    flags = comm.allgather_f64(np.array(mcmc._last_accepted_mem[-K:], dtype=float))
+    assert np.all(flags == flags[0]), "ranks disagree on the decisions"
+    if hip:
+        mcmc._backend.ctx.close()
+    comm.barrier()
+    comm.close()
+    print("RANK %d OK" % rank, flush=True)
+
+
 def run_idle(argv):
     fail_rank, fail_mode = planted(argv)
     rank = int(os.environ["RANK"])
@@ -321,4 +388,4 @@ def run_idle(argv):
 
 
 if __name__ == "__main__":
-    {"mc3": run_mc3, "idle": run_idle, "rowshard": run_rowshard, "rowshard64": run_rowshard64}[sys.argv[1]](sys.argv[2:])
+    {"mc3": run_mc3, "idle": run_idle, "rowshard": run_rowshard, "rowshard64": run_rowshard64, "rowshard_range": run_rowshard_range}[sys.argv[1]](sys.argv[2:])

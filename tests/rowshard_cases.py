@@ -69,6 +69,13 @@ CASES = {
     "gsl3": _c("streamed", "gauss", 600, 1500, (200, 8), 2, k=2, env=_SLICES, wide=True, mcmc=_FEW),
 }
 
+# the planted fp16-range batch (tests/range_cases.py) on two ranks: every rank has to abandon and repeat the same batch
+# (``rank_worker.py rowshard_range``; not one of CASES: its draws are planted, not the chain's own)
+RANGE_CASE = _c("range", "cat", 403, 40, (16, 5), 2, d=3, n_test=0)
+RANGE_CASE["l0"] = "auto"
+RANGE_DISPATCHES = (20, 30, 20)          # clean, the planted one (t* = RANGE_T_STAR), clean
+RANGE_T_STAR = 33
+
 _resident = [n for n, c in CASES.items() if not c["extra"].get("wide")]
 for _i, _n in enumerate(_resident):
     CASES[_n]["l0"] = "auto" if _i % 2 else "f32"
