@@ -141,6 +141,8 @@ class OracleChainBackend(OracleBackend):
         return cur, acc, llp, lpp, dict(loglik=ll, logprior=lp, sigma=sig, n_accepted=n_acc, n_passes=K, n_candidates=1)
 
 
+    _layer_sum = staticmethod(np.sum)      # what UpdateNormalNormalized divides a layer by (tests put wrong sums here)
+
     def run_chain_general(self, weights, draws, log_u, mask=None, indicators=None, feature_indicators=None, feature_means=None,
                           prior_ind1=0.5, has_indicator_prior=False, prior_kind=1, prior_scale=None, w_bound=np.inf, temperature=1.0,
                           lik_temp=1.0, cur_loglik=0.0, cur_logprior=0.0, cur_sigma=None, sigma=None, n_candidates=0, schedule=0,
@@ -176,7 +178,7 @@ class OracleChainBackend(OracleBackend):
                 for li in range(len(shapes)):
                     if (draws["layer_mask"][t] >> li) & 1:
                         lay = prop[offs[li]:offs[li + 1]].reshape(shapes[li])
-                        prop[offs[li]:offs[li + 1]] = (lay / np.sum(lay)).ravel()
+                        prop[offs[li]:offs[li + 1]] = (lay / self._layer_sum(lay)).ravel()
             if m is not None:
                 prop = prop * m
             ind_p, find_p = ind, find

@@ -475,57 +475,85 @@ def draw_general(p, rs, K, kind, ind_shape=None, t_star=None, plant=None):
 
 def slice_general(g, a, b):
     out = dict(g)
-    for key in ("idx", "val", "cnt", "layer_mask", "h_idx", "h_val", "h_fac", "h_cnt"):
+    for key in ("idx", "val", "cnt", "layer_mask", "h_idx", "h_val", "h_fac", "h_cnt", "find_use", "sigma_mult", "hastings"):
         if g.get(key) is not None:
             out[key] = g[key][a:b]
-    if "ind_ptr" in g:
-        ptr = g["ind_ptr"][a:b + 1]
-        out["ind_ptr"], out["ind_pos"] = ptr - ptr[0], g["ind_pos"][ptr[0]:ptr[-1]]
+    for ptr_key, pos_key in (("ind_ptr", "ind_pos"), ("find_ptr", "find_pos")):
+        if ptr_key in g:
+            ptr = g[ptr_key][a:b + 1]
+            out[ptr_key], out[pos_key] = ptr - ptr[0], g[pos_key][ptr[0]:ptr[-1]]
     return out
 
 
 def general_kwargs(p, b):
-    s = b["start"]
-    return dict(draws=b["draws"], log_u=b["log_u"], mask=None, indicators=s["ind"], prior_ind1=PRIOR_IND1, has_indicator_prior=s["ind"] is not None,
-                prior_kind=PRIOR_NORMAL, prior_scale=p["prior_scale"], w_bound=np.inf, temperature=1.0, lik_temp=1.0, cur_loglik=s["ll"],
-                cur_logprior=s["lp"])
+    """What HipContext.chain_run_general and OracleChainBackend.run_chain_general take for batch ``b``.  The chain's settings are
+    ``p["chain"]`` where the problem has one (tests/general_cases.py: prior, walls, tempering, a given sigma, fixed slopes) and
+    the normal prior at temperature 1 without walls where it has none; the sigma multipliers and their Hastings terms travel
+    with the draws; feature indicators and the current sigma with the state."""
+    s, c, g = b["start"], p.get("chain", {}), b["draws"]
+    kw = dict(draws=g, log_u=b["log_u"], mask=p["mask"], indicators=s["ind"], prior_ind1=c.get("prior_ind1", PRIOR_IND1),
+              has_indicator_prior=s["ind"] is not None, prior_kind=c.get("prior_kind", PRIOR_NORMAL), prior_scale=p["prior_scale"],
+              w_bound=c.get("w_bound", np.inf), temperature=c.get("temperature", 1.0), lik_temp=c.get("lik_temp", 1.0),
+              cur_loglik=s["ll"], cur_logprior=s["lp"])
+    if s.get("find") is not None:
+        kw.update(feature_indicators=s["find"], feature_means=p["feature_means"])
+    if s.get("sigma") is not None:
+        kw["cur_sigma"] = s["sigma"]
+    if c.get("sigma") is not None:
+        kw["sigma"] = c["sigma"]
+    if g.get("sigma_mult") is not None:
+        kw.update(sigma_mult=g["sigma_mult"], hastings=g["hastings"])
+    if c.get("fixed_slopes") is not None:
+        kw["fixed_slopes"] = c["fixed_slopes"]
+    return kw
 
 
 def _general_step(be, p, state, g, t, log_u):
     b = dict(start=state, draws=slice_general(g, t, t + 1), log_u=np.array([log_u]))
+    kw = general_kwargs(p, b)
     with np.errstate(over="ignore"):
-        return be.run_chain_general(state["w"], **general_kwargs(p, b))
+        return be.run_chain_general(state["w"], **kw), kw
 
 
-def plan_general(p, be, state, g, pattern):
+def state_after(p, out, res):
+    """The chain's state as the next batch's start: what run_chain_general returned (weights, indicators, feature indicators)
+    and its result dict."""
+    w, ind, find = out[0], out[1], out[2]
+    return dict(w=unpack(np.asarray(w), p["shapes"]), ll=res["loglik"], lp=res["logprior"], ind=ind, find=find, sigma=res["sigma"])
+
+
+def plan_general(p, be, state, g, pattern, observe=None):
     """plan_batch for the general chain: every iteration is proposed once on the stand-in with a bar nothing passes (its proposed
-    log values give the accept statistic) and, where the pattern accepts, once more with a bar everything passes."""
+    log values give the accept statistic) and, where the pattern accepts, once more with a bar everything passes.
+    ``observe(t, state)`` sees the state every iteration is proposed from."""
     import scipy.stats
     K = len(pattern)
     log_u, stat, margin = np.zeros(K), np.zeros(K), np.zeros(K)
     for t in range(K):
-        _, _, _, acc, llp, lpp, _ = _general_step(be, p, state, g, t, np.inf)
+        if observe is not None:
+            observe(t, state)
+        (_, _, _, acc, llp, lpp, _), kw = _general_step(be, p, state, g, t, np.inf)
         assert not acc[0]
-        h = 0.0
+        h = 0.0 if kw.get("hastings") is None else kw["hastings"][0]
         if g["kind"] == PROP_FIXED_NORMAL:
             n = g["h_cnt"][t]
             dd = np.sqrt(0.5 / g["h_fac"][t, :n])
             cur = pack(state["w"])
-            h = np.sum(scipy.stats.norm.logpdf(cur[g["h_idx"][t, :n]], 0, dd) - scipy.stats.norm.logpdf(g["h_val"][t, :n], 0, dd))
-        stat[t] = ((llp[0] + lpp[0]) - (state["ll"] + state["lp"])) * 1.0 + h
+            h += np.sum(scipy.stats.norm.logpdf(cur[g["h_idx"][t, :n]], 0, dd) - scipy.stats.norm.logpdf(g["h_val"][t, :n], 0, dd))
+        stat[t] = ((llp[0] + lpp[0]) - (state["ll"] + state["lp"])) * kw["temperature"] + h
         margin[t] = MARGIN_FACTOR * LL_BAR * max(1.0, abs(state["ll"]), abs(llp[0]))
         log_u[t] = stat[t] - margin[t] if pattern[t] else stat[t] + margin[t]
         if pattern[t]:
-            w, ind, _, acc, _, _, res = _general_step(be, p, state, g, t, -np.inf)
-            assert acc[0]
-            state = dict(w=unpack(w, p["shapes"]), ll=res["loglik"], lp=res["logprior"], ind=ind, sigma=None)
+            out, _ = _general_step(be, p, state, g, t, -np.inf)
+            assert out[3][0]
+            state = state_after(p, out, out[6])
     return log_u, stat, margin
 
 
 def run_standin_general(p, b, be):
     with np.errstate(over="ignore"):
-        w, ind, _, acc, llp, lpp, res = be.run_chain_general(b["start"]["w"], **general_kwargs(p, b))
-    return dict(w=np.array(w), ind=ind, acc=acc, llp=llp, lpp=lpp, ll=res["loglik"], lp=res["logprior"], sigma=None)
+        w, ind, find, acc, llp, lpp, res = be.run_chain_general(b["start"]["w"], **general_kwargs(p, b))
+    return dict(w=np.array(w), ind=ind, find=find, acc=acc, llp=llp, lpp=lpp, ll=res["loglik"], lp=res["logprior"], sigma=res["sigma"])
 
 
 @functools.lru_cache(maxsize=None)

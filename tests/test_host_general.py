@@ -15,7 +15,7 @@ from oracle_backend import OracleChainBackend, serve_from_oracle
 
 
 def build(update_function=bn.UpdateNormal, n_nodes=(6, 4), freq_indicator=0, feature_indicators=None, randomize_seed=False, w_bound=np.inf,
-          regression=False, unit_sums=False, **mcmc_kw):
+          regression=False, unit_sums=False, prior_f=1, use_bias_node=2, use_class_weights=0, mask_blocks=0, **mcmc_kw):
     if regression:
         dat = cases.regression_data(7, 300, 10, 2, 0)
         extra, out_kind = dict(estimation_mode="regression"), 1
@@ -25,10 +25,14 @@ def build(update_function=bn.UpdateNormal, n_nodes=(6, 4), freq_indicator=0, fea
     np.random.seed(1234)
     init = None
     if unit_sums:            # the normalising proposal keeps every layer's sum at 1: start there
-        init = [np.abs(w) / np.sum(np.abs(w)) for w in bn.init_weight_prm(list(n_nodes), 10, 3, bias_node=2)]
+        init = [np.abs(w) / np.sum(np.abs(w)) for w in bn.init_weight_prm(list(n_nodes), 10, 3, bias_node=use_bias_node)]
     with contextlib.redirect_stdout(io.StringIO()):
-        bnn = bn.npBNN(dat, n_nodes=list(n_nodes), use_bias_node=2, actFun=bn.ActFun(fun="tanh"), freq_indicator=freq_indicator,
-                       feature_indicators=feature_indicators, w_bound=w_bound, init_weights=init, **extra)
+        bnn = bn.npBNN(dat, n_nodes=list(n_nodes), use_bias_node=use_bias_node, actFun=bn.ActFun(fun="tanh"), freq_indicator=freq_indicator,
+                       feature_indicators=feature_indicators, w_bound=w_bound, init_weights=init, prior_f=prior_f,
+                       use_class_weights=use_class_weights, **extra)
+        if mask_blocks:          # a block-structured first layer (range_cases.block_mask)
+            import range_cases
+            bnn.apply_mask(range_cases.block_mask(bnn._w_layers, 10, mask_blocks))
     serve_from_oracle(lambda b: OracleChainBackend(b, out_kind))
     n_layers = bnn._n_layers
     mcmc = bn.MCMC(bnn, update_function=update_function, update_f=[0.1] * n_layers, update_ws=[0.02 if unit_sums else 0.05] * n_layers, randomize_seed=randomize_seed,
@@ -43,6 +47,11 @@ CASES = {
     "feature_indicators": dict(feature_indicators=True),
     "feature_and_weight_indicators": dict(n_nodes=(6, 5, 4), freq_indicator=0.3, feature_indicators=True, update_function=bn.UpdateFixedNormal),
     "regression_sigma_and_features": dict(regression=True, feature_indicators=True, estimate_error=True),
+    # the settings tests/general_cases.py takes the stand-in's word for
+    "cauchy_fixed_normal_in_walls": dict(update_function=bn.UpdateFixedNormal, w_bound=0.4, prior_f=2),
+    "laplace_normalized_block_mask": dict(update_function=bn.UpdateNormalNormalized, unit_sums=True, prior_f=3, mask_blocks=2),
+    "feature_indicators_without_bias": dict(feature_indicators=True, use_bias_node=0),
+    "class_weights_and_weight_indicators": dict(n_nodes=(6, 5, 4), freq_indicator=0.3, use_class_weights=1),
 }
 
 
