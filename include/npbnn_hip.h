@@ -193,13 +193,15 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
         * passes and accumulation in the same two slots and its own final kernel in NPBNN_INFO_SUPPORT_FINAL_NS; npbnn_predict_sets_lppd
         * does the same with NPBNN_INFO_LPPD_FINAL_NS (and leaves 0 in its three slots when it refuses a call before any launch), and
         * npbnn_predict_sets_uncertainty with NPBNN_INFO_UNCERTAINTY_FINAL_NS (likewise), and npbnn_predict_sets_convergence with
-        * NPBNN_INFO_CONVERGENCE_FINAL_NS (its diagnostic and summary kernels; likewise).  npbnn_predict_sets and npbnn_predict_sets_hpd
+        * NPBNN_INFO_CONVERGENCE_FINAL_NS (its diagnostic and summary kernels; likewise), and npbnn_predict_sets_calibration with
+        * NPBNN_INFO_CALIBRATION_FINAL_NS (likewise; a slot of its own after the options' and the replay's).  npbnn_predict_sets and npbnn_predict_sets_hpd
         * run the same replay, so after them NPBNN_INFO_SUMMARY_PASS_NS / _ACC_NS describe that call: its passes, and the copies to the
         * host (npbnn_predict_sets) or nothing (npbnn_predict_sets_hpd, whose groups write straight into its stack) */
        NPBNN_INFO_PERMUTE_NS = 14, NPBNN_INFO_SUMMARY_PASS_NS = 15, NPBNN_INFO_SUMMARY_ACC_NS = 16, NPBNN_INFO_SUMMARY_FINAL_NS = 17,
        NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19, NPBNN_INFO_UNCERTAINTY_FINAL_NS = 20,
        NPBNN_INFO_CONVERGENCE_FINAL_NS = 21,
-       NPBNN_INFO_REPLAY_PASSES = 22, NPBNN_INFO_REPLAY_MAX_GROUP = 23, NPBNN_INFO_L0_OPTION = 24 };
+       NPBNN_INFO_REPLAY_PASSES = 22, NPBNN_INFO_REPLAY_MAX_GROUP = 23, NPBNN_INFO_L0_OPTION = 24,
+       NPBNN_INFO_CALIBRATION_FINAL_NS = 25 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -360,6 +362,46 @@ int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, const double* 
  * prediction that is NaN. */
 int npbnn_predict_sets_uncertainty(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
                                    double* out_mean, double* out_total, double* out_aleatoric, double* out_epistemic, double* out_totals);
+
+/* Posterior calibration of the n_sets stored samples on the resident matrix `which`: whether the probabilities the posterior mean
+ * reports can be believed, against the labels (npbnn_set_labels_i64) or targets (npbnn_set_targets_f64) set on `which`.  The reference
+ * has no such function; the predictions are what the loop over RunPredict gives per stored sample (np_bnn/BNN_lib.py:245-256) under
+ * the output function of ctx's architecture (SoftMax, RegressTransform, RegressTransformError, np_bnn/BNN_lib.py:166-182), S = n_sets,
+ * float64 throughout, the sets folded in set order.  B = n_bins in 1..64.
+ *   NPBNN_OUT_SOFTMAX, m = (1/S) sum_s softmax(z_s) of a row's pre-output values z_s (accumulated as
+ *   npbnn_predict_sets_uncertainty accumulates it), C = out_dim:
+ *     out_pred [n_rows]    k*, the first argmax of m            out_point0 [n_rows]  confidence = m[k*]
+ *     out_point1 [n_rows]  brier = sum_k (m_k - [k == label])^2  out_point2 [n_rows]  nll = -log m[label]; +inf when m[label] is 0 (a
+ *                                                                                    value, not an error)
+ *     out_counts [2][B]    count, n_correct of the reliability table: the rows, and the rows with k* == label, per bin
+ *                          min(B - 1, floor(confidence B)) - a confidence of exactly 1 falls in the last bin
+ *     out_bin_sums [B]     sum_confidence: the sum of the confidences of a bin's rows
+ *     out_totals[3]        the sums over the rows of brier, nll and (k* == label)
+ *   NPBNN_OUT_IDENTITY (T = out_dim, mu_s = z_s, sigma_s = sigma_sets[s], required, every entry positive and finite) and
+ *   NPBNN_OUT_SOFTPLUS_HALF (out_dim = 2 T, mu_s = z_s[:T], sigma_s = logaddexp(0, z_s[T:]); sigma_sets must be NULL), y the targets
+ *   [n_rows][T] as the device keeps them (float32); levels[n_levels], n_levels in 0..16, each strictly inside (0, 1):
+ *     out_point0 [n_rows][T]  pit = (1/S) sum_s Phi((y - mu_s) / sigma_s), Phi(u) = 0.5 erfc(-u / sqrt 2): the probability integral
+ *                             transform under the posterior predictive mixture
+ *     out_point1 [n_rows][T]  mean = K + (1/S) sum_s (mu_s - K), K the first set's mu
+ *     out_point2 [n_rows][T]  sq_err = (y - mean)^2
+ *     out_counts [T][B + n_levels]  per target pit_hist[B], the rows per bin min(B - 1, floor(pit B)), then covered[n_levels], the
+ *                             rows with |pit - 0.5| <= level / 2 (the target lies inside the mixture's central interval of that level)
+ *     out_totals[2][T]        the sums over the rows of sq_err and of pit per target
+ *   out_pred and out_bin_sums must be NULL under regression; under NPBNN_OUT_SOFTMAX the levels are checked and play no part.
+ * Every pointwise output (out_point0..2, out_pred) may be NULL (it is then not copied from the device); out_counts and out_totals are
+ * required, and out_bin_sums under NPBNN_OUT_SOFTMAX.  The sets replay as in npbnn_predict_sets_uncertainty, the pre-output values left
+ * on the device in float32 and widened before any exp, log or erfc.  The integer tables are exact; every cross-row floating-point sum
+ * is made of per-workgroup float64 partials added in a fixed order: two calls return the same bits, however the sets are grouped.
+ * Before any evaluation: NPBNN_E_ARG for n_sets < 1, NULL W_sets or required outputs, `which` not 0 or 1, n_bins outside 1..64,
+ * n_levels outside 0..16, a level outside (0, 1), sigma_sets missing, non-positive or non-finite under NPBNN_OUT_IDENTITY or given
+ * under the other two kinds, an odd out_dim under NPBNN_OUT_SOFTPLUS_HALF, targets of another width than T, a label outside
+ * [0, out_dim), out_bin_sums or out_pred given under regression; NPBNN_E_STATE without npbnn_set_arch, without data on `which`, or
+ * without labels / targets on `which`.  NPBNN_E_ARG after the passes: a prediction that is NaN.  A call refused before any
+ * evaluation leaves 0 in its three timing slots (NPBNN_INFO_SUMMARY_PASS_NS, _ACC_NS, NPBNN_INFO_CALIBRATION_FINAL_NS). */
+int npbnn_predict_sets_calibration(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
+                                   const double* sigma_sets, int32_t n_bins, const double* levels, int32_t n_levels,
+                                   double* out_point0, double* out_point1, double* out_point2,
+                                   int64_t* out_pred, int64_t* out_counts, double* out_bin_sums, double* out_totals);
 
 /* Convergence diagnostics of the n_sets stored samples in function space: split R-hat and effective sample size of every (row, output)
  * of their predictions on the resident matrix `which`.  The reference leaves convergence to a trace viewer on the logged weights; for

@@ -36,6 +36,7 @@ from .pdp import get_feature_summary, get_pdp, make_pdp_features, pdp  # noqa: F
 from .hpd import calcHPD, get_posterior_hpd, posterior_hpd  # noqa: F401
 from .lppd import get_posterior_lppd, posterior_lppd  # noqa: F401
 from .uncertainty import get_posterior_uncertainty, posterior_uncertainty  # noqa: F401
+from .calibration import get_posterior_calibration, posterior_calibration  # noqa: F401
 from .convergence import get_posterior_convergence, posterior_convergence  # noqa: F401
 from . import comm  # noqa: F401
 

@@ -38,6 +38,7 @@ INFO_UNCERTAINTY_FINAL_NS = 20
 INFO_CONVERGENCE_FINAL_NS = 21
 INFO_REPLAY_PASSES, INFO_REPLAY_MAX_GROUP = 22, 23
 INFO_L0_OPTION = 24
+INFO_CALIBRATION_FINAL_NS = 25
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
 E_STATE = -2
@@ -155,6 +156,8 @@ SIGNATURES = {
                                              C.POINTER(C.c_uint8)]),
     "npbnn_predict_sets_lppd": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
     "npbnn_predict_sets_uncertainty": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, _DP, _DP, _DP, _DP, _DP]),
+    "npbnn_predict_sets_calibration": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, _DP, C.c_int32, _DP, C.c_int32, _DP, _DP, _DP,
+                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64), _DP, _DP]),
     "npbnn_predict_sets_convergence": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
     "npbnn_time_eval": (C.c_int, [_P, _DP, C.c_int, _DP, _DP]),
     "npbnn_time_pass": (C.c_int, [_P, _DP, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),

@@ -498,6 +498,67 @@ class HipContext:
         return dict(mean=point[0], total_var=point[1], aleatoric_var=point[2], epistemic_var=point[3], mean_avg=avg[0],
                     total_var_avg=avg[1] if sigma else None, aleatoric_var_avg=avg[2] if sigma else None, epistemic_var_avg=avg[3])
 
+    def predict_sets_calibration(self, weight_sets, n_bins=15, levels=(0.5, 0.8, 0.9, 0.95), sigma_sets=None, act_prm_sets=None, which=capi.TRAIN,
+                                 pointwise=True):
+        """Calibration of several weight sets' mean prediction on the resident matrix, against the labels or targets set on it
+        (npbnn_predict_sets_calibration); the kind follows the architecture's output function.  Softmax: a dict with the reliability
+        table ``count``, ``sum_confidence``, ``n_correct`` [n_bins], the scores ``accuracy``, ``brier``, ``nll``, ``ece``, ``mce``
+        and the pointwise ``confidence``, ``predicted_class``, ``brier_i``, ``nll_i`` [n_rows].  Regression (T targets: n_out under
+        OUT_IDENTITY with ``sigma_sets`` [n_sets, T] or [n_sets], n_out / 2 under OUT_SOFTPLUS_HALF): ``levels``, ``pit_hist``
+        [T, n_bins], ``covered`` [T, L], ``rmse``, ``mean_pit`` [T], ``coverage`` [T, L], ``coverage_error`` [T] (None without
+        levels) and the pointwise ``pit``, ``mean``, ``sq_err`` [n_rows, T].  ``npbnn_amd.calibration`` has the definitions; the
+        scores come from the tables through its ``scores_from_table``.  Without ``pointwise`` every [n_rows, ...] array is None and
+        is not copied from the device.  The sets replay as in ``predict_sets_uncertainty``; the predictions never leave the device."""
+        from .calibration import check_bins_and_levels, scores_from_table, sigma_matrix
+        who = "predict_sets_calibration"
+        n_bins, lv = check_bins_and_levels(n_bins, levels, who)
+        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
+            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
+        packed = capi.as_f64(packed)
+        n_sets, n_rows, n_out, kind = packed.shape[0], self.n_rows[which], self.n_out, self.arch.out_kind
+        if n_sets < 1:
+            raise ValueError("%s: no weight sets" % who)
+        if n_rows < 1:
+            raise ValueError("%s: the matrix has no rows" % who)
+        if kind == capi.OUT_SOFTPLUS_HALF and n_out % 2:
+            raise ValueError("%s: OUT_SOFTPLUS_HALF splits the outputs into means and sigmas, and %d is odd" % (who, n_out))
+        softmax = kind == capi.OUT_SOFTMAX
+        t = 1 if softmax else (n_out // 2 if kind == capi.OUT_SOFTPLUS_HALF else n_out)
+        sig = None
+        if kind == capi.OUT_IDENTITY:
+            sig = capi.as_f64(sigma_matrix(sigma_sets, n_sets, t, who))
+        elif sigma_sets is not None:
+            raise ValueError("%s: sigma_sets goes with OUT_IDENTITY only" % who)
+        ap = None
+        if act_prm_sets is not None and self.arch.n_layers > 1:
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+            if ap.shape[0] != n_sets:
+                raise ValueError("%s: %d slope vectors for %d weight sets" % (who, ap.shape[0], n_sets))
+        if softmax:
+            lv = lv[:0]                                 # (the levels belong to regression)
+        point = [np.empty((n_rows,) if softmax else (n_rows, t), dtype=np.float64) for _ in range(3)] if pointwise else [None] * 3
+        pred = np.empty(n_rows, dtype=np.int64) if pointwise and softmax else None
+        counts = np.zeros((2, n_bins) if softmax else (t, n_bins + len(lv)), dtype=np.int64)
+        bin_sums = np.zeros(n_bins, dtype=np.float64) if softmax else None
+        totals = np.zeros(3 if softmax else (2, t), dtype=np.float64)
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._lib.npbnn_predict_sets_calibration(
+            self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which, capi.dptr(sig), n_bins, capi.dptr(lv) if len(lv) else None, len(lv),
+            capi.dptr(point[0]), capi.dptr(point[1]), capi.dptr(point[2]), None if pred is None else pred.ctypes.data_as(i64),
+            counts.ctypes.data_as(i64), capi.dptr(bin_sums), capi.dptr(totals)))
+        res = dict(n_samples=int(n_sets), n_rows=int(n_rows), n_bins=n_bins)
+        if softmax:
+            table = dict(count=counts[0].copy(), sum_confidence=bin_sums, n_correct=counts[1].copy())
+            res.update(table)
+            res.update(scores_from_table(dict(table, brier_sum=totals[0], nll_sum=totals[1]), n_rows))
+            res.update(confidence=point[0], predicted_class=pred, brier_i=point[1], nll_i=point[2])
+            return res
+        table = dict(levels=lv, pit_hist=counts[:, :n_bins].copy(), covered=counts[:, n_bins:].copy())
+        res.update(table)
+        res.update(scores_from_table(dict(table, sq_err_sum=totals[0], pit_sum=totals[1]), n_rows))
+        res.update(pit=point[0], mean=point[1], sq_err=point[2])
+        return res
+
     def predict_sets_convergence(self, weight_sets, n_chains=1, rhat_threshold=1.01, act_prm_sets=None, which=capi.TRAIN, apply_out_fn=True,
                                  pointwise=True):
         """Split R-hat and effective sample size of several weight sets' predictions on the resident matrix, per (row, output)

@@ -1,5 +1,5 @@
 // What the entries that run stored weight sets over a resident table share (npbnn_capi.hip: npbnn_predict_sets; npbnn_hpd.hip;
-// npbnn_importance.hip: npbnn_predict_sets_summary; npbnn_support.hip; npbnn_lppd.hip; npbnn_uncertainty.hip; npbnn_convergence.hip;
+// npbnn_importance.hip: npbnn_predict_sets_summary; npbnn_support.hip; npbnn_lppd.hip; npbnn_uncertainty.hip; npbnn_calibration.hip; npbnn_convergence.hip;
 // npbnn_pdp.hip, route 2):
 // the replay of the sets group after group (replay_sets, npbnn_sets.hip) and the host helpers it is built from, the flag word's bits,
 // the launch shape of the streaming kernels, the HIP-event timer behind NPBNN_FI_TIMING, the fixed-order workgroup sum and the host

@@ -163,6 +163,30 @@ class _SamplePredictor:
                 res["total_var"] = res["epistemic_var"] + aleatoric
         return res
 
+    def calibration(self, features, labels, kind, n_bins=15, levels=(0.5, 0.8, 0.9, 0.95), sigma_sets=None, pointwise=True):
+        """``posterior_calibration``'s dict for the stored samples on ``features`` against ``labels`` - class indices
+        (``"classification"``) or targets (``"regression"`` with ``sigma_sets`` per sample, ``"regression-error"``); the stack
+        stays on the device (npbnn_predict_sets_calibration), and without ``pointwise`` the [N, ...] arrays are None.  A custom
+        output callable has no device kind: its stack is built on the host and goes through ``posterior_calibration``."""
+        from .calibration import CLASS_POINT_KEYS, KINDS, REGRESSION_POINT_KEYS, posterior_calibration
+        if kind not in KINDS:
+            raise ValueError("calibration: kind %r; one of %s" % (kind, ", ".join(KINDS)))
+        if self._kind is None and self._out_fn is not None:
+            res = posterior_calibration(self.predict(features), labels, kind, n_bins, levels, sigma_sets)
+            return res if pointwise else {k: (None if k in CLASS_POINT_KEYS + REGRESSION_POINT_KEYS else v) for k, v in res.items()}
+        want = {"classification": capi.OUT_SOFTMAX, "regression": capi.OUT_IDENTITY, "regression-error": capi.OUT_SOFTPLUS_HALF}[kind]
+        if (capi.OUT_IDENTITY if self._kind is None else self._kind) != want:
+            raise ValueError("calibration: kind %r does not go with the model's output function" % (kind,))
+        if kind == "regression" and sigma_sets is None:
+            raise ValueError("calibration: kind \"regression\" needs sigma_sets (a sigma per sample and target)")
+        ctx = self._load(features)
+        if kind == "classification":
+            ctx.set_labels(labels)
+        else:
+            ctx.set_targets(labels)
+        return ctx.predict_sets_calibration(self._packed, n_bins=n_bins, levels=levels, sigma_sets=sigma_sets, act_prm_sets=self._slopes,
+                                            pointwise=pointwise)
+
     def convergence(self, features, n_chains, rhat_threshold=1.01, pointwise=True):
         """``posterior_convergence``'s dict for the stored samples - ``n_chains`` chains of equal length, chain-major - on
         ``features``, predictions post-output; the stack stays on the device (npbnn_predict_sets_convergence), and without
