@@ -12,6 +12,7 @@ from time import perf_counter as _now
 import numpy as np
 
 from . import _capi as capi
+from .stored import sigma_matrix
 
 
 _PACKED_VIEWS = {}      # id(first layer) -> (the layer arrays, the packed vector they are consecutive views of); strong references: ids stay valid
@@ -47,6 +48,15 @@ def pack_weights(weights):
             _PACKED_VIEWS[id(first)] = (tuple(weights), base)
             return base.copy()
     return np.concatenate([np.ascontiguousarray(w, dtype=np.float64).ravel() for w in weights])
+
+
+def one_vector(x, copy=False):
+    """One weight vector or mask as the C ABI takes it: a list of per-layer matrices is packed (a fresh array), anything else is
+    the packed float64 vector itself - copied when ``copy``, for the entries that write the new state into it."""
+    if isinstance(x, (list, tuple)):
+        return pack_weights(x)
+    x = capi.as_f64(x)
+    return x.copy() if copy else x
 
 
 _NO_SIGMA = np.zeros(0)
@@ -224,7 +234,7 @@ class HipContext:
         """Declare the 0/1 mask of the network (list of per-layer matrices, a packed vector, or None for dense): blocks of the
         first layer in which it is all zero cost neither device memory nor matrix-core work (npbnn_set_layer_mask).  Weights
         passed afterwards must be zero where the mask is."""
-        m = None if mask is None else (pack_weights(mask) if isinstance(mask, (list, tuple)) else capi.as_f64(mask))
+        m = None if mask is None else one_vector(mask)
         self._chk(self._lib.npbnn_set_layer_mask(self._ctx, capi.dptr(m)))
 
     def set_arch_from_weights(self, weights, in_dim, act_kind, out_kind, lik_kind, n_targets=0, final_activation=False):
@@ -246,7 +256,7 @@ class HipContext:
     # -- hot path ---------------------------------------------------------------------
     def eval(self, weights, act_prm=None, col_override=None, lik_temp=1.0, sigma=None, which=capi.TRAIN,
              want_confusion=False):
-        w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights)
+        w = one_vector(weights)
         ap = None if act_prm is None else capi.as_f64(act_prm)
         co = None if col_override is None else capi.as_f64(col_override)
         sg = None if sigma is None else capi.as_f64(np.broadcast_to(sigma, (self.arch.n_targets,)))
@@ -263,7 +273,7 @@ class HipContext:
                     sum_r2=np.array(out.sum_r2[:k]), n_rows=out.n_rows, confusion=conf)
 
     def predict(self, weights, act_prm=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
-        w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights)
+        w = one_vector(weights)
         ap = None if act_prm is None else capi.as_f64(act_prm)
         co = None if col_override is None else capi.as_f64(col_override)
         y = np.empty((self.n_rows[which], self.n_out), dtype=np.float64)
@@ -271,16 +281,30 @@ class HipContext:
                                           1 if apply_out_fn else 0, capi.dptr(y)))
         return y
 
+    def _pack_sets(self, weight_sets, act_prm_sets, who):
+        """What every stored-sample entry hands the library: ``(packed, ap, n_sets)``.  ``packed`` [n_sets, n_w] float64 is
+        ``weight_sets`` itself when that is such a matrix, else its items - per-layer lists or packed vectors - stacked; ``ap``
+        [n_sets, n_layers - 1] float64 holds the hidden layers' slopes per set, or is None (no ``act_prm_sets``, or no hidden
+        layer).  ``ValueError`` in ``who``'s name for no sets and for a number of slope vectors other than the number of sets:
+        the library reads one per set."""
+        if len(weight_sets) == 0:
+            raise ValueError("%s: no weight sets" % who)
+        if not (isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2):
+            weight_sets = np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
+        packed = capi.as_f64(weight_sets)
+        n_sets, n_hidden = packed.shape[0], self.arch.n_layers - 1
+        ap = None
+        if act_prm_sets is not None and n_hidden > 0:
+            if len(act_prm_sets) != n_sets:
+                raise ValueError("%s: %d slope vectors for %d weight sets" % (who, len(act_prm_sets), n_sets))
+            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[:n_hidden] for a in act_prm_sets]))
+        return packed, ap, n_sets
+
     def predict_sets(self, weight_sets, act_prm_sets=None, which=capi.TRAIN, apply_out_fn=True):
         """Predictions of several weight sets on the resident matrix (npbnn_predict_sets): [n_sets, n_rows, n_out].
-        ``weight_sets``: list of per-layer lists (or packed vectors); ``act_prm_sets``: per set the activation slopes
-        of the hidden layers, or None."""
-        packed = np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
-        packed = capi.as_f64(packed)
-        n_sets = packed.shape[0]
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        ``weight_sets``: list of per-layer lists (or packed vectors), or the packed matrix; ``act_prm_sets``: per set the
+        activation slopes of the hidden layers, or None."""
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_sets")
         out = np.empty((n_sets, self.n_rows[which], self.n_out), dtype=np.float64)
         self._chk(self._lib.npbnn_predict_sets(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which,
                                                1 if apply_out_fn else 0, capi.dptr(out)))
@@ -290,12 +314,7 @@ class HipContext:
         """Posterior mean and HPD interval of several weight sets' predictions on the resident matrix (npbnn_predict_sets_hpd):
         ``(mean, lower, upper)``, each [n_rows, n_out].  The sets replay as in ``predict_sets`` into a float32 stack that stays
         on the device; the bounds equal calcHPD's on the float64 array ``predict_sets`` returns."""
-        packed = capi.as_f64(np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel()
-                                       for w in weight_sets]))
-        n_sets = packed.shape[0]
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_sets_hpd")
         shape = (self.n_rows[which], self.n_out)
         mean, lo, hi = np.empty(shape), np.empty(shape), np.empty(shape)
         self._chk(self._lib.npbnn_predict_sets_hpd(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which,
@@ -332,13 +351,7 @@ class HipContext:
             raise ValueError("predict_sets_summary: mode must be 0 (votes) or 1 (mean)")
         if labels is None and not want_summary:
             raise ValueError("predict_sets_summary: nothing asked for (no labels and want_summary off)")
-        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
-            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
-        packed = capi.as_f64(packed)
-        n_sets = packed.shape[0]
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_sets_summary")
         lab = conf = summary = None
         if labels is not None:
             lab = np.ascontiguousarray(labels, dtype=np.int64).ravel()
@@ -368,13 +381,8 @@ class HipContext:
             raise ValueError("predict_sets_support: mode must be 0 (votes) or 1 (mean)")
         if labels is None:
             raise ValueError("predict_sets_support: labels are required")
-        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
-            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
-        packed = capi.as_f64(packed)
-        n_sets, n_rows, c = packed.shape[0], self.n_rows[which], self.n_out
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_sets_support")
+        n_rows, c = self.n_rows[which], self.n_out
         lab = np.ascontiguousarray(labels, dtype=np.int64).ravel()
         if lab.shape[0] != n_rows:
             raise ValueError("predict_sets_support: %d labels but the matrix has %d rows" % (lab.shape[0], n_rows))
@@ -416,33 +424,17 @@ class HipContext:
         if lik_kind not in (capi.LIK_CATEGORICAL, capi.LIK_GAUSS):
             raise ValueError("predict_sets_lppd: lik_kind must be LIK_CATEGORICAL or LIK_GAUSS (predicted-sigma regression and the "
                              "count likelihoods are out of scope), got %r" % (lik_kind,))
-        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
-            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
-        packed = capi.as_f64(packed)
-        n_sets, n_rows = packed.shape[0], self.n_rows[which]
-        if n_sets < 1:
-            raise ValueError("predict_sets_lppd: no weight sets")
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_sets_lppd")
+        n_rows = self.n_rows[which]
         if n_rows < 1:
             raise ValueError("predict_sets_lppd: the matrix has no rows")
         sig = None
         if lik_kind == capi.LIK_GAUSS:
             if sigma_sets is None:
                 raise ValueError("predict_sets_lppd: the Gaussian likelihood needs sigma_sets")
-            sig = np.asarray(sigma_sets, dtype=np.float64)
-            if sig.ndim == 1:
-                sig = sig.reshape(-1, 1)
-            if sig.ndim != 2 or sig.shape[0] != n_sets or sig.shape[1] not in (1, self.n_out):
-                raise ValueError("predict_sets_lppd: sigma_sets is %s, expected (%d, %d)" % (sig.shape, n_sets, self.n_out))
-            sig = capi.as_f64(np.broadcast_to(sig, (n_sets, self.n_out)))
-            if not (np.all(np.isfinite(sig)) and np.all(sig > 0)):
-                raise ValueError("predict_sets_lppd: every sigma must be positive and finite")
+            sig = sigma_matrix(sigma_sets, n_sets, self.n_out, "predict_sets_lppd")
         elif sigma_sets is not None:
             raise ValueError("predict_sets_lppd: sigma_sets goes with LIK_GAUSS only")
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
-            if ap.shape[0] != n_sets:
-                raise ValueError("predict_sets_lppd: %d slope vectors for %d weight sets" % (ap.shape[0], n_sets))
         point = [np.empty(n_rows, dtype=np.float64) for _ in range(3)] if pointwise else [None] * 3
         trace = np.empty(n_sets, dtype=np.float64)
         totals = np.zeros(3, dtype=np.float64)
@@ -462,21 +454,12 @@ class HipContext:
         OUT_IDENTITY predicts no sigma, and its ``aleatoric_var*`` and ``total_var*`` are None (the caller adds its own).  Without
         ``pointwise`` every [n_rows, ...] array is None and is not copied from the device.  The sets replay as in
         ``predict_sets_lppd``; the predictions never leave the device."""
-        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
-            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
-        packed = capi.as_f64(packed)
-        n_sets, n_rows, n_out, kind = packed.shape[0], self.n_rows[which], self.n_out, self.arch.out_kind
-        if n_sets < 1:
-            raise ValueError("predict_sets_uncertainty: no weight sets")
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_sets_uncertainty")
+        n_rows, n_out, kind = self.n_rows[which], self.n_out, self.arch.out_kind
         if n_rows < 1:
             raise ValueError("predict_sets_uncertainty: the matrix has no rows")
         if kind == capi.OUT_SOFTPLUS_HALF and n_out % 2:
             raise ValueError("predict_sets_uncertainty: OUT_SOFTPLUS_HALF splits the outputs into means and sigmas, and %d is odd" % n_out)
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
-            if ap.shape[0] != n_sets:
-                raise ValueError("predict_sets_uncertainty: %d slope vectors for %d weight sets" % (ap.shape[0], n_sets))
         softmax, sigma = kind == capi.OUT_SOFTMAX, kind == capi.OUT_SOFTPLUS_HALF
         t = 1 if softmax else (n_out // 2 if sigma else n_out)
         col = (n_rows,) if softmax else (n_rows, t)
@@ -509,15 +492,11 @@ class HipContext:
         levels) and the pointwise ``pit``, ``mean``, ``sq_err`` [n_rows, T].  ``npbnn_amd.calibration`` has the definitions; the
         scores come from the tables through its ``scores_from_table``.  Without ``pointwise`` every [n_rows, ...] array is None and
         is not copied from the device.  The sets replay as in ``predict_sets_uncertainty``; the predictions never leave the device."""
-        from .calibration import check_bins_and_levels, scores_from_table, sigma_matrix
+        from .calibration import check_bins_and_levels, scores_from_table
         who = "predict_sets_calibration"
         n_bins, lv = check_bins_and_levels(n_bins, levels, who)
-        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
-            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
-        packed = capi.as_f64(packed)
-        n_sets, n_rows, n_out, kind = packed.shape[0], self.n_rows[which], self.n_out, self.arch.out_kind
-        if n_sets < 1:
-            raise ValueError("%s: no weight sets" % who)
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, who)
+        n_rows, n_out, kind = self.n_rows[which], self.n_out, self.arch.out_kind
         if n_rows < 1:
             raise ValueError("%s: the matrix has no rows" % who)
         if kind == capi.OUT_SOFTPLUS_HALF and n_out % 2:
@@ -526,14 +505,9 @@ class HipContext:
         t = 1 if softmax else (n_out // 2 if kind == capi.OUT_SOFTPLUS_HALF else n_out)
         sig = None
         if kind == capi.OUT_IDENTITY:
-            sig = capi.as_f64(sigma_matrix(sigma_sets, n_sets, t, who))
+            sig = sigma_matrix(sigma_sets, n_sets, t, who)
         elif sigma_sets is not None:
             raise ValueError("%s: sigma_sets goes with OUT_IDENTITY only" % who)
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
-            if ap.shape[0] != n_sets:
-                raise ValueError("%s: %d slope vectors for %d weight sets" % (who, ap.shape[0], n_sets))
         if softmax:
             lv = lv[:0]                                 # (the levels belong to regression)
         point = [np.empty((n_rows,) if softmax else (n_rows, t), dtype=np.float64) for _ in range(3)] if pointwise else [None] * 3
@@ -567,18 +541,11 @@ class HipContext:
         replay as in ``predict_sets_hpd`` into a float32 stack that stays on the device; the results are the definition's on the
         float64 array ``predict_sets`` returns."""
         from .convergence import check_shape, result_dict
-        packed = weight_sets if isinstance(weight_sets, np.ndarray) and weight_sets.ndim == 2 else \
-            np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel() for w in weight_sets])
-        packed = capi.as_f64(packed)
-        n_sets, n_rows, n_out = packed.shape[0], self.n_rows[which], self.n_out
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_sets_convergence")
+        n_rows, n_out = self.n_rows[which], self.n_out
         n_draws = check_shape("predict_sets_convergence", n_sets, n_chains)
         if n_rows < 1:
             raise ValueError("predict_sets_convergence: the matrix has no rows")
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
-            if ap.shape[0] != n_sets:
-                raise ValueError("predict_sets_convergence: %d slope vectors for %d weight sets" % (ap.shape[0], n_sets))
         rhat = np.empty((n_rows, n_out)) if pointwise else None
         ess = np.empty((n_rows, n_out)) if pointwise else None
         summary = np.zeros((n_out, 4))
@@ -591,12 +558,7 @@ class HipContext:
         """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
         prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]
         and then the columns ``col_override`` gives (NaN = none) to its constants.  NPBNN_INFO_PDP_ROUTE: the route taken."""
-        packed = capi.as_f64(np.stack([pack_weights(w) if isinstance(w, (list, tuple)) else capi.as_f64(w).ravel()
-                                       for w in weight_sets]))
-        n_sets = packed.shape[0]
-        ap = None
-        if act_prm_sets is not None and self.arch.n_layers > 1:
-            ap = capi.as_f64(np.stack([np.asarray(a, dtype=np.float64).ravel()[: self.arch.n_layers - 1] for a in act_prm_sets]))
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_pdp")
         cols = np.ascontiguousarray(focal, dtype=np.int32).ravel()
         g = np.asarray(grid, dtype=np.float64)
         # (no focal column: the grid has rows and no entries, so its first dimension alone says how many points there are)
@@ -609,14 +571,14 @@ class HipContext:
         return out
 
     def time_eval(self, weights, iters=20):
-        w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights)
+        w = one_vector(weights)
         a, b = C.c_double(0), C.c_double(0)
         self._chk(self._lib.npbnn_time_eval(self._ctx, capi.dptr(w), int(iters), C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def time_pass(self, weights, n_candidates=0, iters=20):
         """Mean duration (ms) of the evaluation kernel of a speculative chain pass and the candidates it evaluates."""
-        w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights)
+        w = one_vector(weights)
         ms, used = C.c_double(0), C.c_int(0)
         self._chk(self._lib.npbnn_time_pass(self._ctx, capi.dptr(w), int(n_candidates), int(iters), C.byref(ms), C.byref(used)))
         return ms.value, used.value
@@ -624,7 +586,7 @@ class HipContext:
     def time_wide(self, weights, iters=20):
         """Weight-streamed path: mean duration (ms) of the first layer's product alone and of a whole pass, and the product's
         geometry (rows, outputs of a workgroup's block, K-slices, workgroups)."""
-        w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights)
+        w = one_vector(weights)
         ms0, ms = C.c_double(0), C.c_double(0)
         info = (C.c_int * 4)()
         self._chk(self._lib.npbnn_time_wide(self._ctx, capi.dptr(w), int(iters), C.byref(ms0), C.byref(ms), info))
@@ -778,7 +740,7 @@ class HipContext:
         proposed logLik, proposed logPrior, result dict)."""
         i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)       # noqa: E731
         ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))        # noqa: E731
-        w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights).copy()
+        w = one_vector(weights, copy=True)
         idx, cnt = i32(draws["idx"]), i32(draws["cnt"])
         val = capi.as_f64(draws["val"])
         K, M = idx.shape
@@ -808,7 +770,7 @@ class HipContext:
             fptr, fpos, fuse = i32(draws["find_ptr"]), i32(draws["find_pos"] if len(draws["find_pos"]) else np.zeros(1)), i32(draws["find_use"])
             g.find_inout, g.feature_means, g.find_ptr, g.find_pos, g.find_use = capi.dptr(find), capi.dptr(means), ip(fptr), ip(fpos), ip(fuse)
             keep += [means, fptr, fpos, fuse]
-        m = None if mask is None else (pack_weights(mask) if isinstance(mask, (list, tuple)) else capi.as_f64(mask))
+        m = None if mask is None else one_vector(mask)
         log_u = capi.as_f64(log_u)
         acc = np.empty(K, dtype=np.uint8)
         llp, lpp = np.empty(K), np.empty(K)
@@ -861,6 +823,53 @@ class FastBatch:
         return rc
 
 
+def fill_chain_job(J, q, job, K, span, chain_id, force_f32=0, n_seg=0, want_cold_w=False):
+    """Fill ``J`` (a capi.ChainJob) from the job dict ``job`` (see :func:`chains_run_exchange`), number ``q`` of its group, for ``K``
+    iterations - ``span`` says how the caller counts them, for the error about a wrong number of rows.  ``n_seg`` > 0 adds the
+    per-exchange outputs ``state`` [n_seg, XSTATE_DOUBLES] and, with ``want_cold_w``, ``cold_w`` [n_seg, n_w].  Returns (the arrays
+    and structs ``J`` points at - keep them until the call has returned -, the job's output dict)."""
+    ctx = job["ctx"]
+    w = one_vector(job["weights"], copy=True)
+    idx, cnt = job["idx"], job["cnt"]
+    if idx.shape[0] != K or len(cnt) != K:
+        raise ValueError("job %d: %d rows of draws for %s iterations" % (q, idx.shape[0], span))
+    if idx.dtype != np.int32 or not idx.flags.c_contiguous:
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+    if cnt.dtype != np.int32 or not cnt.flags.c_contiguous:
+        cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+    delta, log_u = capi.as_f64(job["delta"]), capi.as_f64(job["log_u"])
+    mask = job.get("mask")
+    m = None if mask is None else one_vector(mask)
+    cfg, res = capi.ChainCfg(), capi.ChainResult()
+    ctx._fill_chain_cfg(cfg, **job["cfg"])
+    cfg.force_f32 = force_f32
+    acc = np.zeros(K, dtype=np.uint8)
+    llp, lpp = np.zeros(K), np.zeros(K)
+    i32p = C.POINTER(C.c_int32)
+    J.ctx = ctx._ctx
+    J.cfg = C.pointer(cfg)
+    J.W_inout = capi.dptr(w)
+    J.mask_packed = capi.dptr(m)
+    J.M = idx.shape[1]
+    J.chain_id = int(chain_id)
+    J.idx = idx.ctypes.data_as(i32p)
+    J.delta = capi.dptr(delta)
+    J.cnt = cnt.ctypes.data_as(i32p)
+    J.log_u = capi.dptr(log_u)
+    J.out_accepted = acc.ctypes.data_as(C.POINTER(C.c_uint8))
+    J.out_loglik_prop = capi.dptr(llp)
+    J.out_logprior_prop = capi.dptr(lpp)
+    J.result = C.pointer(res)
+    out = dict(w=w, accepted=acc, loglik_prop=llp, logprior_prop=lpp, _res=res, _ctx=ctx)
+    if n_seg:
+        state = np.zeros((n_seg, capi.XSTATE_DOUBLES))
+        cold = np.zeros((n_seg, w.size)) if want_cold_w else None
+        J.out_state = capi.dptr(state)
+        J.out_cold_w = capi.dptr(cold)
+        out.update(state=state, cold_w=cold)
+    return (w, idx, cnt, delta, log_u, m, cfg, res), out
+
+
 def chains_run_exchange(jobs, n_chains, seg_len, n_seg, swap_j, swap_k, swap_logu, comm=None, launch_slack=1.25,
                         want_cold_w=True):
     """Several chains advance ``n_seg`` swap intervals of ``seg_len`` iterations with the temperature swaps done on the GPU
@@ -879,44 +888,9 @@ def chains_run_exchange(jobs, n_chains, seg_len, n_seg, swap_j, swap_k, swap_log
     keep, outs = [], []
     i32p = C.POINTER(C.c_int32)
     for q, job in enumerate(jobs):
-        ctx = job["ctx"]
-        weights = job["weights"]
-        w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights).copy()
-        idx, cnt = job["idx"], job["cnt"]
-        if idx.shape[0] != K or len(cnt) != K:
-            raise ValueError("job %d: %d rows of draws for %d x %d iterations" % (q, idx.shape[0], n_seg, seg_len))
-        if idx.dtype != np.int32 or not idx.flags.c_contiguous:
-            idx = np.ascontiguousarray(idx, dtype=np.int32)
-        if cnt.dtype != np.int32 or not cnt.flags.c_contiguous:
-            cnt = np.ascontiguousarray(cnt, dtype=np.int32)
-        delta, log_u = capi.as_f64(job["delta"]), capi.as_f64(job["log_u"])
-        mask = job.get("mask")
-        m = None if mask is None else (pack_weights(mask) if isinstance(mask, (list, tuple)) else capi.as_f64(mask))
-        cfg, res = capi.ChainCfg(), capi.ChainResult()
-        ctx._fill_chain_cfg(cfg, **job["cfg"])
-        acc = np.zeros(K, dtype=np.uint8)
-        llp, lpp = np.zeros(K), np.zeros(K)
-        state = np.zeros((n_seg, capi.XSTATE_DOUBLES))
-        cold = np.zeros((n_seg, w.size)) if want_cold_w else None
-        J = arr[q]
-        J.ctx = ctx._ctx
-        J.cfg = C.pointer(cfg)
-        J.W_inout = capi.dptr(w)
-        J.mask_packed = capi.dptr(m)
-        J.M = idx.shape[1]
-        J.chain_id = int(job["chain_id"])
-        J.idx = idx.ctypes.data_as(i32p)
-        J.delta = capi.dptr(delta)
-        J.cnt = cnt.ctypes.data_as(i32p)
-        J.log_u = capi.dptr(log_u)
-        J.out_accepted = acc.ctypes.data_as(C.POINTER(C.c_uint8))
-        J.out_loglik_prop = capi.dptr(llp)
-        J.out_logprior_prop = capi.dptr(lpp)
-        J.out_state = capi.dptr(state)
-        J.out_cold_w = capi.dptr(cold)
-        J.result = C.pointer(res)
-        keep.append((w, idx, cnt, delta, log_u, m, cfg, res))
-        outs.append(dict(w=w, accepted=acc, loglik_prop=llp, logprior_prop=lpp, state=state, cold_w=cold, _res=res, _ctx=ctx))
+        kept, out = fill_chain_job(arr[q], q, job, K, "%d x %d" % (n_seg, seg_len), job["chain_id"], n_seg=n_seg, want_cold_w=want_cold_w)
+        keep.append(kept)
+        outs.append(out)
     sj = np.ascontiguousarray(swap_j, dtype=np.int32)
     sk = np.ascontiguousarray(swap_k, dtype=np.int32)
     su = capi.as_f64(swap_logu)
@@ -938,46 +912,13 @@ def chains_run_batched(jobs, K):
     group through once more on the float32 layer-0 path."""
     K = int(K)
     lib = jobs[0]["ctx"]._lib
-    i32p = C.POINTER(C.c_int32)
     for attempt in (0, 1):
         arr = (capi.ChainJob * len(jobs))()
         keep, outs = [], []
         for q, job in enumerate(jobs):
-            ctx = job["ctx"]
-            weights = job["weights"]
-            w = pack_weights(weights) if isinstance(weights, (list, tuple)) else capi.as_f64(weights).copy()
-            idx, cnt = job["idx"], job["cnt"]
-            if idx.shape[0] != K or len(cnt) != K:
-                raise ValueError("job %d: %d rows of draws for %d iterations" % (q, idx.shape[0], K))
-            if idx.dtype != np.int32 or not idx.flags.c_contiguous:
-                idx = np.ascontiguousarray(idx, dtype=np.int32)
-            if cnt.dtype != np.int32 or not cnt.flags.c_contiguous:
-                cnt = np.ascontiguousarray(cnt, dtype=np.int32)
-            delta, log_u = capi.as_f64(job["delta"]), capi.as_f64(job["log_u"])
-            mask = job.get("mask")
-            m = None if mask is None else (pack_weights(mask) if isinstance(mask, (list, tuple)) else capi.as_f64(mask))
-            cfg, res = capi.ChainCfg(), capi.ChainResult()
-            ctx._fill_chain_cfg(cfg, **job["cfg"])
-            cfg.force_f32 = attempt
-            acc = np.zeros(K, dtype=np.uint8)
-            llp, lpp = np.zeros(K), np.zeros(K)
-            J = arr[q]
-            J.ctx = ctx._ctx
-            J.cfg = C.pointer(cfg)
-            J.W_inout = capi.dptr(w)
-            J.mask_packed = capi.dptr(m)
-            J.M = idx.shape[1]
-            J.chain_id = q
-            J.idx = idx.ctypes.data_as(i32p)
-            J.delta = capi.dptr(delta)
-            J.cnt = cnt.ctypes.data_as(i32p)
-            J.log_u = capi.dptr(log_u)
-            J.out_accepted = acc.ctypes.data_as(C.POINTER(C.c_uint8))
-            J.out_loglik_prop = capi.dptr(llp)
-            J.out_logprior_prop = capi.dptr(lpp)
-            J.result = C.pointer(res)
-            keep.append((w, idx, cnt, delta, log_u, m, cfg, res))
-            outs.append(dict(w=w, accepted=acc, loglik_prop=llp, logprior_prop=lpp, _res=res, _ctx=ctx))
+            kept, out = fill_chain_job(arr[q], q, job, K, "%d" % K, q, force_f32=attempt)
+            keep.append(kept)
+            outs.append(out)
         rc = lib.npbnn_chains_run_batched(arr, len(jobs), K)
         if rc == capi.E_RANGE and attempt == 0 and all(job["ctx"].l0_option() != "f16" for job in jobs):
             continue

@@ -28,6 +28,7 @@ their scores from the tables with the same function (``scores_from_table``)."""
 import numpy as np
 
 from .files import load_obj
+from .stored import choose_table, class_labels, open_checkpoint, open_predictor, sample_sigmas, sigma_matrix, target_matrix
 
 KINDS = ("classification", "regression", "regression-error")
 DEFAULT_LEVELS = (0.5, 0.8, 0.9, 0.95)
@@ -70,39 +71,6 @@ def scores_from_table(table, n_rows):
 
 def _bin_of(value, n_bins):
     return np.minimum(n_bins - 1, np.floor(value * n_bins).astype(np.int64))
-
-
-def class_labels(labels, n_rows, n_classes, who):
-    lab = np.asarray(labels)
-    if lab.ndim != 1 or len(lab) != n_rows:
-        raise ValueError("%s: %s labels for %d rows" % (who, lab.shape, n_rows))
-    if lab.dtype.kind not in "iuf" or not (np.all(lab == np.floor(lab)) and np.all(lab >= 0) and np.all(lab < n_classes)):
-        raise ValueError("%s: the labels are not class indices in [0, %d)" % (who, n_classes))
-    return lab.astype(np.int64)
-
-
-def target_matrix(labels, n_rows, n_targets, who):
-    t = np.asarray(labels, dtype=np.float64)
-    if t.ndim == 1:
-        t = t.reshape(-1, 1)
-    if t.shape != (n_rows, n_targets):
-        raise ValueError("%s: targets are %s, expected %s" % (who, t.shape, (n_rows, n_targets)))
-    if not np.all(np.isfinite(t)):
-        raise ValueError("%s: the targets hold NaN or infinite values" % who)
-    return t
-
-
-def sigma_matrix(sigma_sets, n_samples, n_targets, who):
-    if sigma_sets is None:
-        raise ValueError("%s: kind \"regression\" needs sigma_sets (a sigma per sample and target)" % who)
-    sig = np.asarray(sigma_sets, dtype=np.float64)
-    if sig.ndim == 1:
-        sig = sig.reshape(-1, 1)
-    if sig.ndim != 2 or sig.shape[0] != n_samples or sig.shape[1] not in (1, n_targets):
-        raise ValueError("%s: sigma_sets is %s, expected (%d, %d)" % (who, sig.shape, n_samples, n_targets))
-    if not (np.all(np.isfinite(sig)) and np.all(sig > 0)):
-        raise ValueError("%s: every sigma must be positive and finite" % who)
-    return np.ascontiguousarray(np.broadcast_to(sig, (n_samples, n_targets)))
 
 
 def posterior_calibration(stack, labels, kind="classification", n_bins=15, levels=DEFAULT_LEVELS, sigma_sets=None):
@@ -186,47 +154,20 @@ def get_posterior_calibration(pkl_file, features=None, labels=None, n_bins=15, l
     labels that are not class indices or targets of another shape, ``n_bins`` or ``levels`` out of range, a ``"regression"``
     checkpoint without ``error_prm``, an odd number of outputs under ``"regression-error"``, ``"custom"`` and the count
     likelihoods' estimation modes."""
-    from .lppd import _sample_sigmas
-    from .posterior import _SamplePredictor
     who = "get_posterior_calibration"
     n_bins, lv = check_bins_and_levels(n_bins, levels, who)
-    model, _, logger = load_obj(pkl_file)
-    samples = logger._post_weight_samples
-    if len(samples) == 0:
-        raise ValueError("%s: the checkpoint holds no posterior samples" % who)
-    mode = getattr(model, "_estimation_mode", "classification")
-    if mode not in KINDS:
-        raise ValueError("%s: estimation mode %r is out of scope (%s are served; \"custom\" and the count likelihoods are not)"
-                         % (who, mode, ", ".join(KINDS)))
-    if isinstance(features, str):
-        if features != "train":
-            raise ValueError("%s: features=%r; \"train\", None (the test table) or a matrix" % (who, features))
-        x, y = model._data, model._labels
-    elif features is None:
-        x, y = model._test_data, model._test_labels
-    else:
-        if labels is None:
-            raise ValueError("%s: a feature matrix needs its labels" % who)
-        x, y = features, labels
-    x = np.asarray(x, dtype=np.float64)
-    if x.ndim != 2 or len(x) == 0:
-        raise ValueError("%s: the table is empty" % who)
-    n_out = len(samples[0]['weights'][-1])
+    model, samples, mode, n_out = open_checkpoint(load_obj(pkl_file), who, KINDS, "%s are served; \"custom\" and the count likelihoods are not" % ", ".join(KINDS))
+    x, y = choose_table(model, features, labels, who, need_labels=True)
     sigma = None
     if mode == "classification":
         y = class_labels(y, len(x), n_out, who)
     elif mode == "regression":
-        y, sigma = target_matrix(y, len(x), n_out, who), _sample_sigmas(samples, n_out, who)
+        y, sigma = target_matrix(y, len(x), n_out, who), sample_sigmas(samples, n_out, who)
     else:
         if n_out % 2:
             raise ValueError("%s: \"regression-error\" predicts a mean and a sigma per target, and %d outputs is odd" % (who, n_out))
         y = target_matrix(y, len(x), n_out // 2, who)
-    act = model._act_fun
-    act.reset_prm(samples[-1]['alphas'])          # (as get_posterior_est leaves it)
-    pred = _SamplePredictor(x.shape[1], samples, act, model._output_act_fun)
-    try:
+    with open_predictor(model, samples, x.shape[1]) as pred:
         res = pred.calibration(x, y, mode, n_bins=n_bins, levels=lv, sigma_sets=sigma, pointwise=pointwise)
-    finally:
-        pred.close()
     res = dict(res, n_samples=len(samples), n_rows=len(x))
     return res if pointwise else strip_pointwise(res)

@@ -27,6 +27,7 @@ as constant.  No rank normalisation, no tail ESS, no lag cap.
 import numpy as np
 
 from .files import load_obj
+from .stored import choose_table, open_predictor
 
 MAX_CHAINS = 64
 MIN_DRAWS = 8
@@ -160,7 +161,6 @@ def get_posterior_convergence(pkl_files, features=None, pointwise=True, rhat_thr
     dict; without ``pointwise`` ``rhat`` and ``ess`` are left out (they then never leave the device).  A custom output callable goes
     through the host stack.  ``ValueError`` before any device call: chains of different networks, no samples, fewer than 8 draws
     per chain, more than 64 chains, more than 16384 samples, an empty table."""
-    from .posterior import _SamplePredictor
     who = "get_posterior_convergence"
     files = [pkl_files] if isinstance(pkl_files, (str, bytes)) or hasattr(pkl_files, "__fspath__") else list(pkl_files)
     if len(files) == 0:
@@ -185,22 +185,9 @@ def get_posterior_convergence(pkl_files, features=None, pointwise=True, rhat_thr
     if rhat_threshold != rhat_threshold:
         raise ValueError("%s: the threshold is NaN" % who)
     model = chains[0][0]
-    if isinstance(features, str):
-        if features != "train":
-            raise ValueError("%s: features=%r; \"train\", None (the test table) or a matrix" % (who, features))
-        x = model._data
-    else:
-        x = model._test_data if features is None else features
-    x = np.asarray(x, dtype=np.float64)
-    if x.ndim != 2 or len(x) == 0:
-        raise ValueError("%s: the table is empty" % who)
-    act = model._act_fun
-    act.reset_prm(samples[-1]['alphas'])          # (as get_posterior_est leaves it)
-    pred = _SamplePredictor(x.shape[1], samples, act, model._output_act_fun)
-    try:
+    x, _ = choose_table(model, features, None, who, need_labels=False)
+    with open_predictor(model, samples, x.shape[1]) as pred:
         res = pred.convergence(x, len(chains), rhat_threshold=rhat_threshold, pointwise=pointwise)
-    finally:
-        pred.close()
     if not pointwise:
         res = {k: v for k, v in res.items() if k not in ("rhat", "ess")}
     return res

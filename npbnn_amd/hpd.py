@@ -89,11 +89,8 @@ def _hpd_row_blocks(blocks, post_samples, actFun, output_act_fun, level):
     """[(mean, lower, upper)] for each block of rows of a feature matrix, every stored sample replayed on it (the device seam).
     One device context serves every block: its matrix is replaced, the packed samples stay."""
     from .posterior import _SamplePredictor
-    pred = _SamplePredictor(blocks[0].shape[1], post_samples, actFun, output_act_fun)
-    try:
+    with _SamplePredictor(blocks[0].shape[1], post_samples, actFun, output_act_fun) as pred:
         return [pred.predict_hpd(b, level) for b in blocks]
-    finally:
-        pred.close()
 
 
 def _rows_hpd(matrix, samples, act, output_act_fun, level, n_out):

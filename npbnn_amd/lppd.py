@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _capi as capi
 from .files import load_obj
+from .stored import choose_table, class_labels, open_checkpoint, open_predictor, sample_sigmas, target_matrix
 
 _HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
 
@@ -59,36 +60,6 @@ def log_lik_of_stack(stack, labels, lik_kind, sigma_sets=None):
     return np.sum(-_HALF_LOG_2PI - np.log(sig) - 0.5 * ((t[None] - y) / sig) ** 2, axis=2)
 
 
-def _class_labels(labels, n_rows, n_classes):
-    lab = np.asarray(labels)
-    if lab.ndim != 1 or len(lab) != n_rows:
-        raise ValueError("get_posterior_lppd: %s labels for %d rows" % (lab.shape, n_rows))
-    if lab.dtype.kind not in "iuf" or not (np.all(lab == np.floor(lab)) and np.all(lab >= 0) and np.all(lab < n_classes)):
-        raise ValueError("get_posterior_lppd: the labels are not class indices in [0, %d)" % n_classes)
-    return lab.astype(np.int64)
-
-
-def _targets(labels, n_rows, n_out):
-    t = np.asarray(labels, dtype=np.float64)
-    if t.ndim == 1:
-        t = t.reshape(-1, 1)
-    if t.shape != (n_rows, n_out):
-        raise ValueError("get_posterior_lppd: targets are %s, expected %s" % (t.shape, (n_rows, n_out)))
-    if not np.all(np.isfinite(t)):
-        raise ValueError("get_posterior_lppd: the targets hold NaN or infinite values")
-    return t
-
-
-def _sample_sigmas(samples, n_out, who="get_posterior_lppd"):
-    if any('error_prm' not in s or len(np.atleast_1d(s['error_prm'])) == 0 for s in samples):
-        raise ValueError("%s: the checkpoint's samples carry no error_prm (the per-sample sigma of the Gaussian "
-                         "likelihood): the run had no error parameters to store" % who)
-    sig = np.array([np.ones(n_out) * np.asarray(s['error_prm'], dtype=np.float64) for s in samples])
-    if not (np.all(np.isfinite(sig)) and np.all(sig > 0)):
-        raise ValueError("%s: a sample's error_prm is not positive and finite" % who)
-    return sig
-
-
 def get_posterior_lppd(pkl_file, features=None, labels=None, pointwise=False):
     """lppd and WAIC of a checkpoint's stored samples: on its own test table (default), on its training table
     (``features="train"``), or on ``features`` with ``labels`` given.  Classification (labels are class indices) or Gaussian
@@ -98,40 +69,17 @@ def get_posterior_lppd(pkl_file, features=None, labels=None, pointwise=False):
     [N] only when ``pointwise``.  WAIC is meant for the training table; on a held-out table ``lppd`` is the quantity to compare.
     ``ValueError`` before any device call: no stored samples, an empty table, labels that are not class indices, a
     regression checkpoint without ``error_prm``, an estimation mode other than classification or regression."""
-    from .posterior import _SamplePredictor
-    model, _, logger = load_obj(pkl_file)
-    samples = logger._post_weight_samples
-    if len(samples) == 0:
-        raise ValueError("get_posterior_lppd: the checkpoint holds no posterior samples")
-    mode = getattr(model, "_estimation_mode", "classification")
-    if mode not in ("classification", "regression"):
-        raise ValueError("get_posterior_lppd: estimation mode %r is out of scope (classification and Gaussian regression with a "
-                         "sigma per sample are served; predicted-sigma regression and the count likelihoods are not)" % (mode,))
-    if isinstance(features, str):
-        if features != "train":
-            raise ValueError("get_posterior_lppd: features=%r; \"train\", None (the test table) or a matrix" % (features,))
-        x, y = model._data, model._labels
-    elif features is None:
-        x, y = model._test_data, model._test_labels
-    else:
-        if labels is None:
-            raise ValueError("get_posterior_lppd: a feature matrix needs its labels")
-        x, y = features, labels
-    x = np.asarray(x, dtype=np.float64)
-    if x.ndim != 2 or len(x) == 0:
-        raise ValueError("get_posterior_lppd: the table is empty")
-    n_out = len(samples[0]['weights'][-1])
+    who = "get_posterior_lppd"
+    model, samples, mode, n_out = open_checkpoint(load_obj(pkl_file), who, ("classification", "regression"),
+                                                  "classification and Gaussian regression with a sigma per sample are served; "
+                                                  "predicted-sigma regression and the count likelihoods are not")
+    x, y = choose_table(model, features, labels, who, need_labels=True)
     if mode == "classification":
-        kind, y, sigma = capi.LIK_CATEGORICAL, _class_labels(y, len(x), n_out), None
+        kind, y, sigma = capi.LIK_CATEGORICAL, class_labels(y, len(x), n_out, who), None
     else:
-        kind, y, sigma = capi.LIK_GAUSS, _targets(y, len(x), n_out), _sample_sigmas(samples, n_out)
-    act = model._act_fun
-    act.reset_prm(samples[-1]['alphas'])          # (as get_posterior_est leaves it)
-    pred = _SamplePredictor(x.shape[1], samples, act, model._output_act_fun)
-    try:
+        kind, y, sigma = capi.LIK_GAUSS, target_matrix(y, len(x), n_out, who), sample_sigmas(samples, n_out, who)
+    with open_predictor(model, samples, x.shape[1]) as pred:
         res = pred.lppd(x, y, kind, sigma_sets=sigma, pointwise=pointwise)
-    finally:
-        pred.close()
     res = _finish(dict(res), len(samples), len(x))
     if not pointwise:
         for k in ("lppd_i", "mean_log_lik_i", "p_waic_i"):

@@ -19,6 +19,7 @@ from . import _capi as capi
 from .files import load_obj
 from .layers import ActFun, output_kind
 from .likelihoods import CalcAccuracy
+from .stored import sigma_matrix
 
 
 class _SamplePredictor:
@@ -49,18 +50,27 @@ class _SamplePredictor:
             self._arch_set = True
         return ctx
 
+    @property
+    def custom_output(self):
+        """A custom output callable: no device kind, applied on the host to every sample's stack."""
+        return self._kind is None and self._out_fn is not None
+
+    def _out_kind_for(self, kind, who):
+        """The OUT_* constant the driver's ``kind`` stands for; ``ValueError`` in ``who``'s name when the model's output function is another."""
+        want = {"classification": capi.OUT_SOFTMAX, "regression": capi.OUT_IDENTITY, "regression-error": capi.OUT_SOFTPLUS_HALF}[kind]
+        if (capi.OUT_IDENTITY if self._kind is None else self._kind) != want:
+            raise ValueError("%s: kind %r does not go with the model's output function" % (who, kind))
+        return want
+
     def predict(self, features):
         """[n_samples, n_rows, n_out] predictions of every stored sample on ``features``."""
-        ctx = self._load(features)
-        y = ctx.predict_sets(list(self._packed), act_prm_sets=self._slopes, apply_out_fn=self._kind is not None)
-        if self._kind is None and self._out_fn is not None:      # custom output callable: host side, sample by sample
-            y = np.array([self._out_fn(yi) for yi in y])
-        return y
+        self.load(features)
+        return self.predict_loaded()
 
     def predict_loaded(self):
         """``predict`` on the matrix ``load`` uploaded, without a second upload."""
         y = self._ctx.predict_sets(list(self._packed), act_prm_sets=self._slopes, apply_out_fn=self._kind is not None)
-        if self._kind is None and self._out_fn is not None:
+        if self.custom_output:      # host side, sample by sample
             y = np.array([self._out_fn(yi) for yi in y])
         return y
 
@@ -68,7 +78,7 @@ class _SamplePredictor:
         """(mean, lower, upper) [n_rows, n_out] over the stored samples' predictions on ``features``; the stack stays on the
         device (npbnn_predict_sets_hpd).  A custom output callable has no device kind: its stack is built on the host and goes
         through ``posterior_hpd``."""
-        if self._kind is None and self._out_fn is not None:
+        if self.custom_output:
             from .hpd import posterior_hpd
             y = self.predict(features)
             lo, hi = posterior_hpd(y, level)
@@ -106,7 +116,7 @@ class _SamplePredictor:
         """(summary [n_rows, n_out] or None, confusion table against ``labels`` or None) of the stored samples' predictions on
         the loaded matrix as it stands, mode 0 (votes) or 1 (mean): ``_summarise`` and CalcAccuracy's table, accumulated on
         the device."""
-        if self._kind is None and self._out_fn is not None:
+        if self.custom_output:
             raise ValueError("a custom output callable has no device summary")
         return self._ctx.predict_sets_summary(self._packed, mode, labels=labels, act_prm_sets=self._slopes,
                                               want_summary=want_summary, apply_out_fn=self._kind is not None)
@@ -114,7 +124,7 @@ class _SamplePredictor:
     def support(self, mode, labels, thresholds, **kw):
         """Threshold cube (and Bayes-factor table, NaN-masked summary, keep mask: ``HipContext.predict_sets_support``'s keywords) of
         the stored samples' summary on the loaded matrix, mode 0 or 1."""
-        if self._kind is None and self._out_fn is not None:
+        if self.custom_output:
             raise ValueError("a custom output callable has no device summary")
         return self._ctx.predict_sets_support(self._packed, mode, labels, thresholds, act_prm_sets=self._slopes,
                                               apply_out_fn=self._kind is not None, **kw)
@@ -124,7 +134,7 @@ class _SamplePredictor:
         LIK_CATEGORICAL) or targets (LIK_GAUSS, ``sigma_sets`` per sample): the log-likelihood matrix stays on the device
         (npbnn_predict_sets_lppd).  A custom output callable has no device route: its stack is built on the host and goes through
         ``posterior_lppd``."""
-        if self._kind is None and self._out_fn is not None:
+        if self.custom_output:
             from .lppd import log_lik_of_stack, posterior_lppd
             res = posterior_lppd(log_lik_of_stack(self.predict(features), labels, lik_kind, sigma_sets))
             return res if pointwise else dict(res, lppd_i=None, mean_log_lik_i=None, p_waic_i=None)
@@ -141,17 +151,15 @@ class _SamplePredictor:
         mean of the squared sigmas, which does not depend on the row, is added here) or ``"regression-error"``; the stack stays on
         the device (npbnn_predict_sets_uncertainty), and without ``pointwise`` the [N, ...] arrays are None.  A custom output
         callable has no device kind: its stack is built on the host and goes through ``posterior_uncertainty``."""
-        from .uncertainty import KINDS, _sigma_sets, posterior_uncertainty
+        from .uncertainty import KINDS, posterior_uncertainty
         if kind not in KINDS:
             raise ValueError("uncertainty: kind %r; one of %s" % (kind, ", ".join(KINDS)))
-        if self._kind is None and self._out_fn is not None:
+        if self.custom_output:
             return posterior_uncertainty(self.predict(features), kind, sigma_sets)
-        want = {"classification": capi.OUT_SOFTMAX, "regression": capi.OUT_IDENTITY, "regression-error": capi.OUT_SOFTPLUS_HALF}[kind]
-        if (capi.OUT_IDENTITY if self._kind is None else self._kind) != want:
-            raise ValueError("uncertainty: kind %r does not go with the model's output function" % (kind,))
+        self._out_kind_for(kind, "uncertainty")
         sig = None
         if kind == "regression":
-            sig = _sigma_sets(sigma_sets, len(self._packed), self._weights[0][-1].shape[0], "uncertainty")
+            sig = sigma_matrix(sigma_sets, len(self._packed), self._weights[0][-1].shape[0], "uncertainty", positive=False)
         ctx = self._load(features)
         res = ctx.predict_sets_uncertainty(self._packed, act_prm_sets=self._slopes, pointwise=pointwise)
         if kind == "regression":
@@ -171,12 +179,10 @@ class _SamplePredictor:
         from .calibration import CLASS_POINT_KEYS, KINDS, REGRESSION_POINT_KEYS, posterior_calibration
         if kind not in KINDS:
             raise ValueError("calibration: kind %r; one of %s" % (kind, ", ".join(KINDS)))
-        if self._kind is None and self._out_fn is not None:
+        if self.custom_output:
             res = posterior_calibration(self.predict(features), labels, kind, n_bins, levels, sigma_sets)
             return res if pointwise else {k: (None if k in CLASS_POINT_KEYS + REGRESSION_POINT_KEYS else v) for k, v in res.items()}
-        want = {"classification": capi.OUT_SOFTMAX, "regression": capi.OUT_IDENTITY, "regression-error": capi.OUT_SOFTPLUS_HALF}[kind]
-        if (capi.OUT_IDENTITY if self._kind is None else self._kind) != want:
-            raise ValueError("calibration: kind %r does not go with the model's output function" % (kind,))
+        self._out_kind_for(kind, "calibration")
         if kind == "regression" and sigma_sets is None:
             raise ValueError("calibration: kind \"regression\" needs sigma_sets (a sigma per sample and target)")
         ctx = self._load(features)
@@ -192,7 +198,7 @@ class _SamplePredictor:
         ``features``, predictions post-output; the stack stays on the device (npbnn_predict_sets_convergence), and without
         ``pointwise`` ``rhat`` and ``ess`` are None.  A custom output callable has no device kind: its stack is built on the host
         and goes through ``posterior_convergence``."""
-        if self._kind is None and self._out_fn is not None:
+        if self.custom_output:
             from .convergence import posterior_convergence
             res = posterior_convergence(self.predict(features), n_chains, rhat_threshold)
             return res if pointwise else dict(res, rhat=None, ess=None)
@@ -202,6 +208,12 @@ class _SamplePredictor:
 
     def close(self):
         self._ctx.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def _column_index(col, n_features):
@@ -213,11 +225,8 @@ def _column_index(col, n_features):
 
 
 def _predict_samples(features, post_samples, actFun, output_act_fun):
-    pred = _SamplePredictor(features.shape[1], post_samples, actFun, output_act_fun)
-    try:
+    with _SamplePredictor(features.shape[1], post_samples, actFun, output_act_fun) as pred:
         return pred.predict(features)
-    finally:
-        pred.close()
 
 
 def sample_from_categorical(posterior_weights=None, post_prob_file=None, verbose=False):
@@ -353,14 +362,11 @@ def _prior_mean_prediction(features, prior_samples, act, output_act_fun):
     """Mean over the prior samples of their predictions on ``features`` [row, class]: accumulated on the device
     (``npbnn_predict_sets_summary`` mode 1, no stack) when the output function has a device kind, else from the stack."""
     act.reset_prm(prior_samples[-1]['alphas'])            # (upstream installs every prior sample's slopes in turn: the last stays)
-    pred = _SamplePredictor(features.shape[1], prior_samples, act, output_act_fun)
-    try:
-        if pred._kind is None and pred._out_fn is not None:
+    with _SamplePredictor(features.shape[1], prior_samples, act, output_act_fun) as pred:
+        if pred.custom_output:
             return np.mean(pred.predict(features), axis=0)
         pred.load(features)
         return pred.summary(1)[0]
-    finally:
-        pred.close()
 
 
 def predictBNN(predict_features, pickle_file, test_labels=[], instance_id=[], pickle_file_prior=0, target_acc=None,
@@ -421,7 +427,7 @@ def _device_route(post_summary_mode, predictor, features, true_labels, weights_p
     NPBNN_FI_HOST not set."""
     if os.environ.get("NPBNN_FI_HOST", "") not in ("", "0"):
         return False
-    if post_summary_mode not in (0, 1) or (predictor._kind is None and predictor._out_fn is not None):
+    if post_summary_mode not in (0, 1) or predictor.custom_output:
         return False
     if features.ndim != 2 or len(features) == 0 or len(weights_posterior) == 0:
         return False
@@ -453,8 +459,7 @@ def feature_importance(input_features, weights_pkl=None, weights_posterior=None,
         weights_posterior, actFun, output_act_fun = logger._post_weight_samples, model._act_fun, model._output_act_fun
     act = ActFun() if actFun is None else actFun
 
-    predictor = _SamplePredictor(features.shape[1], weights_posterior, act, output_act_fun)
-    try:
+    with _SamplePredictor(features.shape[1], weights_posterior, act, output_act_fun) as predictor:
         on_device = _device_route(post_summary_mode, predictor, features, true_labels, weights_posterior)
         if on_device:
             labels = np.asarray(true_labels).astype(np.int64).ravel()
@@ -479,8 +484,6 @@ def feature_importance(input_features, weights_pkl=None, weights_posterior=None,
         shuffled = np.array([[accuracy(block) for _ in range(n_permutations)] for block in blocks])    # [block, permutation]
         if on_device:
             predictor.permute(None, False)                          # the columns go back
-    finally:
-        predictor.close()
 
     loss = baseline - shuffled
     table = pd.DataFrame({'feature_block_index': np.arange(len(blocks)).astype(str), 'feature_name': [str(n) for n in block_names],

@@ -144,23 +144,20 @@ def get_posterior_threshold(pkl_file, target_acc=0.9, post_summary_mode=1, outpu
     labels = np.asarray(model._test_labels)
     samples, act, out_fn = logger._post_weight_samples, model._act_fun, model._output_act_fun
     grid = np.linspace(*THRESHOLD_GRID)
-    predictor = posterior._SamplePredictor(features.shape[1] if features.ndim == 2 else 0, samples, act, out_fn) if len(samples) else None
-    try:
-        if predictor is not None and posterior._device_route(post_summary_mode, predictor, features, labels, samples):
-            int_labels = labels.astype(np.int64).ravel()
-            act.reset_prm(samples[-1]['alphas'])                        # (as get_posterior_cat_prob leaves it)
-            predictor.load(features)                                    # the one upload
-            if write_predictions:
-                stack = predictor.predict_loaded()
-                summary = posterior._summarise(stack, post_summary_mode)
-                stem = posterior._output_stem(pkl_file, "", "")
-                posterior._accuracy_report(summary, labels, stem, 0.95, 0)
-                posterior._write_predictions(stem, stack, summary, [], 0)
-            table = table_from_cube(predictor.support(post_summary_mode, int_labels, grid)['cube'], grid)
-            return _select(table, target_acc, output_file)
-    finally:
-        if predictor is not None:
-            predictor.close()
+    if len(samples):
+        with posterior._SamplePredictor(features.shape[1] if features.ndim == 2 else 0, samples, act, out_fn) as predictor:
+            if posterior._device_route(post_summary_mode, predictor, features, labels, samples):
+                int_labels = labels.astype(np.int64).ravel()
+                act.reset_prm(samples[-1]['alphas'])                        # (as get_posterior_cat_prob leaves it)
+                predictor.load(features)                                    # the one upload
+                if write_predictions:
+                    stack = predictor.predict_loaded()
+                    summary = posterior._summarise(stack, post_summary_mode)
+                    stem = posterior._output_stem(pkl_file, "", "")
+                    posterior._accuracy_report(summary, labels, stem, 0.95, 0)
+                    posterior._write_predictions(stem, stack, summary, [], 0)
+                table = table_from_cube(predictor.support(post_summary_mode, int_labels, grid)['cube'], grid)
+                return _select(table, target_acc, output_file)
     if write_predictions:
         res = posterior.predictBNN(model._test_data, pickle_file=pkl_file, test_labels=model._test_labels,
                                    post_summary_mode=post_summary_mode, verbose=0)['post_prob_predictions']

@@ -21,23 +21,11 @@ that returns the stack."""
 import numpy as np
 
 from .files import load_obj
+from .stored import choose_table, open_checkpoint, open_predictor, sample_sigmas, sigma_matrix
 
 KINDS = ("classification", "regression", "regression-error")
 CLASS_ROW_KEYS = ("predictive_entropy_i", "expected_entropy_i", "mutual_information_i")
 REGRESSION_KEYS = ("mean", "epistemic_var", "aleatoric_var", "total_var")
-
-
-def _sigma_sets(sigma_sets, n_samples, n_targets, who):
-    if sigma_sets is None:
-        raise ValueError("%s: kind \"regression\" needs sigma_sets (a sigma per sample and target)" % who)
-    sig = np.asarray(sigma_sets, dtype=np.float64)
-    if sig.ndim == 1:
-        sig = sig.reshape(-1, 1)
-    if sig.ndim != 2 or sig.shape[0] != n_samples or sig.shape[1] not in (1, n_targets):
-        raise ValueError("%s: sigma_sets is %s, expected (%d, %d)" % (who, sig.shape, n_samples, n_targets))
-    if np.any(np.isnan(sig)):
-        raise ValueError("%s: sigma_sets holds NaN" % who)
-    return np.broadcast_to(sig, (n_samples, n_targets))
 
 
 def posterior_uncertainty(stack, kind="classification", sigma_sets=None):
@@ -78,7 +66,7 @@ def posterior_uncertainty(stack, kind="classification", sigma_sets=None):
     else:
         n_targets = y.shape[2]
         mu = y
-        sig = _sigma_sets(sigma_sets, n_samples, n_targets, who)
+        sig = sigma_matrix(sigma_sets, n_samples, n_targets, who, positive=False)
         aleatoric = np.broadcast_to(np.sum(sig * sig, axis=0) / n_samples, (n_rows, n_targets)).copy()
     shifted = mu - mu[0]                       # (by the first sample's value: a large mean with a tiny spread does not cancel)
     mean = mu[0] + np.sum(shifted, axis=0) / n_samples
@@ -102,37 +90,15 @@ def get_posterior_uncertainty(pkl_file, features=None, pointwise=True):
     arrays then never leave the device).  ``ValueError`` before any device call: no stored samples, an empty table, a
     ``"regression"`` checkpoint without ``error_prm``, an odd number of outputs under ``"regression-error"``, ``"custom"`` and the
     count likelihoods' estimation modes."""
-    from .lppd import _sample_sigmas
-    from .posterior import _SamplePredictor
-    model, _, logger = load_obj(pkl_file)
-    samples = logger._post_weight_samples
-    if len(samples) == 0:
-        raise ValueError("get_posterior_uncertainty: the checkpoint holds no posterior samples")
-    mode = getattr(model, "_estimation_mode", "classification")
-    if mode not in KINDS:
-        raise ValueError("get_posterior_uncertainty: estimation mode %r is out of scope (%s are served; \"custom\" and the count "
-                         "likelihoods are not)" % (mode, ", ".join(KINDS)))
-    if isinstance(features, str):
-        if features != "train":
-            raise ValueError("get_posterior_uncertainty: features=%r; \"train\", None (the test table) or a matrix" % (features,))
-        x = model._data
-    else:
-        x = model._test_data if features is None else features
-    x = np.asarray(x, dtype=np.float64)
-    if x.ndim != 2 or len(x) == 0:
-        raise ValueError("get_posterior_uncertainty: the table is empty")
-    n_out = len(samples[0]['weights'][-1])
+    who = "get_posterior_uncertainty"
+    model, samples, mode, n_out = open_checkpoint(load_obj(pkl_file), who, KINDS, "%s are served; \"custom\" and the count likelihoods are not" % ", ".join(KINDS))
+    x, _ = choose_table(model, features, None, who, need_labels=False)
     sigma = None
     if mode == "regression":
-        sigma = _sample_sigmas(samples, n_out, "get_posterior_uncertainty")
+        sigma = sample_sigmas(samples, n_out, who)
     elif mode == "regression-error" and n_out % 2:
-        raise ValueError("get_posterior_uncertainty: \"regression-error\" predicts a mean and a sigma per target, and %d outputs is odd" % n_out)
-    act = model._act_fun
-    act.reset_prm(samples[-1]['alphas'])          # (as get_posterior_est leaves it)
-    pred = _SamplePredictor(x.shape[1], samples, act, model._output_act_fun)
-    try:
+        raise ValueError("%s: \"regression-error\" predicts a mean and a sigma per target, and %d outputs is odd" % (who, n_out))
+    with open_predictor(model, samples, x.shape[1]) as pred:
         res = pred.uncertainty(x, mode, sigma_sets=sigma, pointwise=pointwise)
-    finally:
-        pred.close()
     res = dict(res, n_samples=len(samples), n_rows=len(x))
     return res if pointwise else _strip_pointwise(res)

@@ -44,6 +44,12 @@ class OraclePredictor:
     def close(self):
         pass
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        pass
+
 
 def _confusion(y, lab):
     """Stand-in for device_ops._confusion (npbnn_op_confusion): [true, predicted] counts and predicted-class counts."""
