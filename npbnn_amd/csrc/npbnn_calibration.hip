@@ -14,8 +14,8 @@
 //
 // The sets replay through replay_sets (npbnn_sets.hip.h) with apply_out_fn = 0: a group's d_y holds the float32 pre-output values.
 // The accumulate kernels, one thread per row, take each set of the group in set order and widen the row's values to float64 before
-// any exp, log or erfc.  Softmax: npbnn_uncertainty.hip's accumulation of the class probabilities, without its entropy term - the
-// row is read for its maximum, for sum exp(z - max), and class by class for exp(z - max) / sum onto [C][n_rows].  Regression:
+// any exp, log or erfc.  Softmax: softmax_mean_accumulate_kernel<ENTROPY = false> (npbnn_fold.hip.h), the kernel
+// npbnn_uncertainty.hip folds with, without its entropy term: sum_s softmax(z_s)_k onto [C][n_rows].  Regression:
 // [3][T][n_rows], K, sum (mu - K) and sum Phi.  No sum is reassociated and no product fused into a sum (fp contract off), so a set
 // folded alone and a set folded as the second of a group leave the same bits.
 // The final kernels, one thread per row, write the pointwise values and each row's bin to device arrays.  The integer tables are
@@ -23,7 +23,7 @@
 // the totals, and sum_confidence bin after bin with the bins on the outside - are per-workgroup partials (lanes by shuffles, the
 // waves in wave order through LDS) the host adds in workgroup order.  No floating-point atomics; the grid depends on n_rows alone, so
 // neither the grouping of the sets nor scheduling changes a bit.
-#include "npbnn_sets.hip.h"
+#include "npbnn_fold.hip.h"
 
 #include <cmath>
 #include <vector>
@@ -46,73 +46,10 @@ struct CalLevels {
     double half[kCalMaxLevels];       // level / 2
 };
 
-// softplus as np.logaddexp(0, z) (RegressTransformError): max(z, 0) + log1p(exp(-|z|))
-__device__ inline double cal_softplus(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
-
 // Phi((y - mu) / sigma), the standard normal distribution function as 0.5 erfc(-u / sqrt 2)
 __device__ inline double cal_phi(double y, double mu, double sigma) {
     const double u = (y - mu) / sigma;
     return 0.5 * erfc(-u / 1.4142135623730951);
-}
-
-// Softmax output.  y [g][n_rows][C]; acc [C][n_rows]: sum_s softmax(z_s)_k.  VEC: C is a multiple of 4, rows are read as float4.
-template <bool VEC>
-__global__ __launch_bounds__(kFiThreads) void cal_softmax_accumulate_kernel(const float* __restrict__ y, int g, int s0, long long n_rows, int C,
-                                                                            double* __restrict__ acc, int* __restrict__ flag) {
-    bool nan = false;
-    const long long per_set = n_rows * C;
-    for (long long r = (long long)blockIdx.x * kFiThreads + threadIdx.x; r < n_rows; r += (long long)gridDim.x * kFiThreads) {
-        double mx[kMaxCand], se[kMaxCand];
-#pragma unroll
-        for (int j = 0; j < kMaxCand; ++j) {
-            mx[j] = 0.0;
-            se[j] = 1.0;
-            if (j >= g) continue;
-            const float* row = y + (long long)j * per_set + r * C;
-            const double m = row_max<VEC>(row, C, nan);
-            double e = 0.0;                            // sum exp(z - m), in class order
-            if (VEC) {
-                for (int k = 0; k < C; k += 4) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(row + k);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) e += exp((double)v[q] - m);
-                }
-            } else {
-                for (int k = 0; k < C; ++k) e += exp((double)row[k] - m);
-            }
-            nan = nan || (e != e);
-            mx[j] = m;
-            se[j] = e;
-        }
-        // class by class: the group's probabilities onto the class's sum, in set order
-        if (VEC) {
-            for (int k = 0; k < C; k += 4) {
-                double a[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) a[q] = s0 > 0 ? acc[(long long)(k + q) * n_rows + r] : 0.0;
-#pragma unroll
-                for (int j = 0; j < kMaxCand; ++j) {
-                    if (j >= g) continue;
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(y + (long long)j * per_set + r * C + k);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) a[q] += exp((double)v[q] - mx[j]) / se[j];
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[(long long)(k + q) * n_rows + r] = a[q];
-            }
-        } else {
-            for (int k = 0; k < C; ++k) {
-                double a = s0 > 0 ? acc[(long long)k * n_rows + r] : 0.0;
-#pragma unroll
-                for (int j = 0; j < kMaxCand; ++j) {
-                    if (j >= g) continue;
-                    a += exp((double)y[(long long)j * per_set + r * C + k] - mx[j]) / se[j];
-                }
-                acc[(long long)k * n_rows + r] = a;
-            }
-        }
-    }
-    if (nan) atomicOr(flag, kFlagNaN);
 }
 
 // Target t of row r under the group's sets (mu[j], sg[j], set order) onto its accumulators K, sum (mu - K), sum Phi at
@@ -183,7 +120,7 @@ __global__ __launch_bounds__(kFiThreads) void cal_regress_accumulate_kernel(cons
                     if (j >= g) continue;
                     if (SP) {
                         nan = nan || (vs[j][q] != vs[j][q]);
-                        sg[j] = cal_softplus((double)vs[j][q]);
+                        sg[j] = softplus_f64((double)vs[j][q]);
                     } else {
                         sg[j] = sigma[(long long)(s0 + j) * T + t + q];
                     }
@@ -310,16 +247,6 @@ __global__ __launch_bounds__(kFiThreads) void cal_regress_final_kernel(const dou
     if (nan) atomicOr(flag, kFlagNaN);
 }
 
-// labels outside [0, C): found before any evaluation is launched
-__global__ __launch_bounds__(kFiThreads) void cal_label_check_kernel(const int* __restrict__ labels, long long n_rows, int C, int* __restrict__ flag) {
-    bool bad = false;
-    for (long long r = (long long)blockIdx.x * kFiThreads + threadIdx.x; r < n_rows; r += (long long)gridDim.x * kFiThreads) {
-        const int v = labels[r];
-        if (v < 0 || v >= C) bad = true;
-    }
-    if (bad) atomicOr(flag, kFlagBadLabel);
-}
-
 // The accumulate kernel of out_kind over a group's values y [g][n_rows][n_out], the sets s0 .. s0 + g - 1, on n_wg workgroups.  The
 // accumulator d_acc is [C][n_rows] for the softmax output and [3][T][n_rows] for regression (above).
 void calibration_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int n_out, const float* targets, const double* d_sigma,
@@ -327,8 +254,7 @@ void calibration_accumulate(hipStream_t st, const float* y, int g, int s0, long 
     const dim3 grid((unsigned)n_wg), block(kFiThreads);
     const bool vec = n_out % 4 == 0;
     if (out_kind == NPBNN_OUT_SOFTMAX) {
-        if (vec) hipLaunchKernelGGL(cal_softmax_accumulate_kernel<true>, grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
-        else hipLaunchKernelGGL(cal_softmax_accumulate_kernel<false>, grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
+        launch_softmax_mean_accumulate<false>(st, y, g, s0, n_rows, n_out, d_acc, n_wg, d_flag);
     } else if (out_kind == NPBNN_OUT_SOFTPLUS_HALF) {
         if (vec) hipLaunchKernelGGL((cal_regress_accumulate_kernel<true, true>), grid, block, 0, st, y, g, s0, n_rows, n_out, targets, d_sigma, d_acc, d_flag);
         else hipLaunchKernelGGL((cal_regress_accumulate_kernel<true, false>), grid, block, 0, st, y, g, s0, n_rows, n_out, targets, d_sigma, d_acc, d_flag);
@@ -352,7 +278,6 @@ extern "C" int npbnn_predict_sets_calibration(npbnn_ctx* ctx, const double* W_se
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
     ctx->fi_ns[1] = ctx->fi_ns[2] = ctx->calibration_ns = 0;       // (a call that is refused has launched nothing)
     if (!W_sets || n_sets < 1 || !out_totals || !out_counts) return fail(ctx, NPBNN_E_ARG, "%s: bad arguments", who);
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "%s: which must be 0 or 1", who);
     if (n_bins < 1 || n_bins > kCalMaxBins) return fail(ctx, NPBNN_E_ARG, "%s: n_bins must lie in 1..%d, got %d", who, kCalMaxBins, n_bins);
     if (n_levels < 0 || n_levels > kCalMaxLevels || (n_levels > 0 && !levels))
         return fail(ctx, NPBNN_E_ARG, "%s: n_levels must lie in 0..%d (with levels given), got %d", who, kCalMaxLevels, n_levels);
@@ -362,7 +287,9 @@ extern "C" int npbnn_predict_sets_calibration(npbnn_ctx* ctx, const double* W_se
         if (!(levels[l] > 0.0 && levels[l] < 1.0)) return fail(ctx, NPBNN_E_ARG, "%s: level %d is %g; every level lies strictly inside (0, 1)", who, l, levels[l]);
         lv.half[l] = levels[l] / 2.0;
     }
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "%s: call npbnn_set_arch first", who);
+    SetsTable tb;
+    int rc = open_sets_table(ctx, who, which, &tb);
+    if (rc) return rc;
     const int n_out = ctx->net.n_out;
     const int kind = ctx->arch.out_kind;
     const bool softmax = kind == NPBNN_OUT_SOFTMAX, sp = kind == NPBNN_OUT_SOFTPLUS_HALF;
@@ -380,48 +307,39 @@ extern "C" int npbnn_predict_sets_calibration(npbnn_ctx* ctx, const double* W_se
         if (sp && sigma_sets) return fail(ctx, NPBNN_E_ARG, "%s: NPBNN_OUT_SOFTPLUS_HALF predicts its sigma: sigma_sets must be NULL", who);
         if (!sp && !sigma_sets) return fail(ctx, NPBNN_E_ARG, "%s: NPBNN_OUT_IDENTITY needs sigma_sets [n_sets][n_targets]", who);
     }
-    Dataset& d = ctx->ds[which];
-    int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
-    if (rc) return rc;
+    Dataset& d = *tb.d;
     if (softmax && !d.labels) return fail(ctx, NPBNN_E_STATE, "%s: no labels on this data set (npbnn_set_labels_i64)", who);
     if (!softmax) {
         if (!d.targets) return fail(ctx, NPBNN_E_STATE, "%s: no targets on this data set (npbnn_set_targets_f64)", who);
         if (d.k != T) return fail(ctx, NPBNN_E_ARG, "%s: targets have %d columns, the network predicts %d", who, d.k, T);
-        if (!sp)
-            for (size_t i = 0; i < (size_t)n_sets * T; ++i)
-                if (!(sigma_sets[i] > 0.0) || !std::isfinite(sigma_sets[i]))
-                    return fail(ctx, NPBNN_E_ARG, "%s: sigma of set %zu, target %zu is %g; every sigma must be positive and finite", who, i / T, i % T,
-                                sigma_sets[i]);
+        if (!sp && (rc = check_sigma_sets(ctx, who, sigma_sets, n_sets, T))) return rc;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long n_rows = d.m->n_rows;
-    hipStream_t st = ctx->stream;
-    const int n_wg = (int)grid_for(n_rows);
+    const long long n_rows = tb.n_rows;
+    hipStream_t st = tb.st;
+    const int n_wg = tb.n_wg;
     const size_t n_acc = softmax ? (size_t)n_out * n_rows : (size_t)3 * T * n_rows;
     const size_t n_col = (size_t)n_rows * T;
     const size_t n_cnt = softmax ? (size_t)2 * n_bins : (size_t)T * (n_bins + n_levels);
     const size_t n_q = softmax ? (size_t)3 + n_bins : (size_t)2 * T;       // float sums that come back as per-workgroup partials
-    // accumulators, the pointwise results [3][n_rows][T], predicted class and bin per row, the tables, the partials, the sigmas, the flag word
-    DevBuf<double> d_acc, d_point, d_part, d_sig;
+    // (the final kernels write all three pointwise arrays; those the caller gave come back)
+    PointOuts po;
+    const int o0 = po.add(out_point0, n_col, true), o1 = po.add(out_point1, n_col, true), o2 = po.add(out_point2, n_col, true);
+    // accumulators, the pointwise results (po), predicted class and bin per row, the tables, the partials, the sigmas, the flag word
+    DevBuf<double> d_acc, d_part, d_sig;
     DevBuf<long long> d_pred;
     DevBuf<unsigned long long> d_cnt;
     DevBuf<int> d_bin, d_flag;
     if ((rc = d_acc.reserve(ctx, n_acc))) return rc;
     if ((rc = d_flag.reserve(ctx, 4))) return rc;
     if ((rc = d_part.reserve(ctx, n_q * n_wg))) return rc;
-    if ((rc = d_point.reserve(ctx, 3 * n_col))) return rc;
+    if ((rc = po.reserve(ctx))) return rc;
     if ((rc = d_cnt.reserve(ctx, n_cnt))) return rc;
     if (softmax && (rc = d_pred.reserve(ctx, (size_t)n_rows))) return rc;
     if (softmax && (rc = d_bin.reserve(ctx, (size_t)n_rows))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
     HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, n_cnt * sizeof(unsigned long long), st));
     if (softmax) {
-        hipLaunchKernelGGL(cal_label_check_kernel, dim3((unsigned)n_wg), dim3(kFiThreads), 0, st, (const int*)d.labels.get(), n_rows, n_out, d_flag.get());
-        HIP_TRY(ctx, hipGetLastError());
-        int bad = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&bad, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (bad) return fail(ctx, NPBNN_E_ARG, "%s: a label lies outside [0, %d)", who, n_out);
+        if ((rc = check_labels_on_device(ctx, who, d.labels.get(), n_rows, n_out, d_flag.get()))) return rc;
     } else if (!sp) {
         // (the sets' sigmas go to the device once per call: a group reads its rows of them)
         if ((rc = d_sig.reserve(ctx, (size_t)n_sets * T))) return rc;
@@ -437,21 +355,16 @@ extern "C" int npbnn_predict_sets_calibration(npbnn_ctx* ctx, const double* W_se
     if (rc) return rc;
     FiTimer tm;
     tm.mark(0, st);
-    double* const dev[3] = {d_point.get(), d_point.get() + n_col, d_point.get() + 2 * n_col};
     const dim3 grid((unsigned)n_wg), block(kFiThreads);
     if (softmax)
         hipLaunchKernelGGL(cal_softmax_final_kernel, grid, block, 0, st, (const double*)d_acc.get(), (const int*)d.labels.get(), n_rows, n_out, (int)n_sets,
-                           (int)n_bins, d_pred.get(), dev[0], dev[1], dev[2], d_bin.get(), d_cnt.get(), d_part.get(), d_flag.get());
+                           (int)n_bins, d_pred.get(), po.dev(o0), po.dev(o1), po.dev(o2), d_bin.get(), d_cnt.get(), d_part.get(), d_flag.get());
     else
         hipLaunchKernelGGL(cal_regress_final_kernel, grid, block, 0, st, (const double*)d_acc.get(), (const float*)d.targets.get(), n_rows, T, (int)n_sets,
-                           (int)n_bins, lv, dev[0], dev[1], dev[2], d_cnt.get(), d_part.get(), d_flag.get());
-    HIP_TRY(ctx, hipGetLastError());
-    tm.mark(1, st);
-    int flags = 0;
+                           (int)n_bins, lv, po.dev(o0), po.dev(o1), po.dev(o2), d_cnt.get(), d_part.get(), d_flag.get());
     std::vector<double> sums;
-    if ((rc = fetch_flags_and_totals(ctx, d_flag.get(), d_part.get(), n_q, n_wg, &flags, &sums))) return rc;
-    ctx->calibration_ns = tm.ns(0, 1);
-    if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "%s: a prediction is NaN", who);
+    // (the labels were checked before the replay and the final kernels raise no label flag: 0 classes)
+    if ((rc = finish_sets_entry(ctx, who, tm, d_flag.get(), d_part.get(), n_q, n_wg, &ctx->calibration_ns, 0, &sums))) return rc;
     if (softmax) {
         memcpy(out_totals, sums.data(), 3 * sizeof(double));
         memcpy(out_bin_sums, sums.data() + 3, (size_t)n_bins * sizeof(double));
@@ -460,9 +373,7 @@ extern "C" int npbnn_predict_sets_calibration(npbnn_ctx* ctx, const double* W_se
     }
     static_assert(sizeof(unsigned long long) == sizeof(int64_t) && sizeof(long long) == sizeof(int64_t), "the tables are copied as they are");
     HIP_TRY(ctx, hipMemcpyAsync(out_counts, d_cnt, n_cnt * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    double* const outs[3] = {out_point0, out_point1, out_point2};
-    for (int i = 0; i < 3; ++i)
-        if (outs[i]) HIP_TRY(ctx, hipMemcpyAsync(outs[i], dev[i], n_col * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = po.copy_out(ctx, st))) return rc;
     if (out_pred) HIP_TRY(ctx, hipMemcpyAsync(out_pred, d_pred, (size_t)n_rows * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return NPBNN_OK;

@@ -274,21 +274,18 @@ extern "C" int npbnn_predict_sets_convergence(npbnn_ctx* ctx, const double* W_se
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
     ctx->fi_ns[1] = ctx->fi_ns[2] = ctx->fi_ns[7] = 0;       // (a call that is refused has launched nothing)
     if (!W_sets || !out_summary || n_sets < 1 || n_chains < 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_convergence: bad arguments");
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_convergence: which must be 0 or 1");
     if (rhat_threshold != rhat_threshold) return fail(ctx, NPBNN_E_ARG, "predict_sets_convergence: the threshold is NaN");
     if (n_sets % n_chains != 0)
         return fail(ctx, NPBNN_E_ARG, "predict_sets_convergence: %d sets do not divide into %d chains of equal length", n_sets, n_chains);
     int rc = convergence_shape(ctx, "predict_sets_convergence", n_chains, n_sets / n_chains);
     if (rc) return rc;
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_convergence: call npbnn_set_arch first");
-    Dataset& d = ctx->ds[which];
-    if ((rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE))) return rc;
+    SetsTable tb;
+    if ((rc = open_sets_table(ctx, "predict_sets_convergence", which, &tb))) return rc;
     const int C = ctx->net.n_out;
-    const long long n_rows = d.m->n_rows;
+    const long long n_rows = tb.n_rows;
     const size_t per_set = (size_t)n_rows * C;
     if ((rc = check_stack_budget(ctx, "predict_sets_convergence", n_sets, n_rows, C))) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = tb.st;
     DevBuf<float> stack;
     DevBuf<double> d_res;
     DevBuf<int> d_flag;

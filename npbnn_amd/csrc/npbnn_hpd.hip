@@ -194,17 +194,13 @@ extern "C" int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, cons
                                       int apply_out_fn, double level, double* out_mean, double* out_lo, double* out_hi) {
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
     if (!W_sets || !out_mean || !out_lo || !out_hi || n_sets < 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_hpd: bad arguments");
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_hpd: which must be 0 or 1");
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_hpd: call npbnn_set_arch first");
+    SetsTable tb;
     int n_in = 0;
-    int rc = hpd_window(ctx, "predict_sets_hpd", n_sets, level, &n_in);
-    if (rc) return rc;
-    Dataset& d = ctx->ds[which];
-    if ((rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE))) return rc;
+    int rc = open_sets_table(ctx, "predict_sets_hpd", which, &tb);
+    if (rc || (rc = hpd_window(ctx, "predict_sets_hpd", n_sets, level, &n_in))) return rc;
     const int C = ctx->net.n_out;
-    const size_t per_set = (size_t)d.m->n_rows * C;
-    if ((rc = check_stack_budget(ctx, "predict_sets_hpd", n_sets, (long long)d.m->n_rows, C))) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t per_set = (size_t)tb.n_rows * C;
+    if ((rc = check_stack_budget(ctx, "predict_sets_hpd", n_sets, tb.n_rows, C))) return rc;
     DevBuf<float> stack;
     DevBuf<double> d_res;
     if ((rc = dev_alloc(ctx, stack, (size_t)n_sets * per_set))) return rc;

@@ -341,16 +341,13 @@ extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, 
     if (!W_sets || n_sets < 1 || (!out_summary && !out_confusion) || (out_confusion != nullptr) != (labels != nullptr))
         return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: bad arguments");
     if (mode != 0 && mode != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: mode must be 0 (votes) or 1 (mean), got %d", mode);
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: which must be 0 or 1");
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_summary: call npbnn_set_arch first");
-    Dataset& d = ctx->ds[which];
-    int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
+    SetsTable tb;
+    int rc = open_sets_table(ctx, "predict_sets_summary", which, &tb);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int C = ctx->net.n_out;
-    const long long n_rows = d.m->n_rows;
+    const long long n_rows = tb.n_rows;
     const size_t per_set = (size_t)n_rows * C;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = tb.st;
     // accumulators (per_set doubles, or as many unsigned), the summary, the confusion table, the labels, the flag word
     DevBuf<double> d_acc, d_summary;
     DevBuf<unsigned long long> d_conf;
@@ -383,14 +380,8 @@ extern "C" int npbnn_predict_sets_summary(npbnn_ctx* ctx, const double* W_sets, 
     else
         hipLaunchKernelGGL(summary_final_kernel<double>, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const double*)d_acc.get(), n_rows, C, (double)n_sets,
                            summary, lab, d_conf.get(), lds_conf, d_flag.get());
-    HIP_TRY(ctx, hipGetLastError());
-    tm.mark(1, st);
-    int flags = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->fi_ns[3] = tm.ns(0, 1);
-    if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: a prediction is NaN");
-    if (flags & kFlagBadLabel) return fail(ctx, NPBNN_E_ARG, "predict_sets_summary: a label lies outside [0, %d)", C);
+    std::vector<double> none;                      // (no floating-point partials: the tables are integers)
+    if ((rc = finish_sets_entry(ctx, "predict_sets_summary", tm, d_flag.get(), nullptr, 0, 0, &ctx->fi_ns[3], C, &none))) return rc;
     if (out_summary) HIP_TRY(ctx, hipMemcpyAsync(out_summary, summary, per_set * sizeof(double), hipMemcpyDeviceToHost, st));
     if (out_confusion) HIP_TRY(ctx, hipMemcpyAsync(out_confusion, d_conf, (size_t)C * C * sizeof(long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -16,7 +16,7 @@
 // in workgroup order.  The grid depends on n_rows alone, so neither the grouping of the sets nor scheduling changes a bit.
 // lppd_final_kernel, one thread per row, turns the accumulators into lppd_i, mean_ll_i, p_waic_i and per-workgroup partials of their
 // totals, reduced the same way.
-#include "npbnn_sets.hip.h"
+#include "npbnn_fold.hip.h"
 
 #include <cmath>
 #include <vector>
@@ -38,22 +38,6 @@ struct LppdArgs {
     double* part = nullptr;           // [n_sets][n_wg]: every workgroup's sum of its rows' ll under a set
     int n_wg = 0;                     // workgroups of the accumulate launch: grid_for(n_rows)
 };
-
-// sum_k exp(z[k] - mx), in class order
-template <bool VEC>
-__device__ inline double row_sum_exp(const float* __restrict__ row, int C, double mx) {
-    double s = 0.0;
-    if (VEC) {
-        for (int k = 0; k < C; k += 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(row + k);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s += exp((double)v[q] - mx);
-        }
-    } else {
-        for (int k = 0; k < C; ++k) s += exp((double)row[k] - mx);
-    }
-    return s;
-}
 
 // GAUSS: the likelihood is Gaussian (else categorical).  VEC: C is a multiple of 4, rows are read as float4.
 template <bool GAUSS, bool VEC>
@@ -162,16 +146,6 @@ __global__ __launch_bounds__(kFiThreads) void lppd_final_kernel(const double* __
     }
 }
 
-// labels outside [0, C): found before any evaluation is launched
-__global__ __launch_bounds__(kFiThreads) void lppd_label_check_kernel(const int* __restrict__ labels, long long n_rows, int C, int* __restrict__ flag) {
-    bool bad = false;
-    for (long long r = (long long)blockIdx.x * kFiThreads + threadIdx.x; r < n_rows; r += (long long)gridDim.x * kFiThreads) {
-        const int v = labels[r];
-        if (v < 0 || v >= C) bad = true;
-    }
-    if (bad) atomicOr(flag, kFlagBadLabel);
-}
-
 // lppd_accumulate_kernel over a group's values y [g][n_rows][C], the sets s0 .. s0 + g - 1
 void lppd_accumulate(hipStream_t st, const float* y, int g, int s0, long long n_rows, int C, double* d_acc, const LppdArgs& a, int* d_flag) {
     const dim3 grid((unsigned)a.n_wg), block(kFiThreads);
@@ -194,47 +168,44 @@ using namespace npbnn_api;
 extern "C" int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which, int lik_kind,
                                        const double* sigma_sets, double* out_lppd_i, double* out_mean_ll_i, double* out_pwaic_i,
                                        double* out_ll_sample, double* out_totals) {
+    const char* who = "predict_sets_lppd";
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
     ctx->fi_ns[1] = ctx->fi_ns[2] = ctx->fi_ns[5] = 0;       // (a call that is refused has launched nothing)
-    if (!W_sets || n_sets < 1 || !out_totals) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: bad arguments");
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: which must be 0 or 1");
+    if (!W_sets || n_sets < 1 || !out_totals) return fail(ctx, NPBNN_E_ARG, "%s: bad arguments", who);
     if (lik_kind == NPBNN_LIK_GAUSS_PRED_SIGMA || lik_kind == NPBNN_LIK_POISSON || lik_kind == NPBNN_LIK_NEGBIN || lik_kind == NPBNN_LIK_NEGBIN2D ||
         lik_kind == NPBNN_LIK_NEGBIN_BASE10)
-        return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: predicted-sigma regression and the count likelihoods are out of scope (likelihood kind %d); "
-                    "NPBNN_LIK_CATEGORICAL and NPBNN_LIK_GAUSS are served", lik_kind);
+        return fail(ctx, NPBNN_E_ARG, "%s: predicted-sigma regression and the count likelihoods are out of scope (likelihood kind %d); "
+                    "NPBNN_LIK_CATEGORICAL and NPBNN_LIK_GAUSS are served", who, lik_kind);
     if (lik_kind != NPBNN_LIK_CATEGORICAL && lik_kind != NPBNN_LIK_GAUSS)
-        return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: lik_kind must be NPBNN_LIK_CATEGORICAL or NPBNN_LIK_GAUSS, got %d", lik_kind);
+        return fail(ctx, NPBNN_E_ARG, "%s: lik_kind must be NPBNN_LIK_CATEGORICAL or NPBNN_LIK_GAUSS, got %d", who, lik_kind);
     const bool gauss = lik_kind == NPBNN_LIK_GAUSS;
-    if (gauss != (sigma_sets != nullptr)) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: sigma_sets goes with NPBNN_LIK_GAUSS and with nothing else");
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_lppd: call npbnn_set_arch first");
+    if (gauss != (sigma_sets != nullptr)) return fail(ctx, NPBNN_E_ARG, "%s: sigma_sets goes with NPBNN_LIK_GAUSS and with nothing else", who);
+    SetsTable tb;
+    int rc = open_sets_table(ctx, who, which, &tb);
+    if (rc) return rc;
     const int C = ctx->net.n_out;
     if (ctx->arch.out_kind != (gauss ? NPBNN_OUT_IDENTITY : NPBNN_OUT_SOFTMAX))
-        return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: the %s likelihood goes with the %s output function", gauss ? "Gaussian" : "categorical",
+        return fail(ctx, NPBNN_E_ARG, "%s: the %s likelihood goes with the %s output function", who, gauss ? "Gaussian" : "categorical",
                     gauss ? "identity" : "softmax");
-    Dataset& d = ctx->ds[which];
-    int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
-    if (rc) return rc;
-    if (!gauss && !d.labels) return fail(ctx, NPBNN_E_STATE, "predict_sets_lppd: no labels on this data set (npbnn_set_labels_i64)");
+    Dataset& d = *tb.d;
+    if (!gauss && !d.labels) return fail(ctx, NPBNN_E_STATE, "%s: no labels on this data set (npbnn_set_labels_i64)", who);
     if (gauss) {
-        if (!d.targets) return fail(ctx, NPBNN_E_STATE, "predict_sets_lppd: no targets on this data set (npbnn_set_targets_f64)");
-        if (d.k != C) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: targets have %d columns, the network %d outputs", d.k, C);
-        for (size_t i = 0; i < (size_t)n_sets * C; ++i)
-            if (!(sigma_sets[i] > 0.0) || !std::isfinite(sigma_sets[i]))
-                return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: sigma of set %zu, target %zu is %g; every sigma must be positive and finite", i / C, i % C,
-                            sigma_sets[i]);
+        if (!d.targets) return fail(ctx, NPBNN_E_STATE, "%s: no targets on this data set (npbnn_set_targets_f64)", who);
+        if (d.k != C) return fail(ctx, NPBNN_E_ARG, "%s: targets have %d columns, the network %d outputs", who, d.k, C);
+        if ((rc = check_sigma_sets(ctx, who, sigma_sets, n_sets, C))) return rc;
     }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long n_rows = d.m->n_rows;
-    hipStream_t st = ctx->stream;
-    const int n_wg = (int)grid_for(n_rows);
-    const int n_out_arr = (out_lppd_i ? 1 : 0) + (out_mean_ll_i ? 1 : 0) + (out_pwaic_i ? 1 : 0);
-    // accumulators, the pointwise results, the partials [n_sets][n_wg] | [3][n_wg], the sigma terms [lconst | isigma], the flag word
-    DevBuf<double> d_acc, d_point, d_part, d_sig;
+    const long long n_rows = tb.n_rows;
+    hipStream_t st = tb.st;
+    const int n_wg = tb.n_wg;
+    PointOuts po;
+    const int o_lppd = po.add(out_lppd_i, (size_t)n_rows), o_mean = po.add(out_mean_ll_i, (size_t)n_rows), o_pw = po.add(out_pwaic_i, (size_t)n_rows);
+    // accumulators, the pointwise results (po), the partials [n_sets][n_wg] | [3][n_wg], the sigma terms [lconst | isigma], the flag word
+    DevBuf<double> d_acc, d_part, d_sig;
     DevBuf<int> d_flag;
     if ((rc = d_acc.reserve(ctx, (size_t)kLppdAcc * n_rows))) return rc;
     if ((rc = d_flag.reserve(ctx, 4))) return rc;
     if ((rc = d_part.reserve(ctx, (size_t)(n_sets + 3) * n_wg))) return rc;
-    if (n_out_arr && (rc = d_point.reserve(ctx, (size_t)n_out_arr * n_rows))) return rc;
+    if ((rc = po.reserve(ctx))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
     LppdArgs a;
     a.lik_kind = lik_kind;
@@ -256,43 +227,24 @@ extern "C" int npbnn_predict_sets_lppd(npbnn_ctx* ctx, const double* W_sets, con
         a.isigma = d_sig.get() + n;
     } else {
         a.labels = d.labels.get();
-        hipLaunchKernelGGL(lppd_label_check_kernel, dim3(grid_for(n_rows)), dim3(kFiThreads), 0, st, (const int*)d.labels.get(), n_rows, C, d_flag.get());
-        HIP_TRY(ctx, hipGetLastError());
-        int bad = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&bad, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (bad) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: a label lies outside [0, %d)", C);
+        if ((rc = check_labels_on_device(ctx, who, d.labels.get(), n_rows, C, d_flag.get()))) return rc;
     }
     // (the first set of a row writes every accumulator: d_acc needs no zeroing)
-    rc = replay_sets(ctx, "predict_sets_lppd", W_sets, act_prm_sets, n_sets, which, 0, nullptr, [&](const SetGroup& grp) {
+    rc = replay_sets(ctx, who, W_sets, act_prm_sets, n_sets, which, 0, nullptr, [&](const SetGroup& grp) {
         lppd_accumulate(st, grp.y, grp.g, grp.s0, n_rows, C, d_acc.get(), a, d_flag.get());
         return NPBNN_OK;
     });
     if (rc) return rc;
     FiTimer tm;
     tm.mark(0, st);
-    double* p = d_point.get();
-    double* o_lppd = out_lppd_i ? p : nullptr;
-    if (out_lppd_i) p += n_rows;
-    double* o_mean = out_mean_ll_i ? p : nullptr;
-    if (out_mean_ll_i) p += n_rows;
-    double* o_pw = out_pwaic_i ? p : nullptr;
     double* d_tot = d_part.get() + (size_t)n_sets * n_wg;
-    hipLaunchKernelGGL(lppd_final_kernel, dim3((unsigned)n_wg), dim3(kFiThreads), 0, st, (const double*)d_acc.get(), n_rows, (int)n_sets, o_lppd, o_mean, o_pw,
-                       d_tot);
-    HIP_TRY(ctx, hipGetLastError());
-    tm.mark(1, st);
-    int flags = 0;
+    hipLaunchKernelGGL(lppd_final_kernel, dim3((unsigned)n_wg), dim3(kFiThreads), 0, st, (const double*)d_acc.get(), n_rows, (int)n_sets, po.dev(o_lppd),
+                       po.dev(o_mean), po.dev(o_pw), d_tot);
     std::vector<double> sums;          // every set's ll total, then the three totals
-    if ((rc = fetch_flags_and_totals(ctx, d_flag.get(), d_part.get(), (size_t)n_sets + 3, n_wg, &flags, &sums))) return rc;
-    ctx->fi_ns[5] = tm.ns(0, 1);
-    if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: a prediction is NaN");
-    if (flags & kFlagBadLabel) return fail(ctx, NPBNN_E_ARG, "predict_sets_lppd: a label lies outside [0, %d)", C);
+    if ((rc = finish_sets_entry(ctx, who, tm, d_flag.get(), d_part.get(), (size_t)n_sets + 3, n_wg, &ctx->fi_ns[5], C, &sums))) return rc;
     if (out_ll_sample) memcpy(out_ll_sample, sums.data(), (size_t)n_sets * sizeof(double));
     memcpy(out_totals, sums.data() + n_sets, 3 * sizeof(double));
-    if (out_lppd_i) HIP_TRY(ctx, hipMemcpyAsync(out_lppd_i, o_lppd, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out_mean_ll_i) HIP_TRY(ctx, hipMemcpyAsync(out_mean_ll_i, o_mean, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out_pwaic_i) HIP_TRY(ctx, hipMemcpyAsync(out_pwaic_i, o_pw, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = po.copy_out(ctx, st))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return NPBNN_OK;
 }

@@ -283,17 +283,15 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
     if (!W_sets || !out_mean || n_sets < 1 || n_grid < 1 || n_focal < 0 || (n_focal > 0 && (!focal || !grid)))
         return fail(ctx, NPBNN_E_ARG, "predict_pdp: bad arguments");
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_pdp: which must be 0 or 1");
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_pdp: call npbnn_set_arch first");
-    Dataset& d = ctx->ds[which];
-    int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
+    SetsTable tb;
+    int rc = open_sets_table(ctx, "predict_pdp", which, &tb);
     if (rc) return rc;
+    Dataset& d = *tb.d;
     const int F = ctx->arch.in_dim;
     for (int k = 0; k < n_focal; ++k)
         if (focal[k] < 0 || focal[k] >= F) return fail(ctx, NPBNN_E_ARG, "predict_pdp: focal column %d outside 0..%d", focal[k], F - 1);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int L = ctx->net.n_layers, C = ctx->net.n_out, n_act = L - 1;
-    const long long n_rows = d.m->n_rows;
+    const long long n_rows = tb.n_rows;
     const size_t wn = (size_t)ctx->n_weights;
     const size_t per_set = (size_t)n_rows * C;
 

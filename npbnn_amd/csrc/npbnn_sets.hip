@@ -7,6 +7,8 @@
 // with a group's float32 predictions is its sink.  NPBNN_INFO_REPLAY_PASSES / _MAX_GROUP: what the last replay launched.
 #include "npbnn_sets.hip.h"
 
+#include <cmath>
+
 namespace npbnn_api {
 
 int slope_group_len(const double* act_prm_sets, int n_act, int s0, int n_sets, int cap) {
@@ -126,11 +128,51 @@ int fetch_flags_and_totals(npbnn_ctx* ctx, const int* d_flag, const double* d_pa
     hipStream_t st = ctx->stream;
     std::vector<double> h_part(n_q * n_wg);
     HIP_TRY(ctx, hipMemcpyAsync(flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(h_part.data(), d_part, h_part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (!h_part.empty()) HIP_TRY(ctx, hipMemcpyAsync(h_part.data(), d_part, h_part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     totals->assign(n_q, 0.0);
     for (size_t q = 0; q < n_q; ++q)
         for (int w = 0; w < n_wg; ++w) (*totals)[q] += h_part[q * n_wg + w];
+    return NPBNN_OK;
+}
+
+int open_sets_table(npbnn_ctx* ctx, const char* who, int which, SetsTable* t) {
+    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "%s: which must be 0 or 1", who);
+    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "%s: call npbnn_set_arch first", who);
+    t->d = &ctx->ds[which];
+    const int rc = check_dataset_for_lik(ctx, *t->d, NPBNN_LIK_NONE);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    t->n_rows = t->d->m->n_rows;
+    t->st = ctx->stream;
+    t->n_wg = (int)grid_for(t->n_rows);
+    return NPBNN_OK;
+}
+
+int check_sigma_sets(npbnn_ctx* ctx, const char* who, const double* sigma_sets, int n_sets, int T) {
+    for (size_t i = 0; i < (size_t)n_sets * T; ++i)
+        if (!(sigma_sets[i] > 0.0) || !std::isfinite(sigma_sets[i]))
+            return fail(ctx, NPBNN_E_ARG, "%s: sigma of set %zu, target %zu is %g; every sigma must be positive and finite", who, i / T, i % T,
+                        sigma_sets[i]);
+    return NPBNN_OK;
+}
+
+int PointOuts::copy_out(npbnn_ctx* ctx, hipStream_t st) const {
+    for (int i = 0; i < count; ++i)
+        if (s[i].host) HIP_TRY(ctx, hipMemcpyAsync(s[i].host, dev(i), s[i].len * sizeof(double), hipMemcpyDeviceToHost, st));
+    return NPBNN_OK;
+}
+
+int finish_sets_entry(npbnn_ctx* ctx, const char* who, FiTimer& tm, const int* d_flag, const double* d_part, size_t n_q, int n_wg, int* ns_slot,
+                      int n_classes, std::vector<double>* totals) {
+    HIP_TRY(ctx, hipGetLastError());
+    tm.mark(1, ctx->stream);
+    int flags = 0;
+    const int rc = fetch_flags_and_totals(ctx, d_flag, d_part, n_q, n_wg, &flags, totals);
+    if (rc) return rc;
+    *ns_slot = tm.ns(0, 1);
+    if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "%s: a prediction is NaN", who);
+    if (n_classes > 0 && (flags & kFlagBadLabel)) return fail(ctx, NPBNN_E_ARG, "%s: a label lies outside [0, %d)", who, n_classes);
     return NPBNN_OK;
 }
 

@@ -3,7 +3,11 @@
 // npbnn_pdp.hip, route 2):
 // the replay of the sets group after group (replay_sets, npbnn_sets.hip) and the host helpers it is built from, the flag word's bits,
 // the launch shape of the streaming kernels, the HIP-event timer behind NPBNN_FI_TIMING, the fixed-order workgroup sum and the host
-// tail that adds its partials.  Nothing here belongs to a single entry.  Not part of the ABI.
+// tail that adds its partials, and the host scaffold of an entry: open_sets_table (the checks before the device is touched; every
+// entry but npbnn_predict_sets), finish_sets_entry (the tail of the five entries that end in a final kernel and a flag word),
+// check_sigma_sets and PointOuts (npbnn_lppd.hip, npbnn_uncertainty.hip, npbnn_calibration.hip).  The device code those three fold
+// with - the softmax fold, softplus, the label check - is in npbnn_fold.hip.h, which has a rule on contraction of its own.  Nothing
+// here belongs to a single entry.  Not part of the ABI.
 #pragma once
 #include "npbnn_ctx.hip.h"
 
@@ -161,5 +165,48 @@ void launch_summary_accumulate(hipStream_t st, const float* y, int g, long long 
 // The end of an entry on ctx->stream: the flag word into *flags and the partials d_part [n_q][n_wg] back, the stream
 // synchronised, and each quantity's partials added in workgroup order into (*totals)[n_q].
 int fetch_flags_and_totals(npbnn_ctx* ctx, const int* d_flag, const double* d_part, size_t n_q, int n_wg, int* flags, std::vector<double>* totals);
+
+// ---- the scaffold of an entry over stored sets: plain functions and one struct, called in sequence by the entry
+
+// The resident table an entry runs over, and the launch shape of its streaming kernels.
+struct SetsTable {
+    Dataset* d = nullptr;
+    long long n_rows = 0;
+    hipStream_t st = nullptr;
+    int n_wg = 0;                      // grid_for(n_rows)
+};
+// The checks every entry makes before it touches the device - `which` is 0 or 1, npbnn_set_arch was called, the table is there
+// (check_dataset_for_lik with NPBNN_LIK_NONE) - then hipSetDevice, and *t filled.  Launches nothing.
+int open_sets_table(npbnn_ctx* ctx, const char* who, int which, SetsTable* t);
+
+// NPBNN_E_ARG unless every entry of sigma_sets [n_sets][T] is positive and finite
+int check_sigma_sets(npbnn_ctx* ctx, const char* who, const double* sigma_sets, int n_sets, int T);
+
+// The per-row outputs of an entry that the caller may leave out: one device buffer, a slice per output that is wanted.
+struct PointOuts {
+    struct Slot { double* host; size_t off, len; bool on; };
+    // registers an output of n values (four at most) and returns its slot; always: the kernels write it whether the caller takes it or not
+    int add(double* host_out, size_t n, bool always = false) {
+        s[count] = Slot{host_out, total, n, host_out || always};
+        if (s[count].on) total += n;
+        return count++;
+    }
+    int reserve(npbnn_ctx* ctx) { return buf.reserve(ctx, total); }
+    // the slot's place on the device, or nullptr when it has none
+    double* dev(int i) const { return s[i].on ? buf.get() + s[i].off : nullptr; }
+    // enqueues the copies of the outputs the caller gave
+    int copy_out(npbnn_ctx* ctx, hipStream_t st) const;
+
+    Slot s[4] = {};
+    size_t total = 0;
+    int count = 0;
+    DevBuf<double> buf;
+};
+
+// The tail of an entry whose final kernel has been enqueued, in this order: hipGetLastError, tm.mark(1), fetch_flags_and_totals
+// (d_part [n_q][n_wg] into (*totals)[n_q]; n_q may be 0), the time between the marks 0 and 1 into *ns_slot, the refusal of a NaN
+// prediction, and with n_classes > 0 that of a label outside [0, n_classes).  The time is stored before the refusals.
+int finish_sets_entry(npbnn_ctx* ctx, const char* who, FiTimer& tm, const int* d_flag, const double* d_part, size_t n_q, int n_wg, int* ns_slot,
+                      int n_classes, std::vector<double>* totals);
 
 }  // namespace npbnn_api

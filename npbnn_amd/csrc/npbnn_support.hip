@@ -147,22 +147,19 @@ extern "C" int npbnn_predict_sets_support(npbnn_ctx* ctx, const double* W_sets, 
     if ((prior_summary != nullptr) != (out_bf != nullptr) || (!prior_summary && n_bf > 0) || (n_bf > 0 && !bf_thresholds))
         return fail(ctx, NPBNN_E_ARG, "predict_sets_support: prior_summary, bf_thresholds and out_bf go together");
     if (mode != 0 && mode != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: mode must be 0 (votes) or 1 (mean), got %d", mode);
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: which must be 0 or 1");
     if (!ascending(thresholds, n_thresholds)) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: the thresholds are not ascending (or one is NaN)");
     if (!ascending(bf_thresholds, n_bf)) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: the Bayes-factor thresholds are not ascending (or one is NaN)");
     if (cutoff && std::isnan(*cutoff)) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: the cutoff is NaN");
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_support: call npbnn_set_arch first");
-    Dataset& d = ctx->ds[which];
-    int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
+    SetsTable tb;
+    int rc = open_sets_table(ctx, "predict_sets_support", which, &tb);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int C = ctx->net.n_out;
-    const long long n_rows = d.m->n_rows;
+    const long long n_rows = tb.n_rows;
     const size_t per_set = (size_t)n_rows * C;
     const long long cells_ll = (long long)(n_thresholds + 1) * C * C;
     if (cells_ll > (1ll << 28)) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: %d thresholds x %d x %d classes is too large a table", n_thresholds, C, C);
     const size_t cells = (size_t)cells_ll, bf_cells = prior_summary ? (size_t)(n_bf + 1) * 2 : 0;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = tb.st;
     // accumulators, the summary, the keep mask, both tables, the labels, the thresholds [thresholds | bf thresholds], the prior, the flag word
     DevBuf<double> d_acc, d_summary, d_thr, d_prior;
     DevBuf<unsigned char> d_keep;
@@ -223,14 +220,8 @@ extern "C" int npbnn_predict_sets_support(npbnn_ctx* ctx, const double* W_sets, 
         hipLaunchKernelGGL(support_final_kernel<unsigned>, dim3(grid), dim3(kFiThreads), lds, st, (const unsigned*)reinterpret_cast<unsigned*>(d_acc.get()), a);
     else
         hipLaunchKernelGGL(support_final_kernel<double>, dim3(grid), dim3(kFiThreads), lds, st, (const double*)d_acc.get(), a);
-    HIP_TRY(ctx, hipGetLastError());
-    tm.mark(1, st);
-    int flags = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    ctx->fi_ns[4] = tm.ns(0, 1);
-    if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: a prediction is NaN");
-    if (flags & kFlagBadLabel) return fail(ctx, NPBNN_E_ARG, "predict_sets_support: a label lies outside [0, %d)", C);
+    std::vector<double> none;                      // (no floating-point partials: the tables are integers)
+    if ((rc = finish_sets_entry(ctx, "predict_sets_support", tm, d_flag.get(), nullptr, 0, 0, &ctx->fi_ns[4], C, &none))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(out_cube, d_tables, cells * sizeof(long long), hipMemcpyDeviceToHost, st));
     if (out_bf) HIP_TRY(ctx, hipMemcpyAsync(out_bf, d_tables.get() + cells, bf_cells * sizeof(long long), hipMemcpyDeviceToHost, st));
     if (out_summary) HIP_TRY(ctx, hipMemcpyAsync(out_summary, d_summary, per_set * sizeof(double), hipMemcpyDeviceToHost, st));

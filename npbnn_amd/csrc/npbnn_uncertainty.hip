@@ -10,10 +10,8 @@
 //
 // The sets replay through replay_sets (npbnn_sets.hip.h), the driver all stored-sets entries share, with apply_out_fn = 0: a group's d_y
 // holds the float32 pre-output values.  The accumulate kernels, one thread per row, take each set of the group in set order and widen
-// the row's values to float64 before any exp or log.  Softmax: the row is read for its maximum, again for sum exp(z - max) and
-// sum exp(z - max) (z - max) - H = log(sum) - that sum / sum, never log(softmax): a probability that underflows contributes 0 - and a
-// third time class by class, adding exp(z - max) / sum to the class's accumulator; no class count needs a register array or scratch
-// (the later reads hit the cache).  Accumulators [C + 1][n_rows]: sum_s p_sk per class, then sum_s H_s.  Regression: per (target, row)
+// the row's values to float64 before any exp or log.  Softmax: softmax_mean_accumulate_kernel<ENTROPY = true> (npbnn_fold.hip.h),
+// accumulators [C + 1][n_rows]: sum_s p_sk per class, then sum_s H_s.  Regression: per (target, row)
 // K = the first set's mu, sum (mu - K), sum (mu - K)^2 (the variance does not cancel when the mean is large and the spread tiny), and
 // for RegressTransformError sum sigma^2: [3 or 4][T][n_rows].  Every array is [n_rows] long per class or target, so a thread per row
 // reads and writes it coalesced.  No sum is reassociated and no product fused into a sum (fp contract off), so a set folded alone and a
@@ -21,7 +19,7 @@
 // The final kernels, one thread per row, turn the accumulators into the outputs and into per-workgroup partials of every per-row
 // quantity's total: lanes by shuffles, the waves in wave order through LDS, and the host adds the workgroups in order.  No
 // floating-point atomics; the grid depends on n_rows alone, so neither the grouping of the sets nor scheduling changes a bit.
-#include "npbnn_sets.hip.h"
+#include "npbnn_fold.hip.h"
 
 #include <cmath>
 #include <vector>
@@ -32,81 +30,6 @@
 namespace npbnn_api {
 
 namespace {
-
-// softplus as np.logaddexp(0, z) (RegressTransformError): max(z, 0) + log1p(exp(-|z|))
-__device__ inline double softplus_f64(double z) { return fmax(z, 0.0) + log1p(exp(-fabs(z))); }
-
-// Softmax output.  y [g][n_rows][C]; acc [C + 1][n_rows].  VEC: C is a multiple of 4, rows are read as float4.
-template <bool VEC>
-__global__ __launch_bounds__(kFiThreads) void unc_softmax_accumulate_kernel(const float* __restrict__ y, int g, int s0, long long n_rows, int C,
-                                                                            double* __restrict__ acc, int* __restrict__ flag) {
-    bool nan = false;
-    const long long per_set = n_rows * C;
-    for (long long r = (long long)blockIdx.x * kFiThreads + threadIdx.x; r < n_rows; r += (long long)gridDim.x * kFiThreads) {
-        double mx[kMaxCand], se[kMaxCand];
-        double h = s0 > 0 ? acc[(long long)C * n_rows + r] : 0.0;
-#pragma unroll
-        for (int j = 0; j < kMaxCand; ++j) {
-            mx[j] = 0.0;
-            se[j] = 1.0;
-            if (j >= g) continue;
-            const float* row = y + (long long)j * per_set + r * C;
-            const double m = row_max<VEC>(row, C, nan);
-            double e = 0.0, ez = 0.0;                 // sum exp(z - m), sum exp(z - m) (z - m), in class order
-            if (VEC) {
-                for (int k = 0; k < C; k += 4) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(row + k);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const double d = (double)v[q] - m, x = exp(d);
-                        e += x;
-                        ez += x * d;
-                    }
-                }
-            } else {
-                for (int k = 0; k < C; ++k) {
-                    const double d = (double)row[k] - m, x = exp(d);
-                    e += x;
-                    ez += x * d;
-                }
-            }
-            const double hs = log(e) - ez / e;        // lse(z) - sum_k p_k z_k, both shifted by m
-            nan = nan || (hs != hs);
-            h += hs;
-            mx[j] = m;
-            se[j] = e;
-        }
-        acc[(long long)C * n_rows + r] = h;
-        // class by class: the group's probabilities onto the class's sum, in set order
-        if (VEC) {
-            for (int k = 0; k < C; k += 4) {
-                double a[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) a[q] = s0 > 0 ? acc[(long long)(k + q) * n_rows + r] : 0.0;
-#pragma unroll
-                for (int j = 0; j < kMaxCand; ++j) {
-                    if (j >= g) continue;
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(y + (long long)j * per_set + r * C + k);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) a[q] += exp((double)v[q] - mx[j]) / se[j];
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[(long long)(k + q) * n_rows + r] = a[q];
-            }
-        } else {
-            for (int k = 0; k < C; ++k) {
-                double a = s0 > 0 ? acc[(long long)k * n_rows + r] : 0.0;
-#pragma unroll
-                for (int j = 0; j < kMaxCand; ++j) {
-                    if (j >= g) continue;
-                    a += exp((double)y[(long long)j * per_set + r * C + k] - mx[j]) / se[j];
-                }
-                acc[(long long)k * n_rows + r] = a;
-            }
-        }
-    }
-    if (nan) atomicOr(flag, kFlagNaN);
-}
 
 // One output o of a row under the group's sets (v[j], set order) onto its accumulators.  o < T (always, without SP): the mean of
 // target o - K, sum (mu - K), sum (mu - K)^2 at [0 | 1 | 2][T][n_rows]; o >= T: the sigma of target o - T - sum softplus(z)^2 at
@@ -265,8 +188,7 @@ void uncertainty_accumulate(hipStream_t st, const float* y, int g, int s0, long 
     const dim3 grid((unsigned)n_wg), block(kFiThreads);
     const bool vec = n_out % 4 == 0;
     if (out_kind == NPBNN_OUT_SOFTMAX) {
-        if (vec) hipLaunchKernelGGL(unc_softmax_accumulate_kernel<true>, grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
-        else hipLaunchKernelGGL(unc_softmax_accumulate_kernel<false>, grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
+        launch_softmax_mean_accumulate<true>(st, y, g, s0, n_rows, n_out, d_acc, n_wg, d_flag);
     } else if (out_kind == NPBNN_OUT_SOFTPLUS_HALF) {
         if (vec) hipLaunchKernelGGL((unc_regress_accumulate_kernel<true, true>), grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
         else hipLaunchKernelGGL((unc_regress_accumulate_kernel<true, false>), grid, block, 0, st, y, g, s0, n_rows, n_out, d_acc, d_flag);
@@ -284,74 +206,61 @@ using namespace npbnn_api;
 
 extern "C" int npbnn_predict_sets_uncertainty(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
                                               double* out_mean, double* out_total, double* out_aleatoric, double* out_epistemic, double* out_totals) {
+    const char* who = "predict_sets_uncertainty";
     if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
     ctx->fi_ns[1] = ctx->fi_ns[2] = ctx->fi_ns[6] = 0;       // (a call that is refused has launched nothing)
-    if (!W_sets || n_sets < 1 || !out_totals) return fail(ctx, NPBNN_E_ARG, "predict_sets_uncertainty: bad arguments");
-    if (which != 0 && which != 1) return fail(ctx, NPBNN_E_ARG, "predict_sets_uncertainty: which must be 0 or 1");
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "predict_sets_uncertainty: call npbnn_set_arch first");
-    Dataset& d = ctx->ds[which];
-    int rc = check_dataset_for_lik(ctx, d, NPBNN_LIK_NONE);
+    if (!W_sets || n_sets < 1 || !out_totals) return fail(ctx, NPBNN_E_ARG, "%s: bad arguments", who);
+    SetsTable tb;
+    int rc = open_sets_table(ctx, who, which, &tb);
     if (rc) return rc;
     const int n_out = ctx->net.n_out;
     const int kind = ctx->arch.out_kind;
     const bool softmax = kind == NPBNN_OUT_SOFTMAX, sp = kind == NPBNN_OUT_SOFTPLUS_HALF;
     if (sp && n_out % 2 != 0)
-        return fail(ctx, NPBNN_E_ARG, "predict_sets_uncertainty: NPBNN_OUT_SOFTPLUS_HALF splits the outputs into means and sigmas, and %d is odd", n_out);
+        return fail(ctx, NPBNN_E_ARG, "%s: NPBNN_OUT_SOFTPLUS_HALF splits the outputs into means and sigmas, and %d is odd", who, n_out);
     if (kind == NPBNN_OUT_IDENTITY && (out_total || out_aleatoric))
-        return fail(ctx, NPBNN_E_ARG, "predict_sets_uncertainty: the identity output predicts no sigma: the aleatoric and the total variance are the "
-                    "caller's to add (out_total and out_aleatoric must be NULL)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long n_rows = d.m->n_rows;
-    hipStream_t st = ctx->stream;
-    const int n_wg = (int)grid_for(n_rows);
+        return fail(ctx, NPBNN_E_ARG, "%s: the identity output predicts no sigma: the aleatoric and the total variance are the "
+                    "caller's to add (out_total and out_aleatoric must be NULL)", who);
+    const long long n_rows = tb.n_rows;
+    hipStream_t st = tb.st;
+    const int n_wg = tb.n_wg;
     const int T = softmax ? 1 : (sp ? n_out / 2 : n_out);            // columns of the per-row quantities
     const size_t n_acc = softmax ? (size_t)(n_out + 1) * n_rows : (size_t)(sp ? 4 : 3) * T * n_rows;
     const size_t n_mean = (size_t)n_rows * (softmax ? n_out : T), n_col = (size_t)n_rows * T;
-    const size_t n_part = (size_t)(softmax ? 3 : 4 * T) * n_wg;
-    double* const outs[4] = {out_mean, out_total, out_aleatoric, out_epistemic};
-    size_t n_point = 0;
-    for (int i = 0; i < 4; ++i)
-        if (outs[i]) n_point += i == 0 ? n_mean : n_col;
-    // accumulators, the pointwise results, the partials, the flag word
-    DevBuf<double> d_acc, d_point, d_part;
+    const size_t n_q = softmax ? 3 : (size_t)4 * T;                  // float sums that come back as per-workgroup partials
+    PointOuts po;
+    const int o_mean = po.add(out_mean, n_mean), o_total = po.add(out_total, n_col), o_alea = po.add(out_aleatoric, n_col),
+              o_epi = po.add(out_epistemic, n_col);
+    // accumulators, the pointwise results (po), the partials, the flag word
+    DevBuf<double> d_acc, d_part;
     DevBuf<int> d_flag;
     if ((rc = d_acc.reserve(ctx, n_acc))) return rc;
     if ((rc = d_flag.reserve(ctx, 4))) return rc;
-    if ((rc = d_part.reserve(ctx, n_part))) return rc;
-    if (n_point && (rc = d_point.reserve(ctx, n_point))) return rc;
+    if ((rc = d_part.reserve(ctx, n_q * n_wg))) return rc;
+    if ((rc = po.reserve(ctx))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), st));
     // (the first set of a row writes every accumulator: d_acc needs no zeroing)
-    rc = replay_sets(ctx, "predict_sets_uncertainty", W_sets, act_prm_sets, n_sets, which, 0, nullptr, [&](const SetGroup& grp) {
+    rc = replay_sets(ctx, who, W_sets, act_prm_sets, n_sets, which, 0, nullptr, [&](const SetGroup& grp) {
         uncertainty_accumulate(st, grp.y, grp.g, grp.s0, n_rows, n_out, d_acc.get(), kind, n_wg, d_flag.get());
         return NPBNN_OK;
     });
     if (rc) return rc;
     FiTimer tm;
     tm.mark(0, st);
-    double* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    double* p = d_point.get();
-    for (int i = 0; i < 4; ++i)
-        if (outs[i]) { dev[i] = p; p += i == 0 ? n_mean : n_col; }
     const dim3 grid((unsigned)n_wg), block(kFiThreads);
     if (softmax)
-        hipLaunchKernelGGL(unc_softmax_final_kernel, grid, block, 0, st, (const double*)d_acc.get(), n_rows, n_out, (int)n_sets, dev[0], dev[1], dev[2], dev[3],
-                           d_part.get(), d_flag.get());
+        hipLaunchKernelGGL(unc_softmax_final_kernel, grid, block, 0, st, (const double*)d_acc.get(), n_rows, n_out, (int)n_sets, po.dev(o_mean), po.dev(o_total),
+                           po.dev(o_alea), po.dev(o_epi), d_part.get(), d_flag.get());
     else if (sp)
-        hipLaunchKernelGGL(unc_regress_final_kernel<true>, grid, block, 0, st, (const double*)d_acc.get(), n_rows, T, (int)n_sets, dev[0], dev[1], dev[2], dev[3],
-                           d_part.get(), d_flag.get());
+        hipLaunchKernelGGL(unc_regress_final_kernel<true>, grid, block, 0, st, (const double*)d_acc.get(), n_rows, T, (int)n_sets, po.dev(o_mean),
+                           po.dev(o_total), po.dev(o_alea), po.dev(o_epi), d_part.get(), d_flag.get());
     else
-        hipLaunchKernelGGL(unc_regress_final_kernel<false>, grid, block, 0, st, (const double*)d_acc.get(), n_rows, T, (int)n_sets, dev[0], dev[1], dev[2], dev[3],
-                           d_part.get(), d_flag.get());
-    HIP_TRY(ctx, hipGetLastError());
-    tm.mark(1, st);
-    int flags = 0;
+        hipLaunchKernelGGL(unc_regress_final_kernel<false>, grid, block, 0, st, (const double*)d_acc.get(), n_rows, T, (int)n_sets, po.dev(o_mean),
+                           po.dev(o_total), po.dev(o_alea), po.dev(o_epi), d_part.get(), d_flag.get());
     std::vector<double> totals;
-    if ((rc = fetch_flags_and_totals(ctx, d_flag.get(), d_part.get(), n_part / n_wg, n_wg, &flags, &totals))) return rc;
-    ctx->fi_ns[6] = tm.ns(0, 1);
-    if (flags & kFlagNaN) return fail(ctx, NPBNN_E_ARG, "predict_sets_uncertainty: a prediction is NaN");
+    if ((rc = finish_sets_entry(ctx, who, tm, d_flag.get(), d_part.get(), n_q, n_wg, &ctx->fi_ns[6], 0, &totals))) return rc;
     memcpy(out_totals, totals.data(), totals.size() * sizeof(double));
-    for (int i = 0; i < 4; ++i)
-        if (outs[i]) HIP_TRY(ctx, hipMemcpyAsync(outs[i], dev[i], (i == 0 ? n_mean : n_col) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = po.copy_out(ctx, st))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return NPBNN_OK;
 }
