@@ -664,6 +664,45 @@ void report_eval_stamps(const DevBuf<unsigned long long>& stamps, int grid, int 
             (double)(first_end - first) * 0.01, (double)(last - first) * 0.01);
 }
 
+// diagnostics (NPBNN_STEP_STAMPS): what the step kernel stamped during a batch - [1024][8] phases of a step, rows indexed by the first
+// iteration of the pass it decided
+void report_step_stamps(const DevBuf<unsigned long long>& stamps) {
+    std::vector<unsigned long long> hs(1024 * 8);
+    (void)hipMemcpy(hs.data(), stamps, hs.size() * 8, hipMemcpyDeviceToHost);
+    double acc[8] = {0};
+    int n = 0;
+    for (int r = 1; r < 1024; ++r) {
+        const unsigned long long* q = &hs[(size_t)r * 8];
+        if (!q[0] || !q[6]) continue;
+        bool whole = true;          // (a step that skipped a phase - a void pass has nothing to reduce - left an older stamp there)
+        for (int k = 1; k <= 6; ++k) whole = whole && q[k] >= q[k - 1];
+        if (!whole) continue;
+        for (int k = 1; k <= 6; ++k) acc[k] += (double)(q[k] - q[k - 1]) * 0.01;   // 100 MHz wall clock -> us
+        ++n;
+    }
+    if (n) fprintf(stderr, "[npbnn step stamps] prefetch %.2f  reduce %.2f  decide %.2f  commit %.2f  prepare %.2f  finish %.2f us (mean of %d)\n",
+                   acc[1] / n, acc[2] / n, acc[3] / n, acc[4] / n, acc[5] / n, acc[6] / n, n);
+    // start of a step -> start of the next one (the period of a pass where the step is what the passes wait for), and what of it the
+    // step workgroup spent between two steps (waiting for the evaluating workgroups' sums, flag-ordered schedules).  Rows are
+    // indexed by the first iteration of the decided pass: in time order
+    std::vector<std::pair<unsigned long long, unsigned long long>> se;
+    for (int r = 1; r < 1024; ++r) {
+        const unsigned long long* q = &hs[(size_t)r * 8];
+        if (q[0] && q[6] && q[6] > q[0]) se.push_back({q[0], q[6]});
+    }
+    std::sort(se.begin(), se.end());
+    double period = 0, idle = 0;
+    int m = 0;
+    for (size_t i = 0; i + 1 < se.size(); ++i) {
+        const double d = (double)(se[i + 1].first - se[i].first) * 0.01;
+        if (se[i + 1].first < se[i].second || d > 200.0) continue;      // (a row overwritten by a later lap of the table; a batch boundary)
+        period += d;
+        idle += (double)(se[i + 1].first - se[i].second) * 0.01;
+        ++m;
+    }
+    if (m) fprintf(stderr, "[npbnn step stamps] step start -> next step start %.2f us, of which between steps %.2f us (mean of %d)\n", period / m, idle / m, m);
+}
+
 EvalParams make_params(npbnn_ctx* ctx, const Dataset& d) {
     EvalParams p{};
     p.X = ctx->net.l0_f16 ? d.m->X16 : d.m->X;
@@ -1066,11 +1105,11 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     if (what == NPBNN_INFO_WAVES_PER_BLOCK) { size_t lds = 0; *out = pick_waves_per_block(ctx, &lds, 1, layout_for(ctx, ctx->ds[0])); return NPBNN_OK; }
     if (what == NPBNN_INFO_N_CU) { *out = ctx->n_cu; return NPBNN_OK; }
     if (what == NPBNN_INFO_TURN_NS_OVERLAPPED || what == NPBNN_INFO_TURN_NS_BETWEEN) {
-        *out = (int)(1000.0 * ctx->turn_us[what == NPBNN_INFO_TURN_NS_BETWEEN ? 1 : 0]);
+        *out = (int)(1000.0 * ctx->sched.turn_us[what == NPBNN_INFO_TURN_NS_BETWEEN ? 1 : 0]);
         return NPBNN_OK;
     }
     if (what == NPBNN_INFO_IT_NS_OVERLAPPED || what == NPBNN_INFO_IT_NS_BETWEEN) {
-        const double* c = ctx->it_us[what == NPBNN_INFO_IT_NS_BETWEEN ? 1 : 0];      // (short batches - dispatches of 100 - when measured, else long ones)
+        const double* c = ctx->sched.it_us[what == NPBNN_INFO_IT_NS_BETWEEN ? 1 : 0];      // (short batches - dispatches of 100 - when measured, else long ones)
         *out = (int)(1000.0 * (c[0] > 0.0 ? c[0] : c[1]));
         return NPBNN_OK;
     }

@@ -26,6 +26,19 @@ ResLayout res_layout(size_t kc, size_t wb) {
     L.total = L.lpp + up256(kc * sizeof(double));
     return L;
 }
+constexpr size_t kResFlagWord = 448;           // the block's flag word (kFlag...: ctx->d_chain_ovf), behind the room ChainDev has
+static_assert(sizeof(ChainDev) <= kResFlagWord, "ChainDev must fit its slot of the result block");
+static_assert(kSpecPartSlots == NPBNN_SCHED_SPEC_PART_SLOTS, "npbnn_sched_plan.h holds the evaluating workgroups against the slots spec_rounds reads");
+int res_flags(const npbnn_ctx* ctx) { return *reinterpret_cast<const int*>(ctx->h_res + kResFlagWord); }   // (of the block that has come back)
+
+// what a batch is made from: the caller's arrays, and how the batch is run
+struct ChainArgs {
+    const npbnn_chain_cfg* cfg;
+    const double *W_in, *mask_packed;
+    int K, M;
+    const int32_t* idx; const double* delta; const int32_t* cnt; const double* log_u;     // the draws
+    int seg_len; bool alone_on_device; int group_blocks;                                  // (see chain_prepare)
+};
 
 struct ChainBatch {
     LaunchPlan lp;
@@ -34,7 +47,9 @@ struct ChainBatch {
     bool overlap = false;
     bool persist = false;                      // persistent form: one launch loops over the passes (device flags order them)
     bool sync = false;                         // overlapped schedule with the launches alternating between two streams (device flags)
+    bool spec = false;                         // NPBNN_SCHED_PERSIST_SERIAL: the launch's build with the speculative step
     bool forked = false;                       // sync: the two streams have been made to wait for ctx->stream
+    bool step_keeps_image = false;             // weight-streamed path: the step patches the candidate image itself (ChainParams::cand_image)
     bool make_cands = false;                   // weight-streamed path: the candidates are made between step and pass (ChainParams::prep_terms)
     size_t wb = 0;
     int launch = 0;                            // launches enqueued so far (overlapped schedule: the pass parity follows it)
@@ -104,140 +119,81 @@ int shard_exchange(npbnn_ctx* ctx, const LaunchPlan& lp, int D) {
     return NPBNN_OK;
 }
 
-// seg_len > 0: the chain stops deciding at iteration seg_len until an exchange kernel moves the limit (exchange run)
-int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in, const double* mask_packed, int32_t K, int32_t M,
-                  const int32_t* idx, const double* delta, const int32_t* cnt, const double* log_u, int seg_len, ChainBatch* B,
-                  bool alone_on_device = true, int group_blocks = 0) {
-    // alone_on_device: no other chain's launches share the GPU with this batch (the two-stream schedule counts on that)
-    // group_blocks > 0: the chain is one of a group pass (npbnn_chains_run_batched): one candidate per launch, overlapped schedule,
-    // its sums come from that many evaluating workgroups of the group's launches
-    if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
-    if (!cfg || !W_in || K < 1 || M < 1 || !idx || !delta || !cnt || !log_u) return fail(ctx, NPBNN_E_ARG, "chain_run: bad arguments");
-    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "chain_run: call npbnn_set_arch first");
-    B->tw0 = wall_us();
-    const int lik = ctx->net.lik_kind;
+// ---- prepare, in stages: check, plan and schedule, reserve, upload, parameter blocks, launch.  Everything goes to ctx->stream. ----
+// stage 1: every refusal the arguments and the context's state decide, before anything is reserved or enqueued
+int prepare_check(npbnn_ctx* ctx, const ChainArgs& A) {
+    const npbnn_chain_cfg* cfg = A.cfg;
+    const int K = A.K, M = A.M, lik = ctx->net.lik_kind;
     if (lik == NPBNN_LIK_NONE) return fail(ctx, NPBNN_E_STATE, "chain_run: the architecture has no likelihood");
     if (cfg->prior_kind < 0 || cfg->prior_kind > NPBNN_PRIOR_LAPLACE) return fail(ctx, NPBNN_E_ARG, "chain_run: prior_kind=%d", cfg->prior_kind);
     for (int t = 0; t < K; ++t)
-        if (cnt[t] < 0 || cnt[t] > M) return fail(ctx, NPBNN_E_ARG, "chain_run: cnt[%d]=%d outside 0..%d", t, cnt[t], M);
+        if (A.cnt[t] < 0 || A.cnt[t] > M) return fail(ctx, NPBNN_E_ARG, "chain_run: cnt[%d]=%d outside 0..%d", t, A.cnt[t], M);
     // (the K * M weight indices are checked on the device, where they are read anyway: gather_pos_kernel)
-    Dataset& d = ctx->ds[0];
-    int rc = check_dataset_for_lik(ctx, d, lik);
+    const int rc = check_dataset_for_lik(ctx, ctx->ds[0], lik);
     if (rc) return rc;
+    if (ctx->shard_n > 0 && (A.group_blocks > 0 || A.seg_len > 0))
+        return fail(ctx, NPBNN_E_STATE, "chain_run: a context whose rows are split over ranks runs plain batches only (no group pass, no exchange run)");
+    if (cfg->sigma_mult || cfg->hastings) {
+        if (!cfg->sigma_mult || !cfg->hastings || lik != NPBNN_LIK_GAUSS)
+            return fail(ctx, NPBNN_E_ARG, "chain_run: sigma_mult and hastings go together, with the Gaussian likelihood");
+        for (size_t i = 0; i < (size_t)K * ctx->net.k_targets; ++i)
+            if (!(cfg->sigma_mult[i] > 0.0)) return fail(ctx, NPBNN_E_ARG, "chain_run: sigma_mult[%zu] is not positive", i);
+    }
+    if (cfg->prior_scale_w && cfg->prior_kind != NPBNN_PRIOR_UNIFORM)
+        for (int i = 0; i < ctx->n_weights; ++i)
+            if (!(cfg->prior_scale_w[i] > 0.0)) return fail(ctx, NPBNN_E_ARG, "chain_run: prior_scale_w[%d] is not positive", i);
+    if (cfg->slope_idx || cfg->slope_delta) {          // trainable activation slopes
+        if (!cfg->slope_idx || !cfg->slope_delta || cfg->n_slopes < 1 || cfg->n_slopes > kMaxLayers || cfg->n_slopes != ctx->net.n_layers - 1)
+            return fail(ctx, NPBNN_E_ARG, "chain_run: slope_idx and slope_delta go together, with one slope per hidden layer (got %d for %d layers)",
+                        cfg->n_slopes, ctx->net.n_layers);
+        if (ctx->net.slope_off < 0) return fail(ctx, NPBNN_E_STATE, "chain_run: trainable slopes need NPBNN_OPT_TRAINABLE_SLOPES");
+        if (A.seg_len > 0 || A.group_blocks > 0) return fail(ctx, NPBNN_E_ARG, "chain_run: trainable slopes run in plain batches only");
+        for (int t = 0; t < K; ++t)
+            if (cfg->slope_idx[t] < 0 || cfg->slope_idx[t] >= cfg->n_slopes) return fail(ctx, NPBNN_E_ARG, "chain_run: slope_idx[%d] out of range", t);
+    }
+    return NPBNN_OK;
+}
+
+// stage 2: the launch, and the schedule its passes run on (npbnn_sched_plan.h: the rule reads neither the plan nor the environment)
+int prepare_plan(npbnn_ctx* ctx, const ChainArgs& A, ChainBatch* B) {
+    const npbnn_chain_cfg* cfg = A.cfg;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     LaunchPlan& lp = B->lp;
     int want_cand = cfg->n_candidates;
     if (want_cand < 1) want_cand = kMaxCand;            // 0 = as many as fit
-    if (group_blocks > 0) want_cand = 1;
+    if (A.group_blocks > 0) want_cand = 1;
     if (cfg->slope_idx && ctx->wide) want_cand = 1;      // (weight-streamed path: candidates with slopes of their own travel one per pass)
-    rc = plan_launch(ctx, 0, &lp, cfg->force_f32, want_cand, false, true);
+    const int rc = plan_launch(ctx, 0, &lp, cfg->force_f32, want_cand, false, true);
     if (rc) return rc;
-    const int D = lp.n_cand;
-    const bool sharded = ctx->shard_n > 0;
-    if (sharded && (group_blocks > 0 || seg_len > 0))
-        return fail(ctx, NPBNN_E_STATE, "chain_run: a context whose rows are split over ranks runs plain batches only (no group pass, no exchange run)");
-    // schedule: overlapping the decision of a pass with the evaluation of the next pays as long as most passes reject everything
-    if (lp.wide && group_blocks > 0)
+    if (lp.wide && A.group_blocks > 0)
         return fail(ctx, NPBNN_E_STATE, "chain_run: a network on the weight-streamed path carries one weight set per pass (no group pass)");
-    // (row shards: a gather between pass and step; weight-streamed path: the candidate image is patched between step and pass)
-    int schedule = group_blocks > 0 ? NPBNN_SCHED_OVERLAP : (sharded || lp.wide) ? NPBNN_SCHED_SERIAL : cfg->schedule;
-    if (schedule != NPBNN_SCHED_SERIAL && schedule != NPBNN_SCHED_OVERLAP && schedule != NPBNN_SCHED_OVERLAP2 && schedule != NPBNN_SCHED_PERSIST &&
-        schedule != NPBNN_SCHED_PERSIST_SERIAL) {
-        const double p_acc = ctx->accept_rate < 0 ? 0.0 : ctx->accept_rate;
-        // (measured, config-2 shapes, tools/stress_schedules.py 10000 1 2 4: up to 34 % of the proposals accepted - 71 % of the passes -
-        // the overlapped forms lead, 48-63 k against 45-50 k it/s; config 4 at 46 % / 84 %: serial 18.8 k against 17.4-18.4 k)
-        schedule = (1.0 - std::pow(1.0 - p_acc, D)) < 0.75 ? NPBNN_SCHED_OVERLAP : NPBNN_SCHED_SERIAL;
-        // Where overlapping pays and the chain has the GPU to itself, the persistent form of it: one launch whose workgroups loop
-        // over the passes (no launch boundary between passes; a workgroup that is through with pass L starts pass L + 1 while
-        // others still finish L).  Its device-side waits only need the launch's workgroups resident together - one per compute
-        // unit, at most as many as there are - and are bounded: a time-out ends the batch with NPBNN_E_SYNC, state untouched, and
-        // the context stays on kernel boundaries from then on.  (The two-stream form, NPBNN_SCHED_OVERLAP2, is never picked here:
-        // it also needs the two streams on hardware queues of their own, which nothing promises.)
-        if (schedule == NPBNN_SCHED_OVERLAP && alone_on_device && seg_len == 0 && !ctx->sync_failed && ctx->persist_option)
-            schedule = NPBNN_SCHED_PERSIST;
-        // A chain that moves: in the overlapped forms every pass that accepts something voids the pass in flight behind it (at 28 %
-        // acceptance 63 % of the passes do), and on kernel boundaries a decision between two passes costs a step kernel and two
-        // boundaries.  The persistent launch with the decision between the passes (NPBNN_SCHED_PERSIST_SERIAL) wastes no pass and
-        // decides in a few microseconds: it leads where the predicted cost per decided pass says so (npbnn_ctx.hip.h, kSpecTurnExtraUs).
-        // (its step workgroup must keep pace with the evaluation: with proposals much wider than a few hundred weights it does not)
-        if (alone_on_device && seg_len == 0 && !ctx->sync_failed && ctx->persist_option && p_acc > 0.0 && group_blocks == 0 &&
-            !cfg->slope_idx && M <= kPersistSerialMaxWidth && lp.fn_spec != nullptr &&
-            (cfg->prior_kind == NPBNN_PRIOR_UNIFORM || (cfg->prior_kind == NPBNN_PRIOR_NORMAL && !cfg->prior_scale_w))) {
-            // What decides is what a form was MEASURED to cost per iteration on this chain (npbnn_ctx.it_us: a batch's time over its
-            // iterations); the model - a decided pass costs (1 + a) turns overlapped, a turn + `extra` with the decision between the
-            // passes - only prices the form that has not run yet from the one that has.
-            const double a = 1.0 - std::pow(1.0 - p_acc, D);                 // share of the passes that accept something
-            const double ipp = a / p_acc;                                    // iterations a decided pass settles: 1 + (1-p) + ... + (1-p)^(D-1)
-            const double extra = kSpecTurnExtraUs + kSpecTurnExtraUsPerWeight * M;
-            const int kc = K < kShortBatch ? 0 : 1;                          // (a form's fixed cost per batch differs: short and long batches apart)
-            double c_over = ctx->it_us[0][kc], c_ser = ctx->it_us[1][kc];    // us per iteration
-            if (c_over <= 0.0 && c_ser <= 0.0) c_over = kTurnUsGuess * (1.0 + a) / ipp;
-            if (c_over <= 0.0) {
-                const double t_over = c_ser * ipp - extra > 5.0 ? c_ser * ipp - extra : 5.0;
-                c_over = t_over * (1.0 + a) / ipp;
-            }
-            if (c_ser <= 0.0) c_ser = (c_over * ipp / (1.0 + a) + extra) / ipp;
-            // (3 % in favour of the form the chain is on: no flipping on noise)
-            const bool on_serial = ctx->last_schedule == NPBNN_SCHED_PERSIST_SERIAL;
-            if (c_ser * (on_serial ? 0.97 : 1.03) < c_over) schedule = NPBNN_SCHED_PERSIST_SERIAL;
-            // a measured cost goes stale while the other form runs (the chain's acceptance rate moves, the box's clocks do): after
-            // kTurnReprobeBatches batches on one form, one batch on the other - if it is within reach or was never run
-            // (a form's first batch in a size class pays for the switch - other builds of the kernel, cold tables: it runs a second one
-            // before its figure is held against the other's)
-            if (ctx->it_n[0][kc] == 1) schedule = NPBNN_SCHED_PERSIST;
-            else if (ctx->it_n[1][kc] == 1) schedule = NPBNN_SCHED_PERSIST_SERIAL;
-            const int other = schedule == NPBNN_SCHED_PERSIST_SERIAL ? 0 : 1;
-            // (a form never measured in this size class gets its batch after a handful on the other: the model is a prior, not a verdict -
-            // it prices every accept of the overlapped form at a whole pass in vain, and such a pass is cut short)
-            const int since = ctx->turn_batches[other][kc];
-            const bool never = ctx->it_us[other][kc] <= 0.0;
-            if (since >= (never ? kTurnFirstProbeBatches : kTurnReprobeBatches)) {
-                const double ratio = other == 1 ? c_ser / c_over : c_over / c_ser;
-                // A form that has run: within a factor two, that is - its figure dates from when it last ran, the chain's acceptance rate has
-                // moved since, and with it both forms' costs; one batch in kTurnReprobeBatches costs a per cent at worst.  A form never
-                // run: when the model puts it within kFirstProbeWithin of the running one (at a few per cent acceptance the decision between
-                // the passes is predicted a fifth to a third dearer, and is: two batches on it would be two batches lost - a chain's first
-                // dispatches are where short runs are timed) - and whatever the model says after kTurnForcedProbeBatches, so that a wrong
-                // model cannot park a chain for good.
-                const bool probe = never ? (ratio < kFirstProbeWithin || since >= kTurnForcedProbeBatches) : ratio < 2.0;
-                if (probe || !never) ctx->turn_batches[other][kc] = 0;
-                if (probe) schedule = other == 1 ? NPBNN_SCHED_PERSIST_SERIAL : NPBNN_SCHED_PERSIST;
-            }
-        }
-    }
-    if ((schedule == NPBNN_SCHED_OVERLAP2 || schedule == NPBNN_SCHED_PERSIST) && ctx->sync_failed) schedule = NPBNN_SCHED_OVERLAP;
-    // (asked for by name where it cannot run - no build with the speculative step for this launch, another prior, trainable slopes, a
-    // shared GPU: the persistent overlapped form where that can, else kernel boundaries)
-    // (the evaluating workgroups' tagged sums of that schedule sit in kSpecPartSlots slots per value, and the step reads exactly that
-    // many: a part with more compute units than slots - none today: 256 of each on gfx950 - stays on the overlapped form)
-    const int eval_wgs = lp.grid > ctx->n_cu - 1 ? ctx->n_cu - 1 : lp.grid;
-    if (schedule == NPBNN_SCHED_PERSIST_SERIAL &&
-        (eval_wgs > kSpecPartSlots || ctx->sync_failed || !alone_on_device || seg_len > 0 || group_blocks > 0 || lp.fn_spec == nullptr || cfg->slope_idx || getenv("NPBNN_NO_SPEC_STEP") ||
-         !(cfg->prior_kind == NPBNN_PRIOR_UNIFORM || (cfg->prior_kind == NPBNN_PRIOR_NORMAL && !cfg->prior_scale_w))))
-        schedule = (alone_on_device && seg_len == 0 && !ctx->sync_failed && group_blocks == 0) ? NPBNN_SCHED_PERSIST : NPBNN_SCHED_OVERLAP;
-    // the persistent form needs every workgroup of its launch resident at once: one per compute unit at most, the GPU to itself, and
-    // a plain run (an exchange run's kernels go between the passes)
-    // (its grid is at most one workgroup per compute unit: the evaluating workgroups are capped at n_cu - 1 below, plus the step's)
-    if (schedule == NPBNN_SCHED_PERSIST && (!alone_on_device || seg_len > 0)) schedule = NPBNN_SCHED_OVERLAP;
-    const bool pserial = schedule == NPBNN_SCHED_PERSIST_SERIAL;
-    const bool persist = schedule == NPBNN_SCHED_PERSIST || pserial;
-    const bool overlap = schedule == NPBNN_SCHED_OVERLAP || schedule == NPBNN_SCHED_OVERLAP2 || persist;
-    const bool sync = (schedule == NPBNN_SCHED_OVERLAP2 && alone_on_device) || persist;   // (several chains on one GPU: one stream each)
-    if (schedule == NPBNN_SCHED_OVERLAP2 && !sync) schedule = NPBNN_SCHED_OVERLAP;
+    const int eval_wgs = lp.grid > ctx->n_cu - 1 ? ctx->n_cu - 1 : lp.grid;      // one workgroup of an overlapped launch runs the step: the others share the tiles
+    npbnn_sched_req r;
+    r.asked = cfg->schedule; r.D = lp.n_cand; r.K = A.K; r.M = A.M; r.eval_wgs = eval_wgs;
+    r.alone = A.alone_on_device; r.plain = A.seg_len == 0; r.group = A.group_blocks > 0; r.boundaries_only = ctx->shard_n > 0 || lp.wide;
+    r.sync_failed = ctx->sync_failed; r.persist_option = ctx->persist_option != 0;
+    r.has_spec_build = lp.fn_spec != nullptr; r.own_slopes = cfg->slope_idx != nullptr; r.no_spec_step = getenv("NPBNN_NO_SPEC_STEP") != nullptr;
+    r.prior_fits_spec = cfg->prior_kind == NPBNN_PRIOR_UNIFORM || (cfg->prior_kind == NPBNN_PRIOR_NORMAL && !cfg->prior_scale_w);
+    const npbnn_sched_choice c = npbnn_sched_choose(&r, &ctx->sched);
+    B->D = lp.n_cand; B->schedule = c.schedule; B->persist = c.persist; B->overlap = c.overlap; B->spec = c.spec;
+    B->sync = c.sync && !c.persist;          // (two launch streams to fork and join)
     if (!ctx->stream_e[0]) {      // (with the chain's first batch, whatever its schedule: creating a stream takes milliseconds)
         for (int i = 0; i < 2; ++i) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream_e[i], hipStreamNonBlocking));
     }
-    if (overlap) {                      // one workgroup of the launch runs the step: the others share the tiles
-        int g = lp.grid;
-        if (g > ctx->n_cu - 1) g = ctx->n_cu - 1;
-        if (g < 1) g = 1;
-        lp.grid = g;
-        lp.n_waves = g;
-    }
-    if (group_blocks > 0) { lp.grid = group_blocks; lp.n_waves = group_blocks; }
-    rc = ensure_work_buffers(ctx, lp.n_waves);
+    if (B->overlap) lp.grid = lp.n_waves = eval_wgs < 1 ? 1 : eval_wgs;
+    if (A.group_blocks > 0) { lp.grid = A.group_blocks; lp.n_waves = A.group_blocks; }
+    if (B->spec) lp.fn = lp.fn_spec;       // (the builds that carry spec_rounds)      // prepare the next pass ahead for every outcome
+    return NPBNN_OK;
+}
+
+// stage 3: room for everything the batch puts on the device (the spec buffers' pass tags are cleared here, before they could repeat)
+int prepare_reserve(npbnn_ctx* ctx, const ChainArgs& A, ChainBatch* B) {
+    const npbnn_chain_cfg* cfg = A.cfg;
+    const int K = A.K, M = A.M;
+    const LaunchPlan& lp = B->lp;
+    int rc = ensure_work_buffers(ctx, lp.n_waves);
     if (rc) return rc;
-    const size_t wb = (size_t)ctx->n_weights * sizeof(double);
+    const size_t wb = B->wb = (size_t)ctx->n_weights * sizeof(double);
     if ((size_t)K > ctx->res_k || (size_t)ctx->n_weights != ctx->res_nw) {
         size_t kc = (size_t)K > ctx->res_k ? (size_t)K : ctx->res_k;
         if (kc < kChainMinCapacity) kc = kChainMinCapacity;
@@ -250,7 +206,7 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
         ctx->res_k = kc; ctx->res_nw = (size_t)ctx->n_weights;
         char* b = ctx->d_res;
         ctx->d_chain = reinterpret_cast<ChainDev*>(b);
-        ctx->d_chain_ovf = reinterpret_cast<int*>(b + 448);
+        ctx->d_chain_ovf = reinterpret_cast<int*>(b + kResFlagWord);
         ctx->d_wcur = reinterpret_cast<double*>(b + L.w);
         ctx->d_cnt = reinterpret_cast<int*>(b + L.cnt);
         ctx->d_logu = reinterpret_cast<double*>(b + L.logu);
@@ -258,13 +214,10 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
         ctx->d_llp = reinterpret_cast<double*>(b + L.llp);
         ctx->d_lpp = reinterpret_cast<double*>(b + L.lpp);
     }
-    const ResLayout RL = res_layout(ctx->res_k, wb);
-    static_assert(sizeof(ChainDev) <= 448, "ChainDev must fit its slot of the result block");
-    if (mask_packed && (rc = ctx->d_mask.reserve(ctx, (size_t)ctx->n_weights))) return rc;
+    B->RL = res_layout(ctx->res_k, wb);
+    if (A.mask_packed && (rc = ctx->d_mask.reserve(ctx, (size_t)ctx->n_weights))) return rc;
     if ((rc = ctx->d_pv.reserve(ctx, (size_t)2 * kMaxCand * M))) return rc;
-    const bool spec = pserial;             // (every condition was checked where the schedule was fixed)
-    if (spec) lp.fn = lp.fn_spec;          // (the builds that carry spec_rounds)      // prepare the next pass ahead for every outcome
-    if (spec) {
+    if (B->spec) {
         bool touch_new = false, part_new = false;
         if ((rc = ctx->d_spec.reserve(ctx, 1)) || (rc = ctx->d_spec_pv.reserve(ctx, (size_t)3 * kSpecOutcomes * kMaxCand * M)) ||
             (rc = ctx->d_spec_touch.reserve(ctx, (size_t)kMaxCand * ctx->n_weights * 4, 0, &touch_new)) ||
@@ -280,132 +233,129 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
     const size_t need = (size_t)K * M;
     {   // room for K x M draws, and when it grows, for at least kChainMinCapacity iterations of M
         const size_t cap = need > (size_t)kChainMinCapacity * M ? need : (size_t)kChainMinCapacity * M;
-        const auto idx_ints = [](size_t n) { return (n * (sizeof(int) + sizeof(double)) + 512) / sizeof(int); };   // (indices, then the deviates: see below)
+        const auto idx_ints = [](size_t n) { return (n * (sizeof(int) + sizeof(double)) + 512) / sizeof(int); };   // (indices, then the deviates: see prepare_upload)
         if ((rc = ctx->d_idx.reserve(ctx, idx_ints(need), idx_ints(cap))) || (rc = ctx->d_pos.reserve(ctx, need, cap)) ||
             (rc = ctx->d_pscale.reserve(ctx, need, cap)))
             return rc;
     }
-    ctx->d_delta = reinterpret_cast<double*>(reinterpret_cast<char*>(ctx->d_idx.get()) + ((size_t)K * M * sizeof(int) + 255) / 256 * 256);
-    hipStream_t st = ctx->stream;
-    double t_stage = wall_us();
-    stage_mark(ctx, "(host set-up so far)", &t_stage);
-    if (mask_packed) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mask, mask_packed, wb, hipMemcpyHostToDevice, st));
-    // indices and deviates: ONE copy when the caller laid them out the way the device holds them (idx, then delta at the next
-    // multiple of 256 bytes - npbnn_amd's pre-draw does), else one each
-    const size_t idx_bytes = need * sizeof(int), delta_off = (idx_bytes + 255) / 256 * 256;
-    if (reinterpret_cast<const char*>(delta) == reinterpret_cast<const char*>(idx) + delta_off) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_idx, idx, delta_off + need * sizeof(double), hipMemcpyHostToDevice, st));
-    } else {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_idx, idx, idx_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_delta, delta, need * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    stage_mark(ctx, "copy of indices + deviates", &t_stage);
-    const bool f16 = ctx->net.l0_f16 != 0;
-    ChainDev init{};
-    init.logLik = cfg->cur_loglik;
-    init.logPrior = cfg->cur_logprior;
-    init.logPrior_rep = cfg->cur_logprior;
-    for (int j = 0; j < NPBNN_MAX_TARGETS; ++j) init.sigma[j] = cfg->cur_sigma[j];
-    init.t = 0;
-    init.n_accepted = 0;
-    init.n_passes = 0;
-    init.void_launch = -2;
-    init.n_void = 0;
-    init.seg_end = (seg_len > 0 && seg_len < K) ? seg_len : K;
-    init.temperature = cfg->temperature;
-    init.seg_idx = 0;
-    init.poisoned = 0;
-    init.prepared = -1;             // (the first step kernel raises it to 0)
-    init.aborted = 0;
-    init.started = -1;
-    init.exchanged = 0;
-    for (int i = 0; i < 4; ++i) init.done[i] = 0;
-    {   // initial chain state, overflow flag, weights and the per-iteration scalars travel together (head of the block)
-        memset(ctx->h_res, 0, 512);
-        memcpy(ctx->h_res, &init, sizeof(ChainDev));
-        memcpy(ctx->h_res + RL.w, W_in, wb);
-        memcpy(ctx->h_res + RL.cnt, cnt, (size_t)K * sizeof(int));
-        memcpy(ctx->h_res + RL.logu, log_u, (size_t)K * sizeof(double));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_res, ctx->h_res, RL.acc, hipMemcpyHostToDevice, st));
-    }
-    stage_mark(ctx, "copy of state + weights", &t_stage);
-    // activation slopes of the batch: fixed ones (ActFun("genReLU", prm=...): cfg->cur_slopes with no slope draws) go into the network
-    // description every candidate reads; trainable ones travel per candidate in the weight image (slope_idx below)
-    for (int l = 0; l < kMaxLayers; ++l)
-        ctx->net.act_prm[l] = (!cfg->slope_idx && l < cfg->n_slopes && l < NPBNN_MAX_LAYERS) ? (float)cfg->cur_slopes[l] : 0.f;
-    ChainParams c{};
-    c.st = ctx->d_chain;
-    c.pass = reinterpret_cast<PassDesc*>(reinterpret_cast<char*>(ctx->d_eparams) + offsetof(EvalParams, pass_desc));   // inside the evaluation's block
-    c.w_cur = ctx->d_wcur;
-    c.mask = mask_packed ? ctx->d_mask : nullptr;
-    c.idx = ctx->d_idx;
-    c.delta = ctx->d_delta;
-    c.cnt = ctx->d_cnt;
-    c.log_u = ctx->d_logu;
-    c.hastings = nullptr;
-    c.sigma_mult = nullptr;
-    if (cfg->sigma_mult || cfg->hastings) {
-        if (!cfg->sigma_mult || !cfg->hastings || lik != NPBNN_LIK_GAUSS)
-            return fail(ctx, NPBNN_E_ARG, "chain_run: sigma_mult and hastings go together, with the Gaussian likelihood");
-        const int kt = ctx->net.k_targets;
-        const size_t cap = (size_t)K > kChainMinCapacity ? (size_t)K : kChainMinCapacity;
-        if ((rc = ctx->d_smult.reserve(ctx, (size_t)K * NPBNN_MAX_TARGETS, cap * NPBNN_MAX_TARGETS)) || (rc = ctx->d_hast.reserve(ctx, (size_t)K, cap)))
-            return rc;
-        for (size_t i = 0; i < (size_t)K * kt; ++i)
-            if (!(cfg->sigma_mult[i] > 0.0)) return fail(ctx, NPBNN_E_ARG, "chain_run: sigma_mult[%zu] is not positive", i);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_smult, cfg->sigma_mult, (size_t)K * kt * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_hast, cfg->hastings, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
-        c.sigma_mult = ctx->d_smult;
-        c.hastings = ctx->d_hast;
-    }
-    c.out_acc = ctx->d_acc;
-    c.out_ll = ctx->d_llp;
-    c.out_lp = ctx->d_lpp;
-    c.partials = sharded ? ctx->d_shard_part : ctx->d_partials;
-    c.image = ctx->d_image;
-    // (weight-streamed path: the step keeps the candidate image itself while a proposal fits its staged entries; wider ones get two
-    // launches over all compute units between step and pass - wide_cand_sync)
-    c.cand_image = (lp.wide && M <= kWideStepPatchMax && D == 1) ? ctx->d_wide_cand : nullptr;
-    // ... and where those launches run anyway they also MAKE the candidates (values, prior terms: wide_cand_prepare_kernel) - one
-    // workgroup's walk over 3 x 2.6 k entries is 24 us of a 37-us step.  Plain batches without slopes of their own only (an exchange
-    // run stops a chain at the proposal that leaves the fp16 range: the step must see that flag when it prepares).
-    c.prep_terms = nullptr;
-    B->make_cands = false;
-    if (lp.wide && !c.cand_image && seg_len == 0 && !cfg->slope_idx && !getenv("NPBNN_WIDE_STEP_MAKES")) {
-        if ((rc = ctx->d_prep_terms.reserve(ctx, (size_t)kMaxCand * M))) return rc;
-        c.prep_terms = ctx->d_prep_terms;
-        B->make_cands = true;
-    }
-    c.pos = ctx->d_pos;
-    c.pscale = f16 ? ctx->d_pscale : nullptr;
-    c.pv = spec ? ctx->d_spec_pv : ctx->d_pv;      // (spec: the first step writes pass 0 into slot (parity 0, outcome 0))
-    c.spec = nullptr;
-    c.spec_pv = nullptr;
-    c.spec_touch = nullptr;
-    c.spec_part = nullptr;
-    c.n_weights_spec = ctx->n_weights;
-    c.spec_gen = 0;
-    if (spec) {
-        c.spec = ctx->d_spec;
-        c.spec_pv = ctx->d_spec_pv;
-        c.spec_touch = ctx->d_spec_touch;
-        c.spec_part = ctx->d_spec_part;
-        c.spec_gen = (int)ctx->spec_gen;
-        ctx->spec_gen += (unsigned)K + 8u;             // (a pass decides at least one iteration)
-    }
-    c.overflow = ctx->d_chain_ovf;
+    ctx->d_delta = reinterpret_cast<double*>(reinterpret_cast<char*>(ctx->d_idx.get()) + (need * sizeof(int) + 255) / 256 * 256);
+    const size_t cap = (size_t)K > kChainMinCapacity ? (size_t)K : kChainMinCapacity;     // the optional per-iteration arrays
+    if (cfg->sigma_mult && ((rc = ctx->d_smult.reserve(ctx, (size_t)K * NPBNN_MAX_TARGETS, cap * NPBNN_MAX_TARGETS)) || (rc = ctx->d_hast.reserve(ctx, (size_t)K, cap))))
+        return rc;
+    if (cfg->prior_scale_w && cfg->prior_kind != NPBNN_PRIOR_UNIFORM && (rc = ctx->d_pscale_w.reserve(ctx, (size_t)ctx->n_weights))) return rc;
+    if (cfg->slope_idx && ((rc = ctx->d_sidx.reserve(ctx, (size_t)K, cap)) || (rc = ctx->d_sdelta.reserve(ctx, (size_t)K, cap)) || (rc = ctx->d_slopes.reserve(ctx, 1))))
+        return rc;
+    // Weight-streamed path: the step keeps the candidate image itself while a proposal fits its staged entries (ChainParams::cand_image);
+    // wider ones get two launches over all compute units between step and pass - wide_cand_sync - and where those launches run anyway
+    // they also MAKE the candidates (values, prior terms: wide_cand_prepare_kernel) - one workgroup's walk over 3 x 2.6 k entries is
+    // 24 us of a 37-us step.  Plain batches without slopes of their own only (an exchange run stops a chain at the proposal that
+    // leaves the fp16 range: the step must see that flag when it prepares).
+    B->step_keeps_image = lp.wide && M <= kWideStepPatchMax && B->D == 1;
+    B->make_cands = lp.wide && !B->step_keeps_image && A.seg_len == 0 && !cfg->slope_idx && !getenv("NPBNN_WIDE_STEP_MAKES");
+    if (B->make_cands && (rc = ctx->d_prep_terms.reserve(ctx, (size_t)kMaxCand * M))) return rc;
     if (getenv("NPBNN_STEP_STAMPS")) {      // diagnostics: per-phase wall-clock stamps of the step kernel
         if ((rc = B->d_stamps.reserve(ctx, 1024 * 8))) return rc;
         HIP_TRY(ctx, hipMemset(B->d_stamps, 0, 1024 * 8 * sizeof(unsigned long long)));
     }
-    c.stamps = B->d_stamps;
-    c.K = K;
-    c.M = M;
-    c.D = D;
+    if (getenv("NPBNN_EVAL_STAMPS") && A.group_blocks == 0) {
+        if ((rc = B->d_estamps.reserve(ctx, (size_t)(lp.grid + 1) * 32))) return rc;
+        HIP_TRY(ctx, hipMemset(B->d_estamps, 0, (size_t)(lp.grid + 1) * 32 * sizeof(unsigned long long)));
+    }
+    return NPBNN_OK;
+}
+
+// the state a batch starts from
+ChainDev initial_state(const ChainArgs& A) {
+    ChainDev init{};                // (counters, flags and done[] start at zero)
+    init.logLik = A.cfg->cur_loglik;
+    init.logPrior = A.cfg->cur_logprior;
+    init.logPrior_rep = A.cfg->cur_logprior;
+    for (int j = 0; j < NPBNN_MAX_TARGETS; ++j) init.sigma[j] = A.cfg->cur_sigma[j];
+    init.void_launch = -2;
+    init.seg_end = (A.seg_len > 0 && A.seg_len < A.K) ? A.seg_len : A.K;
+    init.temperature = A.cfg->temperature;
+    init.prepared = -1;             // (the first step kernel raises it to 0)
+    init.started = -1;
+    return init;
+}
+
+// stage 4: the draws, the head of the result block, the optional arrays
+int prepare_upload(npbnn_ctx* ctx, const ChainArgs& A, const ChainBatch& B, double* t_stage) {
+    const npbnn_chain_cfg* cfg = A.cfg;
+    const int K = A.K;
+    const size_t need = (size_t)K * A.M;
+    hipStream_t st = ctx->stream;
+    if (A.mask_packed) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_mask, A.mask_packed, B.wb, hipMemcpyHostToDevice, st));
+    // indices and deviates: ONE copy when the caller laid them out the way the device holds them (idx, then delta at the next
+    // multiple of 256 bytes - npbnn_amd's pre-draw does), else one each
+    const size_t idx_bytes = need * sizeof(int), delta_off = (idx_bytes + 255) / 256 * 256;
+    if (reinterpret_cast<const char*>(A.delta) == reinterpret_cast<const char*>(A.idx) + delta_off) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_idx, A.idx, delta_off + need * sizeof(double), hipMemcpyHostToDevice, st));
+    } else {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_idx, A.idx, idx_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_delta, A.delta, need * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    stage_mark(ctx, "copy of indices + deviates", t_stage);
+    {   // initial chain state, overflow flag, weights and the per-iteration scalars travel together (head of the block)
+        const ChainDev init = initial_state(A);
+        memset(ctx->h_res, 0, 512);
+        memcpy(ctx->h_res, &init, sizeof(ChainDev));
+        memcpy(ctx->h_res + B.RL.w, A.W_in, B.wb);
+        memcpy(ctx->h_res + B.RL.cnt, A.cnt, (size_t)K * sizeof(int));
+        memcpy(ctx->h_res + B.RL.logu, A.log_u, (size_t)K * sizeof(double));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_res, ctx->h_res, B.RL.acc, hipMemcpyHostToDevice, st));
+    }
+    stage_mark(ctx, "copy of state + weights", t_stage);
+    if (cfg->sigma_mult) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_smult, cfg->sigma_mult, (size_t)K * ctx->net.k_targets * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_hast, cfg->hastings, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (cfg->prior_scale_w && cfg->prior_kind != NPBNN_PRIOR_UNIFORM)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pscale_w, cfg->prior_scale_w, B.wb, hipMemcpyHostToDevice, st));
+    if (cfg->slope_idx) {
+        SlopeState init_s{};
+        for (int l = 0; l < cfg->n_slopes; ++l) init_s.cur[l] = cfg->cur_slopes[l];
+        // (pageable sources: the copies are staged by the runtime before the calls return)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_slopes, &init_s, sizeof(SlopeState), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sidx, cfg->slope_idx, (size_t)K * sizeof(int), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sdelta, cfg->slope_delta, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    return NPBNN_OK;
+}
+
+// stage 5: the two parameter blocks.  What ChainParams c{} leaves at zero: no sigma multipliers, Hastings terms, per-weight prior
+// scales, slopes of their own, prepared prior terms or speculative step unless the batch has them
+void fill_chain_params(npbnn_ctx* ctx, const ChainArgs& A, const ChainBatch& B, ChainParams& c) {
+    const npbnn_chain_cfg* cfg = A.cfg;
+    const LaunchPlan& lp = B.lp;
+    const bool sharded = ctx->shard_n > 0, f16 = ctx->net.l0_f16 != 0;
+    c.st = ctx->d_chain;
+    c.pass = reinterpret_cast<PassDesc*>(reinterpret_cast<char*>(ctx->d_eparams) + offsetof(EvalParams, pass_desc));   // inside the evaluation's block
+    c.w_cur = ctx->d_wcur;
+    c.mask = A.mask_packed ? ctx->d_mask : nullptr;
+    c.idx = ctx->d_idx; c.delta = ctx->d_delta; c.cnt = ctx->d_cnt; c.log_u = ctx->d_logu;
+    if (cfg->sigma_mult) { c.sigma_mult = ctx->d_smult; c.hastings = ctx->d_hast; }
+    c.out_acc = ctx->d_acc; c.out_ll = ctx->d_llp; c.out_lp = ctx->d_lpp;
+    c.partials = sharded ? ctx->d_shard_part : ctx->d_partials;
+    c.image = ctx->d_image;
+    c.cand_image = B.step_keeps_image ? ctx->d_wide_cand : nullptr;
+    c.prep_terms = B.make_cands ? ctx->d_prep_terms : nullptr;
+    c.pos = ctx->d_pos;
+    c.pscale = f16 ? ctx->d_pscale : nullptr;
+    c.pv = B.spec ? ctx->d_spec_pv : ctx->d_pv;      // (spec: the first step writes pass 0 into slot (parity 0, outcome 0))
+    c.n_weights_spec = ctx->n_weights;
+    if (B.spec) {
+        c.spec = ctx->d_spec; c.spec_pv = ctx->d_spec_pv; c.spec_touch = ctx->d_spec_touch; c.spec_part = ctx->d_spec_part;
+        c.spec_gen = (int)ctx->spec_gen;
+        ctx->spec_gen += (unsigned)A.K + 8u;           // (a pass decides at least one iteration)
+    }
+    c.overflow = ctx->d_chain_ovf;
+    c.stamps = B.d_stamps;
+    c.K = A.K; c.M = A.M; c.D = B.D;
     c.n_blocks = sharded ? ctx->shard_n : lp.n_waves;      // (row shards: one record per rank, gathered)
-    c.stop_on_overflow = seg_len > 0 ? 1 : 0;
+    c.stop_on_overflow = A.seg_len > 0 ? 1 : 0;
     c.sync_test_skip = -1;
-    if (sync && ctx->debug_sync_skip >= 0) {       // (npbnn_debug_sync_skip_: provoke the time-out of the two-stream schedule, once)
+    if ((B.sync || B.persist) && ctx->debug_sync_skip >= 0) {       // (npbnn_debug_sync_skip_: provoke the time-out of the two-stream schedule, once)
         c.sync_test_skip = ctx->debug_sync_skip;
         ctx->debug_sync_skip = -1;
     }
@@ -414,80 +364,66 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
         c.prior_scale[l] = cfg->prior_scale[l];
         c.half_inv_s2[l] = cfg->prior_scale[l] > 0 ? 0.5 / (cfg->prior_scale[l] * cfg->prior_scale[l]) : 0.0;
     }
-    c.prior_scale_w = nullptr;
-    if (cfg->prior_scale_w && cfg->prior_kind != NPBNN_PRIOR_UNIFORM) {
-        for (int i = 0; i < ctx->n_weights; ++i)
-            if (!(cfg->prior_scale_w[i] > 0.0)) return fail(ctx, NPBNN_E_ARG, "chain_run: prior_scale_w[%d] is not positive", i);
-        if ((rc = ctx->d_pscale_w.reserve(ctx, (size_t)ctx->n_weights))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pscale_w, cfg->prior_scale_w, wb, hipMemcpyHostToDevice, st));
-        c.prior_scale_w = ctx->d_pscale_w;
-    }
-    c.slopes = nullptr;
-    c.slope_idx = nullptr;
-    c.slope_delta = nullptr;
-    c.n_slopes = 0;
-    c.slope_term_in = 0;
-    ctx->batch_slopes = false;
-    if (cfg->slope_idx || cfg->slope_delta) {          // trainable activation slopes
-        if (!cfg->slope_idx || !cfg->slope_delta || cfg->n_slopes < 1 || cfg->n_slopes > kMaxLayers || cfg->n_slopes != ctx->net.n_layers - 1)
-            return fail(ctx, NPBNN_E_ARG, "chain_run: slope_idx and slope_delta go together, with one slope per hidden layer (got %d for %d layers)",
-                        cfg->n_slopes, ctx->net.n_layers);
-        if (ctx->net.slope_off < 0) return fail(ctx, NPBNN_E_STATE, "chain_run: trainable slopes need NPBNN_OPT_TRAINABLE_SLOPES");
-        if (seg_len > 0 || group_blocks > 0) return fail(ctx, NPBNN_E_ARG, "chain_run: trainable slopes run in plain batches only");
-        for (int t = 0; t < K; ++t)
-            if (cfg->slope_idx[t] < 0 || cfg->slope_idx[t] >= cfg->n_slopes) return fail(ctx, NPBNN_E_ARG, "chain_run: slope_idx[%d] out of range", t);
-        const size_t cap = (size_t)K > kChainMinCapacity ? (size_t)K : kChainMinCapacity;
-        if ((rc = ctx->d_sidx.reserve(ctx, (size_t)K, cap)) || (rc = ctx->d_sdelta.reserve(ctx, (size_t)K, cap)) || (rc = ctx->d_slopes.reserve(ctx, 1)))
-            return rc;
-        SlopeState init_s{};
-        for (int l = 0; l < cfg->n_slopes; ++l) init_s.cur[l] = cfg->cur_slopes[l];
-        // (pageable sources: the copies are staged by the runtime before the calls return)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_slopes, &init_s, sizeof(SlopeState), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sidx, cfg->slope_idx, (size_t)K * sizeof(int), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sdelta, cfg->slope_delta, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
-        c.slopes = ctx->d_slopes;
-        c.slope_idx = ctx->d_sidx;
-        c.slope_delta = ctx->d_sdelta;
+    if (cfg->prior_scale_w && cfg->prior_kind != NPBNN_PRIOR_UNIFORM) c.prior_scale_w = ctx->d_pscale_w;
+    if (cfg->slope_idx) {
+        c.slopes = ctx->d_slopes; c.slope_idx = ctx->d_sidx; c.slope_delta = ctx->d_sdelta;
         c.n_slopes = cfg->n_slopes;
         c.slope_term_in = cfg->slope_term_in_prior ? 1 : 0;
-        ctx->batch_slopes = true;
     }
-    c.w_bound = cfg->w_bound;
-    c.lik_temp = cfg->lik_temp;
-    c.sigma_given = cfg->sigma_given;
+    c.w_bound = cfg->w_bound; c.lik_temp = cfg->lik_temp; c.sigma_given = cfg->sigma_given;
     for (int j = 0; j < NPBNN_MAX_TARGETS; ++j) c.sigma_fixed[j] = cfg->sigma[j];
-    c.n_rows = sharded ? ctx->shard_rows_total : d.m->n_rows;
+    c.n_rows = sharded ? ctx->shard_rows_total : ctx->ds[0].m->n_rows;
     c.net = ctx->net;
-    EvalParams p = make_params(ctx, d);
+    c.class_w = ctx->n_classw ? ctx->d_classw : nullptr;
+    c.w_scale = f16 ? ctx->store->wscale : nullptr;
+}
+
+void fill_eval_params(npbnn_ctx* ctx, const ChainArgs& A, const ChainBatch& B, EvalParams& p) {
+    const Dataset& d = ctx->ds[0];
+    const LaunchPlan& lp = B.lp;
+    const bool f16 = ctx->net.l0_f16 != 0;
     p.partials = ctx->d_partials;
     p.inst_w = d.inst_w;
     p.use_classw = ctx->n_classw > 0 ? 1 : 0;
     p.has_pass = 1;
-    if (getenv("NPBNN_EVAL_STAMPS") && group_blocks == 0) {
-        if ((rc = B->d_estamps.reserve(ctx, (size_t)(lp.grid + 1) * 32))) return rc;
-        HIP_TRY(ctx, hipMemset(B->d_estamps, 0, (size_t)(lp.grid + 1) * 32 * sizeof(unsigned long long)));
-        p.stamps = B->d_estamps;
-    }
-    p.pv = spec ? ctx->d_spec_pv : ctx->d_pv;
+    if (B.d_estamps) p.stamps = B.d_estamps;
+    p.pv = B.spec ? ctx->d_spec_pv : ctx->d_pv;
     p.pos = ctx->d_pos;
     p.pscale = f16 ? ctx->d_pscale : nullptr;
-    p.M = M;
-    p.chain = overlap ? ctx->d_cparams : nullptr;
-    p.sync_mode = spec ? 3 : sync ? 1 : 0;
+    p.M = A.M;
+    p.chain = B.overlap ? ctx->d_cparams : nullptr;
+    p.sync_mode = B.spec ? 3 : (B.sync || B.persist) ? 1 : 0;
     // (the persistent overlapped launch: workgroups run up to a pass ahead of each other, so the heavier shares taking turns evens out)
-    p.share_rot = (persist && !spec && group_blocks == 0 && lp.grid > 1 && !getenv("NPBNN_NO_SHARE_ROTATION")) ? d.m->n_tiles % lp.grid : 0;
-    p.cand_slopes = c.slopes ? &ctx->d_slopes->cand[0][0][0] : nullptr;
-    c.class_w = ctx->n_classw ? ctx->d_classw : nullptr;
-    c.w_scale = f16 ? ctx->store->wscale : nullptr;
-    {   // both parameter blocks in one copy (they sit in one device allocation, laid out like the staging area)
-        memcpy(ctx->h_params, &p, sizeof(EvalParams));
-        memcpy(ctx->h_params + sizeof(EvalParams) + sizeof(FinalizeParams), &c, sizeof(ChainParams));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_eparams, ctx->h_params, sizeof(EvalParams) + sizeof(FinalizeParams) + sizeof(ChainParams),
-                                    hipMemcpyHostToDevice, st));
-    }
-    // step (pack the weight image, prepare candidates) -> [eval -> step (decide + prepare)]* ; a pass consumes 1..D iterations, so
-    // the number of passes is only known on the device
-    stage_mark(ctx, "copy of parameter blocks", &t_stage);
+    p.share_rot = (B.persist && !B.spec && A.group_blocks == 0 && lp.grid > 1 && !getenv("NPBNN_NO_SHARE_ROTATION")) ? d.m->n_tiles % lp.grid : 0;
+    p.cand_slopes = A.cfg->slope_idx ? &ctx->d_slopes->cand[0][0][0] : nullptr;
+}
+
+int prepare_params(npbnn_ctx* ctx, const ChainArgs& A, const ChainBatch& B) {
+    const npbnn_chain_cfg* cfg = A.cfg;
+    // activation slopes of the batch: fixed ones (ActFun("genReLU", prm=...): cfg->cur_slopes with no slope draws) go into the network
+    // description every candidate reads; trainable ones travel per candidate in the weight image (ChainParams::slope_idx)
+    for (int l = 0; l < kMaxLayers; ++l)
+        ctx->net.act_prm[l] = (!cfg->slope_idx && l < cfg->n_slopes && l < NPBNN_MAX_LAYERS) ? (float)cfg->cur_slopes[l] : 0.f;
+    ctx->batch_slopes = cfg->slope_idx != nullptr;
+    ChainParams c{};
+    fill_chain_params(ctx, A, B, c);
+    EvalParams p = make_params(ctx, ctx->ds[0]);
+    fill_eval_params(ctx, A, B, p);
+    // both parameter blocks in one copy (they sit in one device allocation, laid out like the staging area)
+    memcpy(ctx->h_params, &p, sizeof(EvalParams));
+    memcpy(ctx->h_params + sizeof(EvalParams) + sizeof(FinalizeParams), &c, sizeof(ChainParams));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_eparams, ctx->h_params, sizeof(EvalParams) + sizeof(FinalizeParams) + sizeof(ChainParams), hipMemcpyHostToDevice,
+                                ctx->stream));
+    return NPBNN_OK;
+}
+
+// stage 6: step (pack the weight image, prepare candidates) -> [eval -> step (decide + prepare)]* ; a pass consumes 1..D iterations, so
+// the number of passes is only known on the device
+int prepare_launch(npbnn_ctx* ctx, const ChainArgs& A, const ChainBatch& B, double* t_stage) {
+    const LaunchPlan& lp = B.lp;
+    const bool f16 = ctx->net.l0_f16 != 0;
+    const size_t need = (size_t)A.K * A.M;
+    hipStream_t st = ctx->stream;
     {   // one launch: image position (and fp16-split scale) of every drawn entry, so that no kernel needs a dependent lookup - indices
         // outside the network are neutralised there and reported when the batch comes back (kFlagBadIndex) - and, in the blocks
         // behind those, the weight image of the state the batch starts from (accepted candidates are committed to it entry by entry)
@@ -504,55 +440,37 @@ int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in
     }
     if (lp.wide) {       // the committed image of the state the batch starts from, and the candidate image as a copy of it
         wide_pack(ctx, ctx->d_wcur, nullptr, ctx->d_image, ctx->d_chain_ovf);
-        rc = wide_cand_begin(ctx);
+        const int rc = wide_cand_begin(ctx);
         if (rc) return rc;
     }
-    stage_mark(ctx, "gather + pack kernel", &t_stage);
+    stage_mark(ctx, "gather + pack kernel", t_stage);
     hipLaunchKernelGGL(chain_step_kernel, dim3(1), dim3(1024), 0, st, (const ChainParams*)ctx->d_cparams, 1);
-    stage_mark(ctx, "first step kernel", &t_stage);
-    B->RL = RL;
-    B->persist = persist;
-    B->sync = sync && !persist;              // (two launch streams to fork and join)
-    B->forked = false;
-    B->D = D;
-    B->schedule = schedule;
-    B->overlap = overlap;
-    B->K = K;
-    B->M = M;
-    B->wb = wb;
-    B->launch = 0;
-    B->tw1 = wall_us();
+    stage_mark(ctx, "first step kernel", t_stage);
     return NPBNN_OK;
 }
 
-// passes to launch for `rem` iterations: a pass decides between 1 and D of them; what the previous batch's average says is
-// needed plus a margin (passes launched after the last iteration return at once)
-int passes_for(const npbnn_ctx* ctx, const ChainBatch& B, int rem, double slack) {
-    int n = (rem + B.D - 1) / B.D;
-    if (B.persist) {
-        // the persistent launch ends by itself at the chain's terminal pass, so a generous bound costs nothing - and a second round
-        // (results back, look, launch again) costs a host round trip: the worst case, every iteration accepted (one iteration per
-        // pass and a void pass after each)
-        return 2 * rem + 4;
-    }
-    if (ctx->its_per_pass >= 1.0) {
-        const int est = (int)std::ceil(slack * (double)rem / ctx->its_per_pass);
-        if (est > n) n = est;
-        // a launch past the end of the batch returns at once (a few microseconds); coming back short costs a host round trip and a
-        // second round: lean towards the former
-        n += 3 + n / 8;
-    }
-    if (B.overlap) n += 1;                   // the last pass is decided by the launch after it
-    return n;
-}
-
-// the same for a segment of an exchange run, where falling short is expensive (no second round): with no history, the
-// worst case (every iteration accepted: one iteration per pass, and in the overlapped schedule a void pass after each)
-int passes_for_segment(const npbnn_ctx* ctx, const ChainBatch& B, int seg_len, double slack) {
-    double est = ctx->its_per_pass >= 1.0 ? (double)seg_len / ctx->its_per_pass : (double)seg_len * (B.overlap ? 2.0 : 1.0);
-    const double least = (double)((seg_len + B.D - 1) / B.D);
-    if (est < least) est = least;
-    return (int)std::ceil(slack * est) + 2 + (B.overlap ? 1 : 0);
+// seg_len > 0: the chain stops deciding at iteration seg_len until an exchange kernel moves the limit (exchange run)
+// alone_on_device: no other chain's launches share the GPU with this batch (the two-stream schedule counts on that)
+// group_blocks > 0: the chain is one of a group pass (npbnn_chains_run_batched): one candidate per launch, overlapped schedule,
+// its sums come from that many evaluating workgroups of the group's launches
+int chain_prepare(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, const double* W_in, const double* mask_packed, int32_t K, int32_t M,
+                  const int32_t* idx, const double* delta, const int32_t* cnt, const double* log_u, int seg_len, ChainBatch* B,
+                  bool alone_on_device = true, int group_blocks = 0) {
+    if (!ctx) return fail(nullptr, NPBNN_E_ARG, "null ctx");
+    if (!cfg || !W_in || K < 1 || M < 1 || !idx || !delta || !cnt || !log_u) return fail(ctx, NPBNN_E_ARG, "chain_run: bad arguments");
+    if (!ctx->arch_set) return fail(ctx, NPBNN_E_STATE, "chain_run: call npbnn_set_arch first");
+    B->tw0 = wall_us();
+    const ChainArgs A{cfg, W_in, mask_packed, K, M, idx, delta, cnt, log_u, seg_len, alone_on_device, group_blocks};
+    int rc;
+    if ((rc = prepare_check(ctx, A)) || (rc = prepare_plan(ctx, A, B)) || (rc = prepare_reserve(ctx, A, B))) return rc;
+    double t_stage = wall_us();
+    stage_mark(ctx, "(host set-up so far)", &t_stage);
+    if ((rc = prepare_upload(ctx, A, *B, &t_stage)) || (rc = prepare_params(ctx, A, *B))) return rc;
+    stage_mark(ctx, "copy of parameter blocks", &t_stage);
+    if ((rc = prepare_launch(ctx, A, *B, &t_stage))) return rc;
+    B->K = K; B->M = M; B->forked = false; B->launch = 0;
+    B->tw1 = wall_us();
+    return NPBNN_OK;
 }
 
 // flag-ordered overlapped schedule: the launches go to two streams in turn.  Work enqueued on ctx->stream (uploads, the first
@@ -612,48 +530,10 @@ int chain_enqueue(npbnn_ctx* ctx, ChainBatch& B, int n) {
 int chain_finish(npbnn_ctx* ctx, ChainBatch& B, const npbnn_chain_cfg* cfg, double* W_inout, uint8_t* out_accepted, double* out_loglik_prop,
                  double* out_logprior_prop, npbnn_chain_result* result, int k_take, bool exchange_run = false) {
     const ChainDev fin = *reinterpret_cast<const ChainDev*>(ctx->h_res.get());
-    if (fin.n_passes + fin.n_void > 0 && k_take > 0) ctx->its_per_pass = (double)k_take / (fin.n_passes + fin.n_void);
-    ctx->last_schedule = B.schedule;
-    if (k_take > 0) ctx->accept_rate = (double)fin.n_accepted / k_take;
-    if (B.d_stamps) {
-        std::vector<unsigned long long> hs(1024 * 8);
-        (void)hipMemcpy(hs.data(), B.d_stamps, hs.size() * 8, hipMemcpyDeviceToHost);
-        double acc[8] = {0};
-        int n = 0;
-        for (int r = 1; r < 1024; ++r) {
-            const unsigned long long* q = &hs[(size_t)r * 8];
-            if (!q[0] || !q[6]) continue;
-            bool whole = true;          // (a step that skipped a phase - a void pass has nothing to reduce - left an older stamp there)
-            for (int k = 1; k <= 6; ++k) whole = whole && q[k] >= q[k - 1];
-            if (!whole) continue;
-            for (int k = 1; k <= 6; ++k) acc[k] += (double)(q[k] - q[k - 1]) * 0.01;   // 100 MHz wall clock -> us
-            ++n;
-        }
-        if (n) fprintf(stderr, "[npbnn step stamps] prefetch %.2f  reduce %.2f  decide %.2f  commit %.2f  prepare %.2f  finish %.2f us (mean of %d)\n",
-                       acc[1] / n, acc[2] / n, acc[3] / n, acc[4] / n, acc[5] / n, acc[6] / n, n);
-        {   // start of a step -> start of the next one (the period of a pass where the step is what the passes wait for), and what of it the
-            // step workgroup spent between two steps (waiting for the evaluating workgroups' sums, flag-ordered schedules).  Rows are
-            // indexed by the first iteration of the decided pass: in time order
-            std::vector<std::pair<unsigned long long, unsigned long long>> se;
-            for (int r = 1; r < 1024; ++r) {
-                const unsigned long long* q = &hs[(size_t)r * 8];
-                if (q[0] && q[6] && q[6] > q[0]) se.push_back({q[0], q[6]});
-            }
-            std::sort(se.begin(), se.end());
-            double period = 0, idle = 0;
-            int m = 0;
-            for (size_t i = 0; i + 1 < se.size(); ++i) {
-                const double d = (double)(se[i + 1].first - se[i].first) * 0.01;
-                if (se[i + 1].first < se[i].second || d > 200.0) continue;      // (a row overwritten by a later lap of the table; a batch boundary)
-                period += d;
-                idle += (double)(se[i + 1].first - se[i].second) * 0.01;
-                ++m;
-            }
-            if (m) fprintf(stderr, "[npbnn step stamps] step start -> next step start %.2f us, of which between steps %.2f us (mean of %d)\n", period / m, idle / m, m);
-        }
-    }
+    npbnn_sched_record_outcome(&ctx->sched, B.schedule, k_take, fin.n_passes + fin.n_void, fin.n_accepted);
+    if (B.d_stamps) report_step_stamps(B.d_stamps);
     if (B.d_estamps) report_eval_stamps(B.d_estamps, B.lp.grid + (B.overlap ? 1 : 0), B.lp.wpb, (B.sync || B.persist) ? 1 : 0);
-    const int flags = *reinterpret_cast<const int*>(ctx->h_res + 448);
+    const int flags = res_flags(ctx);
     if (flags & kFlagStructure) return fail(ctx, NPBNN_E_ARG, "chain_run: a layer-0 weight is not zero where the mask given to npbnn_set_layer_mask is");
     if (flags & kFlagBadIndex) return fail(ctx, NPBNN_E_ARG, "chain_run: a weight index of the batch is outside 0 .. %d (the entry was ignored)", ctx->n_weights - 1);
     const int overflow = (ctx->net.l0_f16 && (flags & kFlagF16Range)) ? 1 : 0;
@@ -686,6 +566,24 @@ int chain_finish(npbnn_ctx* ctx, ChainBatch& B, const npbnn_chain_cfg* cfg, doub
     return NPBNN_OK;
 }
 
+// the multi-chain entries: every job complete, no context twice (`entry`: who asks, for the text)
+int check_jobs(const npbnn_chain_job* jobs, int n_jobs, const char* entry) {
+    for (int q = 0; q < n_jobs; ++q) {
+        const npbnn_chain_job& J = jobs[q];
+        if (!J.ctx || !J.cfg || !J.W_inout || !J.result || !J.out_accepted) return fail(J.ctx, NPBNN_E_ARG, "%s: job %d incomplete", entry, q);
+        for (int p2 = 0; p2 < q; ++p2)
+            if (jobs[p2].ctx == J.ctx) return fail(J.ctx, NPBNN_E_ARG, "%s: jobs %d and %d share a ctx", entry, p2, q);
+    }
+    return NPBNN_OK;
+}
+
+// a failure in the middle of such an entry: job 0's context reports it (`from`: the context that holds the text, if another one does),
+// and the first n jobs' streams are drained of what was enqueued for them
+void drain_jobs(const npbnn_chain_job* jobs, int n, const npbnn_ctx* from = nullptr) {
+    if (from && from != jobs[0].ctx) jobs[0].ctx->err = from->err;
+    for (int q = 0; q < n; ++q) (void)hipStreamSynchronize(jobs[q].ctx->stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -705,7 +603,7 @@ int npbnn_chain_run(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, double* W_inout,
     while (t_done < K) {       // launch the least number of passes that can finish, look at the counter, repeat if short
         ++n_rounds;
         const double ta = timing ? wall_us() : 0.0;
-        const int n_launch = passes_for(ctx, B, K - t_done, 1.0);
+        const int n_launch = npbnn_sched_passes(K - t_done, B.D, B.persist, B.overlap, ctx->sched.its_per_pass, 1.0);
         double t_stage = wall_us();
         rc = chain_enqueue(ctx, B, n_launch);
         if (!rc) rc = chain_join(ctx, B);
@@ -738,26 +636,7 @@ int npbnn_chain_run(npbnn_ctx* ctx, const npbnn_chain_cfg* cfg, double* W_inout,
     const double tw2 = wall_us();
     rc = chain_finish(ctx, B, cfg, W_inout, out_accepted, out_loglik_prop, out_logprior_prop, result, K);
     if (rc) return rc;
-    if (B.persist && n_rounds == 1 && result->n_passes + result->n_void_passes >= 8) {      // what a turn of this form takes here (NPBNN_SCHED_AUTO)
-        double& t = ctx->turn_us[B.schedule == NPBNN_SCHED_PERSIST_SERIAL ? 1 : 0];
-        double now_us = (tw2 - B.tw1) / (result->n_passes + result->n_void_passes);
-        // one stalled call (the host descheduled, a collector pause: 80 ms were seen) must not price a form out for good - the form
-        // that lost is not run again, so nothing would ever correct its estimate: a sample counts for at most 1.25 x the estimate
-        if (t > 0.0 && now_us > 1.25 * t) now_us = 1.25 * t;
-        t = t > 0.0 ? 0.75 * t + 0.25 * now_us : now_us;
-        const int form = B.schedule == NPBNN_SCHED_PERSIST_SERIAL ? 1 : 0, kc = K < kShortBatch ? 0 : 1;
-        double& c = ctx->it_us[form][kc];                  // ... and what an iteration cost on it, in batches of this size class
-        double it_now = (tw2 - B.tw1) / K;
-        int& n_seen = ctx->it_n[form][kc];
-        if (n_seen == 1) c = it_now < c ? it_now : c;      // (the better of a form's first two batches)
-        else {
-            if (c > 0.0 && it_now > 1.25 * c) it_now = 1.25 * c;
-            c = c > 0.0 ? 0.75 * c + 0.25 * it_now : it_now;
-        }
-        if (n_seen < 1000) ++n_seen;
-        ctx->turn_batches[form][kc] = 0;
-        ctx->turn_batches[1 - form][kc] += 1;
-    }
+    npbnn_sched_record_timing(&ctx->sched, B.schedule, B.persist, K, n_rounds, result->n_passes + result->n_void_passes, tw2 - B.tw1);
     if (timing && ctx->d_spec && B.schedule == NPBNN_SCHED_PERSIST_SERIAL) {
         SpecState hs;
         if (hipMemcpy(&hs, ctx->d_spec, sizeof hs, hipMemcpyDeviceToHost) == hipSuccess && hs.rounds > 0)
@@ -777,13 +656,11 @@ int npbnn_chains_run_batched(npbnn_chain_job* jobs, int32_t n_jobs, int32_t K) {
     if (!jobs || n_jobs < 2 || n_jobs > kMaxCand || K < 1) return fail(nullptr, NPBNN_E_ARG, "chains_run_batched: 2..%d chains, K >= 1", kMaxCand);
     npbnn_ctx* ctx0 = jobs[0].ctx;
     if (!ctx0) return fail(nullptr, NPBNN_E_ARG, "chains_run_batched: job 0 has no context");
-    int force_f32 = 0;
+    int force_f32 = 0, rc = check_jobs(jobs, n_jobs, "chains_run_batched");
+    if (rc) return rc;
     for (int q = 0; q < n_jobs; ++q) {
         const npbnn_chain_job& J = jobs[q];
-        if (!J.ctx || !J.cfg || !J.W_inout || !J.result || !J.out_accepted) return fail(J.ctx, NPBNN_E_ARG, "chains_run_batched: job %d incomplete", q);
         if (!J.ctx->arch_set) return fail(J.ctx, NPBNN_E_STATE, "chains_run_batched: job %d: call npbnn_set_arch first", q);
-        for (int p2 = 0; p2 < q; ++p2)
-            if (jobs[p2].ctx == J.ctx) return fail(J.ctx, NPBNN_E_ARG, "chains_run_batched: jobs %d and %d share a ctx", p2, q);
         // replicas of one model over the same resident matrix: same device, same X, same network shape, same likelihood
         const npbnn_ctx* a = ctx0;
         const npbnn_ctx* b = J.ctx;
@@ -796,7 +673,7 @@ int npbnn_chains_run_batched(npbnn_chain_job* jobs, int32_t n_jobs, int32_t K) {
     }
     HIP_TRY(ctx0, hipSetDevice(ctx0->device));
     Dataset& d0 = ctx0->ds[0];
-    int rc = check_dataset_for_lik(ctx0, d0, ctx0->net.lik_kind);
+    rc = check_dataset_for_lik(ctx0, d0, ctx0->net.lik_kind);
     if (rc) return rc;
     // the group's launch: one candidate per chain, the evaluating workgroups share the tiles, one step workgroup per chain
     LaunchPlan lpG;
@@ -815,12 +692,11 @@ int npbnn_chains_run_batched(npbnn_chain_job* jobs, int32_t n_jobs, int32_t K) {
         cfgs[q].force_f32 = force_f32;
         rc = chain_prepare(J.ctx, &cfgs[q], J.W_inout, J.mask_packed, K, J.M, J.idx, J.delta, J.cnt, J.log_u, 0, &B[q], false, G);
         if (rc) {
-            if (J.ctx != ctx0) ctx0->err = J.ctx->err;
-            for (int p2 = 0; p2 <= q; ++p2) (void)hipStreamSynchronize(jobs[p2].ctx->stream);
+            drain_jobs(jobs, q + 1, J.ctx);
             return rc;
         }
         if ((J.ctx->net.l0_f16 != 0) != (ctx0->net.l0_f16 != 0)) {
-            for (int p2 = 0; p2 <= q; ++p2) (void)hipStreamSynchronize(jobs[p2].ctx->stream);
+            drain_jobs(jobs, q + 1);
             return fail(ctx0, NPBNN_E_STATE, "chains_run_batched: the chains ended up on different layer-0 paths");
         }
     }
@@ -864,12 +740,12 @@ int npbnn_chains_run_batched(npbnn_chain_job* jobs, int32_t n_jobs, int32_t K) {
         double acc = 0.0;
         for (int q = 0; q < n_jobs; ++q) {
             if (K - t_done[q] > rem) rem = K - t_done[q];
-            const double a = jobs[q].ctx->accept_rate < 0 ? 0.3 : jobs[q].ctx->accept_rate;
+            const double a = jobs[q].ctx->sched.accept_rate < 0 ? 0.3 : jobs[q].ctx->sched.accept_rate;
             if (a > acc) acc = a;
         }
         if (rem == 0) break;
         if (++rounds > 64) return fail(ctx0, NPBNN_E_STATE, "chains_run_batched: the chains are stuck");
-        const int n = (int)std::ceil((double)rem * (1.0 + acc) * 1.05) + 3;
+        const int n = npbnn_sched_passes_group(rem, acc);
         for (int i = 0; i < n; ++i, ++launch)
             hipLaunchKernelGGL(lpG.fn, dim3(G + n_jobs), dim3(lpG.wpb * 64), lpG.lds, st, (const EvalParams*)ctx0->d_gparams, launch, 1);
         HIP_TRY(ctx0, hipGetLastError());
@@ -885,7 +761,7 @@ int npbnn_chains_run_batched(npbnn_chain_job* jobs, int32_t n_jobs, int32_t K) {
         }
     }
     for (int q = 0; q < n_jobs; ++q)            // (nothing is handed back unless every chain's batch is good: the caller repeats the
-        if (jobs[q].ctx->net.l0_f16 && (*reinterpret_cast<const int*>(jobs[q].ctx->h_res + 448) & kFlagF16Range))      // whole group)
+        if (jobs[q].ctx->net.l0_f16 && (res_flags(jobs[q].ctx) & kFlagF16Range))      // whole group)
             return fail(ctx0, NPBNN_E_RANGE, "chains_run_batched: a layer-0 weight of chain %d left the fp16 range during this batch", q);
     for (int q = 0; q < n_jobs; ++q) {
         const npbnn_chain_job& J = jobs[q];
@@ -911,14 +787,12 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
     }
     if (n_chains != world * n_jobs)
         return fail(nullptr, NPBNN_E_ARG, "chains_run_exchange: %d chains on %d ranks x %d jobs (every rank must hold the same number)", n_chains, world, n_jobs);
+    if (int rc = check_jobs(jobs, n_jobs, "chains_run_exchange")) return rc;
     for (int q = 0; q < n_jobs; ++q) {
         const npbnn_chain_job& J = jobs[q];
-        if (!J.ctx || !J.cfg || !J.W_inout || !J.result || !J.out_accepted) return fail(J.ctx, NPBNN_E_ARG, "chains_run_exchange: job %d incomplete", q);
         if (device < 0) device = J.ctx->device;
         if (J.ctx->device != device) return fail(J.ctx, NPBNN_E_ARG, "chains_run_exchange: job %d is on device %d, the others on %d", q, J.ctx->device, device);
         if (J.chain_id != rank + world * q) return fail(J.ctx, NPBNN_E_ARG, "chains_run_exchange: job %d holds chain %d, expected %d", q, J.chain_id, rank + world * q);
-        for (int p2 = 0; p2 < q; ++p2)
-            if (jobs[p2].ctx == J.ctx) return fail(J.ctx, NPBNN_E_ARG, "chains_run_exchange: jobs %d and %d share a ctx", p2, q);
     }
     for (int s = 0; s < n_seg; ++s)
         if (swap_j[s] < 0 || swap_j[s] >= n_chains || swap_k[s] < 0 || swap_k[s] >= n_chains)
@@ -964,8 +838,7 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
         npbnn_ctx* ctx = J.ctx;
         int rc = chain_prepare(ctx, J.cfg, J.W_inout, J.mask_packed, K, J.M, J.idx, J.delta, J.cnt, J.log_u, seg_len, &B[q], n_jobs == 1);
         if (rc) {
-            if (ctx != ctx0) ctx0->err = ctx->err;
-            for (int p2 = 0; p2 <= q; ++p2) (void)hipStreamSynchronize(jobs[p2].ctx->stream);
+            drain_jobs(jobs, q + 1, ctx);
             rc_prepare = rc;
             break;
         }
@@ -998,14 +871,14 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
         int rc = npbnn_comm_allgather_f64(comm, &ok_mine, 1, ok_all.data());
         if (rc) {
             ctx0->err = npbnn_last_error(nullptr);
-            for (int q = 0; q < n_jobs; ++q) (void)hipStreamSynchronize(jobs[q].ctx->stream);
+            drain_jobs(jobs, n_jobs);
             return rc;
         }
         int bad_rank = -1;
         for (int r = 0; r < world; ++r)
             if (ok_all[(size_t)r] != 1.0 && bad_rank < 0) bad_rank = r;
         if (bad_rank >= 0) {
-            for (int q = 0; q < n_jobs; ++q) (void)hipStreamSynchronize(jobs[q].ctx->stream);
+            drain_jobs(jobs, n_jobs);
             if (rc_prepare) return rc_prepare;
             return fail(ctx0, NPBNN_E_COMM, "chains_run_exchange: rank %d could not prepare its chains; nothing was enqueued on any rank", bad_rank);
         }
@@ -1022,7 +895,7 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
     for (int s = 0; s < n_seg; ++s) {
         for (int q = 0; q < n_jobs; ++q) {
             npbnn_ctx* ctx = jobs[q].ctx;
-            int rc = chain_enqueue(ctx, B[q], passes_for_segment(ctx, B[q], seg_len, launch_slack));
+            int rc = chain_enqueue(ctx, B[q], npbnn_sched_passes_segment(seg_len, B[q].D, B[q].overlap, ctx->sched.its_per_pass, launch_slack));
             if (rc) {       // the peers have this interval's collective in flight: it must not pair with anything else we issue
                 if (ctx != ctx0) ctx0->err = ctx->err;
                 if (comm && world > 1) npbnn_comm_abort_(comm);
@@ -1046,7 +919,7 @@ int npbnn_chains_run_exchange(npbnn_comm* comm, npbnn_chain_job* jobs, int32_t n
             if (rc) {
                 ctx0->err = npbnn_last_error(nullptr);
                 if (world > 1) npbnn_comm_abort_(comm);
-                for (int q = 0; q < n_jobs; ++q) (void)hipStreamSynchronize(jobs[q].ctx->stream);
+                drain_jobs(jobs, n_jobs);
                 return rc;
             }
         }
@@ -1151,8 +1024,8 @@ int npbnn_set_row_shard(npbnn_ctx* ctx, npbnn_comm* comm, npbnn_gather_fn gather
     ctx->shard_comm = comm;
     ctx->shard_gather = comm ? nullptr : gather;
     ctx->shard_user = user;
-    ctx->its_per_pass = 0.0;          // (the ranks must agree on the number of launches: start from the same history)
-    ctx->accept_rate = -1.0;
+    ctx->sched.its_per_pass = 0.0;    // (the ranks must agree on the number of launches: start from the same history)
+    ctx->sched.accept_rate = -1.0;
     return NPBNN_OK;
 }
 

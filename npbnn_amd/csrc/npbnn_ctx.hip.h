@@ -18,6 +18,7 @@
 #include "npbnn_buf.hip.h"
 #include "npbnn_hip.h"
 #include "npbnn_kernels.hip.h"
+#include "npbnn_sched_plan.h"
 
 using namespace npbnn;
 using npbnn_api::DevBuf;
@@ -197,15 +198,7 @@ struct npbnn_ctx : npbnn_ctx_streams {
     PinnedBuf<char> h_res;
     size_t res_k = 0, res_nw = 0;
     int* d_chain_ovf = nullptr;    // (view into d_res)
-    int last_schedule = 0;         // schedule of the previous batch
-    int turn_batches[2][2] = {{0, 0}, {0, 0}};   // [form][batch-size class] batches run since that form was last measured in that class (kTurnReprobeBatches)
-    double turn_us[2] = {0.0, 0.0}; // measured time of a launch turn (pass, decided or void) of the persistent forms: overlapped, decision between passes
-    int it_n[2][2] = {{0, 0}, {0, 0}};           // [form][batch-size class] batches that went into it_us (the first one of a form is slow: a second follows it)
-    double it_us[2][2] = {{0.0, 0.0}, {0.0, 0.0}};   // [form][batch-size class] measured time per ITERATION of a batch (what NPBNN_SCHED_AUTO
-                                    // compares); classes: batches of fewer than kShortBatch iterations, and the others - a form's fixed
-                                    // cost per batch differs, so what wins in dispatches of 100 need not win in sub-batches of 512
-    double its_per_pass = 0.0;     // iterations a launch decided on average in the previous batch (0: unknown)
-    double accept_rate = -1.0;     // acceptance rate of the previous batch (< 0: unknown)
+    npbnn_sched_hist sched = NPBNN_SCHED_HIST_INIT;   // what the chain's batches ran on and cost: the history their schedule goes by (npbnn_sched_plan.h)
     double* d_wcur = nullptr;      // (view into d_res)
     DevBuf<double> d_pv;           // [2][kMaxCand][M] proposed values of the candidates in flight
     // NPBNN_SCHED_PERSIST_SERIAL (spec_round): outcome-speculative preparation
@@ -269,23 +262,6 @@ static_assert(sizeof(EvalParams) % 8 == 0 && sizeof(FinalizeParams) % 8 == 0, "p
 
 namespace npbnn_api {
 
-// NPBNN_SCHED_AUTO between the two persistent forms.  Overlapped (PERSIST): a pass that accepts voids the pass in flight behind it - a
-// decided pass costs (1 + a) turns, a = 1 - (1 - p)^D the share of passes that accept something.  Decision between the passes
-// (PERSIST_SERIAL): no pass in vain, but every turn is longer by the decision and by what the step workgroup cannot hide of preparing
-// the next pass for every outcome - more, the wider the proposals.  The context keeps what an iteration cost on each form
-// (npbnn_ctx.it_us: a batch's time over its iterations) and picks the cheaper one; a form that has not run yet is priced from the other
-// one with that model and kSpecTurnExtraUs + kSpecTurnExtraUsPerWeight * M (measured on config-2 shapes: 33.2 against 28.5 us per turn
-// at M = 33, 40 at M = 428), and is given its first batches after kTurnFirstProbeBatches batches on the other when the model puts it within kFirstProbeWithin of it, or after kTurnForcedProbeBatches regardless (then
-// one every kTurnReprobeBatches while within a factor two: measurements go stale).  Short batches (dispatches of 100) and long ones (the
-// sub-batches of a long call) are measured and decided apart.
-constexpr double kSpecTurnExtraUs = 4.5, kSpecTurnExtraUsPerWeight = 0.0175;
-constexpr double kTurnUsGuess = 30.0;           // before anything has been measured
-constexpr int kShortBatch = 256;                // batches below / from this many iterations are measured (and decided) apart
-constexpr double kFirstProbeWithin = 1.15;      // ... if the model prices it within this factor of the measured one (asked again at every batch: the acceptance rate moves)
-constexpr int kTurnForcedProbeBatches = 200;    // ... or whatever the model says after this many batches without it (a wrong model must not park a chain for good)
-constexpr int kTurnFirstProbeBatches = 4;       // batches on one persistent form before the other, never measured, is given one
-constexpr int kTurnReprobeBatches = 48;         // batches on one persistent form before the other's measured turn time is refreshed
-constexpr int kPersistSerialMaxWidth = 640;     // ... and the widest proposal (weights perturbed per iteration) it is picked for
 constexpr int kWideMaxCand = 3;                // weight sets a fused pass of the weight-streamed path carries at most
 static_assert(kWideMaxCand <= kMaxCand, "d_y, the staged weights and the per-set flag words are sized for kMaxCand sets per pass");
 constexpr int kSetFlags = kMaxCand;            // per-set flag words behind ctx->d_overflow[0] (launch_pack_group)
@@ -360,6 +336,7 @@ int push_finalize_params(npbnn_ctx* ctx, const FinalizeParams& f);
 int push_chain_params(npbnn_ctx* ctx, const ChainParams& c);
 EvalParams make_params(npbnn_ctx* ctx, const Dataset& d);
 void report_eval_stamps(const DevBuf<unsigned long long>& stamps, int grid, int wpb, int first_wg);
+void report_step_stamps(const DevBuf<unsigned long long>& stamps);
 int check_dataset_for_lik(npbnn_ctx* ctx, const Dataset& d, int lik);
 double wall_us();
 // launches of kernels that live in npbnn_capi.hip, for the other translation units: the weight image of device-resident float64

@@ -24,6 +24,7 @@
 #include "numpy/random/bitgen.h"
 #include "numpy/random/distributions.h"
 
+#include "npbnn_sched_plan.h"
 #include "npbnn_wide_plan.h"
 
 #define NPBNN_HOST_MAX_LAYERS 8
@@ -686,3 +687,29 @@ long long npbnn_host_wide_slice_room(int n_layers, const int32_t* out_dim, int i
     if (n_layers < 1 || n_layers > NPBNN_HOST_MAX_LAYERS || !out_dim || in_dim < 1 || n_rows < 1 || n_cu < 1) return -1;
     return npbnn_wide_slice_room(n_layers, out_dim, in_dim, n_rows, n_cu);
 }
+
+/* The schedule rule of the device chains (npbnn_sched_plan.h: what the HIP library chooses, records and counts by), exported for the
+ * CPU tests of that rule.  req: the fields of npbnn_sched_req in their order; out: schedule, persist, overlap, sync, spec. */
+void npbnn_host_sched_hist_init(npbnn_sched_hist* h) {
+    const npbnn_sched_hist fresh = NPBNN_SCHED_HIST_INIT;
+    *h = fresh;
+}
+int npbnn_host_sched_choose(const int32_t* req, npbnn_sched_hist* h, int32_t* out) {
+    const npbnn_sched_req r = {req[0], req[1], req[2], req[3], req[4], req[5], req[6], req[7], req[8], req[9], req[10], req[11], req[12], req[13], req[14]};
+    const npbnn_sched_choice c = npbnn_sched_choose(&r, h);
+    out[0] = c.schedule; out[1] = c.persist; out[2] = c.overlap; out[3] = c.sync; out[4] = c.spec;
+    return c.schedule;
+}
+void npbnn_host_sched_record_outcome(npbnn_sched_hist* h, int schedule, int k_take, int n_turns, int n_accepted) {
+    npbnn_sched_record_outcome(h, schedule, k_take, n_turns, n_accepted);
+}
+void npbnn_host_sched_record_timing(npbnn_sched_hist* h, int schedule, int persist, int K, int n_rounds, int n_turns, double batch_us) {
+    npbnn_sched_record_timing(h, schedule, persist, K, n_rounds, n_turns, batch_us);
+}
+int npbnn_host_sched_passes(int rem, int D, int persist, int overlap, double its_per_pass, double slack) {
+    return npbnn_sched_passes(rem, D, persist, overlap, its_per_pass, slack);
+}
+int npbnn_host_sched_passes_segment(int seg_len, int D, int overlap, double its_per_pass, double slack) {
+    return npbnn_sched_passes_segment(seg_len, D, overlap, its_per_pass, slack);
+}
+int npbnn_host_sched_passes_group(int rem, double acc) { return npbnn_sched_passes_group(rem, acc); }

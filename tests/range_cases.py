@@ -307,7 +307,8 @@ SCHEDULES = (1, 2, 4, 5)       # serial, overlapped, persistent, persistent with
 
 
 def effective_schedule(name, d, schedule, path):
-    """The schedule the library runs when ``schedule`` is asked for by number (chain_prepare, npbnn_chain_api.hip): the
+    """The schedule the library runs when ``schedule`` is asked for by number (npbnn_sched_choose, npbnn_sched_plan.h;
+    tests/test_host_sched_plan.py holds the rule itself to this function for every run of ``direct_runs``): the
     weight-streamed path patches its candidate image between step and pass and runs on kernel boundaries (1) whatever is asked;
     schedule 5 needs a build with the speculative step - there are such builds for one and three candidates of a dense first
     layer - and falls back to the persistent overlapped form (4) elsewhere; 1, 2, 3 and 4 run as asked on a GPU the chain has to

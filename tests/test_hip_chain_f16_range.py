@@ -76,7 +76,7 @@ def run_batch(ctx, p, b, d, schedule):
 
 def ran_as_named(ctx, got, name, d, schedule, path, what):
     """The launch carried the candidates and ran on the schedule the run names (range_cases.effective_schedule: what
-    chain_prepare makes of the number).  The two-stream schedule 3 is the one form whose device-side waits may time out by
+    npbnn_sched_choose, npbnn_sched_plan.h, makes of the number).  The two-stream schedule 3 is the one form whose device-side waits may time out by
     design; the wrapper then repeats the batch on schedule 2, counts it in ``sync_fallbacks``, and that is what must be seen."""
     assert got["res"]["n_candidates"] == d, (what, "the launch did not carry the candidates the run names", got["res"]["n_candidates"])
     want = rc.effective_schedule(name, d, schedule, path)
