@@ -201,7 +201,9 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
        NPBNN_INFO_SUPPORT_FINAL_NS = 18, NPBNN_INFO_LPPD_FINAL_NS = 19, NPBNN_INFO_UNCERTAINTY_FINAL_NS = 20,
        NPBNN_INFO_CONVERGENCE_FINAL_NS = 21,
        NPBNN_INFO_REPLAY_PASSES = 22, NPBNN_INFO_REPLAY_MAX_GROUP = 23, NPBNN_INFO_L0_OPTION = 24,
-       NPBNN_INFO_CALIBRATION_FINAL_NS = 25 };
+       NPBNN_INFO_CALIBRATION_FINAL_NS = 25,
+       /* the route that served the last npbnn_predict_ale (1 or 2; 0 before any call, and after one that was refused) */
+       NPBNN_INFO_ALE_ROUTE = 26 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -251,6 +253,25 @@ int npbnn_predict_sets(npbnn_ctx* ctx, const double* W_sets, const double* act_p
  * These figures are constants of the code (kPdp* in npbnn_pdp.hip), chosen for register and LDS room, not measured cross-over points. */
 int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, const int32_t* focal, int32_t n_focal,
                       const double* grid, int32_t n_grid, const double* col_override, int which, int apply_out_fn, double* out_mean);
+
+/* Accumulated local effects (Apley & Zhu 2020) of one feature column, per stored weight set; np_bnn has no counterpart.  The n_bins + 1
+ * edges (finite, strictly increasing) cut the column `focal` into n_bins bins: a row belongs to the first bin k = 1 .. n_bins whose
+ * upper edge edges[k] is not below its entry - float32 entry against the edge rounded to float32 - and to the last bin when it lies
+ * above every edge; entries at or below edges[0] fall into bin 1.  out_counts [n_bins]: the rows of each bin.  out_effect
+ * [n_sets][n_bins][out_dim]: per set and bin, the mean over the bin's rows of (the prediction with the focal column at edges[k]) minus
+ * (the prediction with it at edges[k - 1]); 0 for a bin without rows.  The edges enter in float64, as npbnn_predict_pdp's grid values
+ * do, and col_override applies after them as it does there: with the focal column overridden every effect is 0.  The running sums
+ * over the bins and their centring are the caller's (npbnn_amd/ale.py).  NPBNN_INFO_ALE_ROUTE tells which route served the call:
+ *   1  networks inside npbnn_predict_pdp's route-1 envelope (limits a - d above): one read of X per group of sets computes layer 0
+ *      with the focal column at 0, and each row adds the shifts of its own bin's two edges;
+ *   2  one pass of the evaluation kernels per (edge, group of sets), the edge folded into layer 0's bias; after the pass at edge k its
+ *      predictions are added to bin k's sums and taken from bin k + 1's.
+ * Sums over rows run per workgroup of 256 rows in row order, then over the workgroups in a fixed order, in float64, without
+ * floating-point atomics: the same input gives the same bits.  NPBNN_ALE_PER_EDGE=1 (environment) forces route 2.  NPBNN_E_ARG, before any launch:
+ * a null W_sets, edges, out_counts or out_effect, n_sets < 1, n_bins outside 1 .. 1024, focal outside 0 .. in_dim - 1, edges that
+ * are not finite or not strictly increasing. */
+int npbnn_predict_ale(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int32_t focal, const double* edges,
+                      int32_t n_bins, const double* col_override, int which, int apply_out_fn, int64_t* out_counts, double* out_effect);
 
 /* Posterior credible intervals: calcHPD (np_bnn/BNN_lib.py:286-302) applied to every (row, output) of the n_sets stored samples'
  * predictions, as its summary code does once per row (np_bnn/BNN_plot.py:73-75).  The sets replay as in npbnn_predict_sets, but

@@ -570,6 +570,22 @@ class HipContext:
                                               capi.dptr(co), which, 1 if apply_out_fn else 0, capi.dptr(out)))
         return out
 
+    def predict_ale(self, weight_sets, focal, edges, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
+        """Local effects of the column ``focal`` on the resident matrix (npbnn_predict_ale): ``(counts [K], effects [S, K, n_out])``
+        for the K bins the K + 1 ``edges`` cut - the rows of each bin and, per weight set, the mean over them of the prediction at
+        the bin's upper edge minus the one at its lower edge (0 for an empty bin).  ``col_override`` (NaN = none) applies after the
+        edges.  NPBNN_INFO_ALE_ROUTE: the route taken."""
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_ale")
+        z = capi.as_f64(np.asarray(edges, dtype=np.float64).ravel())
+        n_bins = len(z) - 1
+        co = None if col_override is None else capi.as_f64(np.asarray(col_override, dtype=np.float64).ravel())
+        counts = np.zeros(max(n_bins, 0), dtype=np.int64)
+        effects = np.zeros((n_sets, max(n_bins, 0), self.n_out), dtype=np.float64)
+        self._chk(self._lib.npbnn_predict_ale(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, int(focal), capi.dptr(z), n_bins,
+                                              capi.dptr(co), which, 1 if apply_out_fn else 0,
+                                              counts.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(effects)))
+        return counts, effects
+
     def time_eval(self, weights, iters=20):
         w = one_vector(weights)
         a, b = C.c_double(0), C.c_double(0)
