@@ -108,23 +108,6 @@ int build_net(npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
     if (a->act_kind < 0 || a->act_kind > NPBNN_ACT_TANH) return fail(ctx, NPBNN_E_ARG, "set_arch: act_kind=%d", a->act_kind);
     if (a->out_kind < 0 || a->out_kind > NPBNN_OUT_SOFTPLUS_HALF) return fail(ctx, NPBNN_E_ARG, "set_arch: out_kind=%d", a->out_kind);
     if (a->lik_kind < 0 || a->lik_kind > NPBNN_LIK_NONE) return fail(ctx, NPBNN_E_ARG, "set_arch: lik_kind=%d", a->lik_kind);
-    NetMeta net{};
-    net.n_layers = a->n_layers;
-    net.act_kind = a->act_kind;
-    net.out_kind = a->out_kind;
-    net.lik_kind = a->lik_kind;
-    net.k_targets = a->n_targets;
-    net.final_act = a->final_act ? 1 : 0;
-    net.l0_f16 = f16 ? 1 : 0;
-    // softmax / categorical heads: padding outputs are masked through their bias (see NetMeta::pad_masked)
-    net.pad_masked = (!net.final_act && (a->out_kind == NPBNN_OUT_SOFTMAX || a->lik_kind == NPBNN_LIK_CATEGORICAL)) ? 1 : 0;
-    if (getenv("NPBNN_NO_PAD_MASK")) net.pad_masked = 0;       // (A/B timing)
-    {   // layer 1 on fp16-split products (NetMeta::l1_f16)
-        bool narrow_later = a->n_layers >= 2;
-        for (int l = 1; l < a->n_layers; ++l) narrow_later = narrow_later && a->out_dim[l] <= 16;
-        net.l1_f16 = (f16 && narrow_later && a->act_kind == NPBNN_ACT_TANH && a->out_dim[0] > 16 && !a->final_act && !getenv("NPBNN_NO_L1_F16")) ? 1 : 0;
-    }
-    int in = a->in_dim, off = 0, woff = 0;
     for (int l = 0; l < a->n_layers; ++l)
         if (a->out_dim[l] < 1 || a->out_dim[l] > NPBNN_MAX_WIDTH)
             return fail(ctx, NPBNN_E_ARG, "set_arch: layer %d has %d nodes; this backend supports 1..%d per layer", l, a->out_dim[l],
@@ -135,15 +118,36 @@ int build_net(npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
         for (int l = 0; l < a->n_layers; ++l) { nw += (long long)a->out_dim[l] * (in_l + (a->has_bias[l] ? 1 : 0)); in_l = a->out_dim[l]; }
         if (nw >= (1ll << 31)) return fail(ctx, NPBNN_E_ARG, "set_arch: %lld weights; this backend indexes up to 2^31", nw);
     }
+    // the resident image's layout (npbnn_resident_plan.h); the A/B timing switches are read here
+    npbnn_resident_req req{};
+    req.arch = a;
+    req.f16 = f16;
+    req.l0_blocks = ctx->l0_blocks.empty() ? nullptr : ctx->l0_blocks.data();
+    req.has_classw = ctx->n_classw > 0;
+    req.slopes_option = ctx->slopes_option;
+    req.no_pad_mask = getenv("NPBNN_NO_PAD_MASK") != nullptr;
+    req.no_l1_f16 = getenv("NPBNN_NO_L1_F16") != nullptr;
+    req.no_tile_perm = getenv("NPBNN_NO_TILE_PERM") != nullptr;
+    req.no_compact_rows = getenv("NPBNN_NO_COMPACT_ROWS") != nullptr;
+    npbnn_resident_layout lay{};
+    const int rc_lay = npbnn_resident_layout_of(&req, &lay);
+    if (rc_lay == NPBNN_RESIDENT_E_ARG) return fail(ctx, NPBNN_E_INTERNAL, "set_arch: the layout rule refused a checked network (internal error)");
+    NetMeta net{};
+    net.n_layers = a->n_layers;
+    net.act_kind = a->act_kind;
+    net.out_kind = a->out_kind;
+    net.lik_kind = a->lik_kind;
+    net.k_targets = a->n_targets;
+    net.final_act = a->final_act ? 1 : 0;
+    net.l0_f16 = f16 ? 1 : 0;
     // Networks the LDS of a compute unit cannot hold (or a layer wider than the resident builds' tiles) run on the weight-streamed
     // path (npbnn_wide.hip): the description below then carries what the chain step and the likelihood need - shapes, offsets into
     // the packed weights, kinds - and none of the resident image's layout.
-    ctx->wide = wide_needed(ctx, a, f16);
+    ctx->wide = wide_needed(ctx, a, rc_lay, lay);
+    int woff = 0;
     if (ctx->wide) {
-        net.pad_masked = 0;
-        net.l1_f16 = 0;
+        int in = a->in_dim;
         net.l0_rows = 16;
-        for (int mt = 0; mt < kMaxMT; ++mt) { net.l0_begin[mt] = 0; net.l0_end[mt] = 0; net.l0_base[mt] = 0; }
         for (int l = 0; l < a->n_layers; ++l) {
             LayerMeta& L = net.L[l];
             L.in_dim = in;
@@ -151,9 +155,6 @@ int build_net(npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
             L.has_bias = a->has_bias[l] ? 1 : 0;
             L.kt = (in + 15) / 16;
             L.mt = (L.out_dim + 15) / 16;
-            L.frag_off = 0;
-            L.bias_off = 0;
-            L.out_perm = 0;
             L.in_live = 4;
             L.w_off = woff;
             woff += L.out_dim * (in + L.has_bias);
@@ -161,72 +162,16 @@ int build_net(npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
         }
         net.classw_off = -1;
         net.slope_off = ctx->slopes_option ? 0 : -1;     // (>= 0 says "candidates carry their own slopes": the streamed kernels read them from the chain)
-        net.image_floats = 0;
-    }
-    for (int l = 0; l < a->n_layers && !ctx->wide; ++l) {
-        const int out = a->out_dim[l];
-        LayerMeta& L = net.L[l];
-        L.in_dim = in;
-        L.out_dim = out;
-        L.has_bias = a->has_bias[l] ? 1 : 0;
-        L.kt = (l == 0 && f16) ? 2 * ((in + 31) / 32) : (in + 15) / 16;   // 1-KiB pieces (16 rows x 64 B) per tile
-        L.mt = (out + 15) / 16;
-        L.frag_off = off;
-        L.out_perm = (l >= 1 && l + 1 < a->n_layers && L.mt == 1 && !getenv("NPBNN_NO_TILE_PERM")) ? 1 : 0;
-        L.in_live = (l >= 1 && net.L[l - 1].out_perm) ? (net.L[l - 1].out_dim + 3) / 4 : 4;
-        if (l == 0) {
-            // K-units of the layer-0 loop (32 features on the fp16-split path, 16 on the float32 one); per output tile the hull of
-            // the units in which the mask has anything (the whole layer when no structure was declared)
-            const int g16 = (in + 15) / 16, per_unit = f16 ? 2 : 1, units = f16 ? (in + 31) / 32 : g16;
-            int slots = 0;
-            for (int mt = 0; mt < kMaxMT; ++mt) { net.l0_begin[mt] = 0; net.l0_end[mt] = 0; net.l0_base[mt] = 0; }
-            for (int mt = 0; mt < L.mt; ++mt) {
-                int b = 0, e = units;
-                if (!ctx->l0_blocks.empty()) {
-                    b = units; e = 0;
-                    for (int g = 0; g < g16; ++g)
-                        if (ctx->l0_blocks[(size_t)mt * g16 + g]) { const int u = g / per_unit; if (u < b) b = u; if (u + 1 > e) e = u + 1; }
-                    if (e <= b) { b = 0; e = 0; }
-                }
-                net.l0_begin[mt] = b; net.l0_end[mt] = e; net.l0_base[mt] = slots;
-                slots += e - b;
-            }
-            // rows per tile in the image (NetMeta::l0_rows): a dense fp16-split first layer of three or more tiles whose width is not a
-            // multiple of 16 is stored without its padding rows (the builds for one and two tiles - every BASELINE shape - keep 16)
-            // (never a network of one matrix: its first layer's positions are the outputs' - the predictions and the likelihood read
-            // output c at position c, and there is no layer 1 whose weights could meet the moved units.  Until this was excluded, one
-            // matrix of 33 or more outputs, not a multiple of 16, gave its outputs in the image's order: found by the partial-dependence
-            // envelope test's 33-output case on route 2, wrong by 0.2 in a probability)
-            net.l0_rows = 16;
-            if (f16 && ctx->l0_blocks.empty() && a->n_layers >= 2 && L.mt >= 3 && out % 16 != 0 && !getenv("NPBNN_NO_COMPACT_ROWS"))
-                net.l0_rows = (out + L.mt - 1) / L.mt;
-            off += slots * (f16 ? 32 * net.l0_rows : 256);
-        } else if (l == 1 && net.l1_f16) {
-            off += ((net.L[0].mt + 1) / 2) * 512;      // a high and a low block of 256 floats per K-step
-        } else {
-            off += L.kt * L.mt * 256;
-        }
-        L.w_off = woff;
-        woff += out * (in + L.has_bias);
-        in = out;
-    }
-    if (!ctx->wide) {
-    for (int l = 0; l < a->n_layers; ++l) {
-        net.L[l].bias_off = off;
-        off += 16 * net.L[l].mt;
-    }
-    if (ctx->n_classw > 0) {            // class weights ride in the image only when there are any
-        net.classw_off = off;
-        off += kResidentMaxWidth;
     } else {
-        net.classw_off = -1;
-    }
-    net.slope_off = -1;
-    if (ctx->slopes_option) {           // a slot per hidden layer for the candidates' activation slopes (filled in LDS by a chain pass)
-        net.slope_off = off;
-        off += kMaxLayers;
-    }
-    net.image_floats = round_up(off, 64);   // a multiple of 256 B (the LDS copies of several candidates sit back to back)
+        for (int l = 0; l < a->n_layers; ++l) net.L[l] = lay.L[l];
+        for (int mt = 0; mt < kMaxMT; ++mt) { net.l0_begin[mt] = lay.l0_begin[mt]; net.l0_end[mt] = lay.l0_end[mt]; net.l0_base[mt] = lay.l0_base[mt]; }
+        net.l0_rows = lay.l0_rows;
+        net.l1_f16 = lay.l1_f16;
+        net.pad_masked = lay.pad_masked;
+        net.classw_off = lay.classw_off;
+        net.slope_off = lay.slope_off;
+        net.image_floats = lay.image_floats;
+        woff = lay.n_weights;
     }
     net.n_out = a->out_dim[a->n_layers - 1];
     if (a->lik_kind == NPBNN_LIK_GAUSS) {
@@ -243,18 +188,10 @@ int build_net(npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
                         a->lik_kind, need_out, k, net.n_out);
     }
     ctx->net = net;
+    ctx->rlay = lay;
     ctx->n_weights = woff;
     ctx->mt0_template = net.L[0].mt;
     return NPBNN_OK;
-}
-
-// waves per block such that the fragment image + per-wave rings fit the CU's LDS
-int max_inner_tiles(const NetMeta& net) {
-    int mti = 1;
-    for (int l = 1; l < net.n_layers; ++l)
-        if (net.L[l].mt > mti) mti = net.L[l].mt;
-    if (net.n_layers == 1) mti = net.L[0].mt;        // the single layer's tiles are also the final tiles
-    return mti;
 }
 
 WaveLayout layout_for(const npbnn_ctx* ctx, const Dataset& d, bool predict_only) {
@@ -262,22 +199,23 @@ WaveLayout layout_for(const npbnn_ctx* ctx, const Dataset& d, bool predict_only)
                             predict_only ? NPBNN_LIK_NONE : ctx->net.lik_kind);
 }
 
-int pick_waves_per_block(const npbnn_ctx* ctx, size_t* lds_bytes, int n_cand, const WaveLayout& lay, bool predict_only, bool fast) {
-    const int lk = predict_only ? kLikCat : lik_class(ctx->net.lik_kind);
-    const int top = max_waves_for(ctx->net.L[0].mt, max_inner_tiles(ctx->net) == 1 ? 1 : 8, ctx->net.l0_f16 != 0, n_cand, lk, fast);   // launch bound of the build in use
-    for (int w = top; w >= 1; --w) {
-        const size_t need = (size_t)n_cand * ctx->net.image_floats * 4 + (size_t)w * lay.wave_lds;
-        if (need + 64 <= ctx->lds_limit) {       // (+ 64: the flag word of the device-side waits, plan_launch)
-            *lds_bytes = need;
-            return w;
-        }
-    }
-    return 0;
-}
-
-
-eval_fn_t pick_kernel(const NetMeta& net, int n_cand) {
-    return npbnn_pick_eval_kernel(net.L[0].mt, max_inner_tiles(net) == 1 ? 1 : 8, net.l0_f16, n_cand, lik_class(net.lik_kind));
+// the launch rule (npbnn_resident_plan.h) on the context's network, table and options; NPBNN_WAVES is the caller's to read
+static int resident_launch(const npbnn_ctx* ctx, const Dataset& d, int want_cand, bool predict_only, bool lik_only, bool plain, int waves_override,
+                           npbnn_resident_launch* out) {
+    npbnn_resident_launch_req q{};
+    q.has_labels = d.labels != nullptr;
+    q.has_row_w = d.inst_w != nullptr;
+    q.has_targets = d.targets != nullptr;
+    q.n_tiles = d.m->n_tiles;
+    q.n_cu = ctx->n_cu > 0 ? ctx->n_cu : 1;
+    q.lds_limit = (int)ctx->lds_limit;
+    q.want_cand = want_cand;
+    q.predict_only = predict_only;
+    q.lik_only = lik_only;
+    q.plain = plain;
+    q.fast_option = ctx->fast_option;
+    q.waves_override = waves_override;
+    return npbnn_resident_launch_of(&ctx->rlay, &q, out);
 }
 
 // Per column of a resident matrix under the context's scales (split_quality_kernel): how far the fp16 pair's largest counted entry
@@ -428,26 +366,6 @@ int ensure_x16(npbnn_ctx* ctx, int which, int* usable) {
     return NPBNN_OK;
 }
 
-// May a launch that wants nothing but the likelihood terms run on the fast builds (eval_kernel, FAST)?  2 or 3 layers, later
-// layers of <= 16 nodes, layer 0 of <= 16 * kFastMaxMT0, categorical (padding outputs masked through the bias) or Gaussian
-// likelihood, no row or class weights, no activation after the last layer.
-// does layer 0 skip anything (some output tile without weights in some K-unit)?
-bool l0_blocked(const NetMeta& net) {
-    const int units = net.l0_f16 ? net.L[0].kt / 2 : net.L[0].kt;
-    for (int mt = 0; mt < net.L[0].mt; ++mt)
-        if (net.l0_begin[mt] != 0 || net.l0_end[mt] != units) return true;
-    return false;
-}
-
-bool fast_launch_ok(const npbnn_ctx* ctx, const Dataset& d) {
-    const NetMeta& net = ctx->net;
-    if (!ctx->fast_option || max_inner_tiles(net) != 1 || net.n_layers < 2 || net.n_layers > kFastLayers || net.L[0].mt > kFastMaxMT0) return false;
-    if (net.final_act || d.inst_w || ctx->n_classw > 0 || net.slope_off >= 0) return false;
-    if (l0_blocked(net) && !net.l0_f16) return false;          // (the fast builds for block-structured layers are fp16-split ones)
-    if (net.lik_kind == NPBNN_LIK_CATEGORICAL) return net.pad_masked != 0 && d.labels != nullptr;
-    return net.lik_kind == NPBNN_LIK_GAUSS && d.targets != nullptr && net.k_targets <= (l0_blocked(net) ? 1 : kFastGaussTargets);
-}
-
 // lik_only: the caller wants the likelihood terms and nothing else from the launch (no statistics, no predictions)
 int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32, int want_cand, bool predict_only, bool lik_only, bool plain) {
     Dataset& d = ctx->ds[which];
@@ -476,59 +394,32 @@ int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32, int wa
     }
     if (ctx->wide) return wide_plan(ctx, which, lp, (predict_only || lik_only) ? want_cand : 1, predict_only);
     lp->wide = false;
-    size_t lds = 0;
-    // speculative passes: as many candidates as still leave >= 8 waves per workgroup (only the MTI = 1 builds have them)
-    int n_cand = (max_inner_tiles(ctx->net) == 1 && (predict_only || !lik_needs_row_scratch(ctx->net.lik_kind))) ? want_cand : 1;
-    if (n_cand > kMaxCand) n_cand = kMaxCand;
-    if (n_cand > max_cand_for(ctx->net.L[0].mt)) n_cand = max_cand_for(ctx->net.L[0].mt);
-    const WaveLayout lay = layout_for(ctx, d, predict_only);
-    const bool fast = lik_only && !predict_only && fast_launch_ok(ctx, d);
-    while (n_cand > 1 && pick_waves_per_block(ctx, &lds, n_cand, lay, predict_only, fast) < 8) --n_cand;
-    lp->n_cand = n_cand;
-    lp->fast = fast;
-    int wpb = pick_waves_per_block(ctx, &lds, n_cand, lay, predict_only, fast);
-    if (wpb == 0)
+    int waves_override = 0;
+    if (const char* e = getenv("NPBNN_WAVES")) { const int v = atoi(e); if (v >= 1) waves_override = v; }      // (A/B switch)
+    npbnn_resident_launch r;
+    const int refusal = resident_launch(ctx, d, want_cand, predict_only, lik_only, plain, waves_override, &r);
+    if (refusal == NPBNN_RESIDENT_NO_FIT)
         return fail(ctx, NPBNN_E_ARG, "network too large: weight image of %d KiB does not fit the %zu KiB LDS of a CU",
                     ctx->net.image_floats * 4 / 1024, ctx->lds_limit / 1024);
-    lp->fn = predict_only ? npbnn_pick_eval_kernel(ctx->net.L[0].mt, max_inner_tiles(ctx->net) == 1 ? 1 : 8, ctx->net.l0_f16, n_cand, kLikCat)
-                          : npbnn_pick_eval_kernel(ctx->net.L[0].mt, max_inner_tiles(ctx->net) == 1 ? 1 : 8, ctx->net.l0_f16, n_cand,
-                                                   lik_class(ctx->net.lik_kind), fast, fast && l0_blocked(ctx->net), plain && fast);
+    if (refusal == NPBNN_RESIDENT_FEW_WAVES)
+        return fail(ctx, NPBNN_E_ARG, "network too large for the LDS-resident path on this data set (%d waves beside a weight image of %d KiB); "
+                                      "NPBNN_OPT_WIDE = 1 runs it on the weight-streamed path", r.waves, ctx->net.image_floats * 4 / 1024);
+    if (refusal) return fail(ctx, NPBNN_E_INTERNAL, "the launch rule refused its request (internal error)");
+    const int mt0 = ctx->net.L[0].mt, l0f16 = ctx->net.l0_f16;
+    lp->n_cand = r.n_cand;
+    lp->fast = r.fast != 0;
+    lp->fn = npbnn_pick_eval_kernel(mt0, r.mti, l0f16, r.n_cand, r.lk, r.fast, r.fast && r.blocked, plain && r.fast);
     if (!lp->fn) return fail(ctx, NPBNN_E_STATE, "no evaluation kernel for this shape (internal error)");
     lp->fn_spec = nullptr;
-    if (fast && !plain && !predict_only && !l0_blocked(ctx->net) && (n_cand == 1 || n_cand == 3)) {
-        const bool g = lik_class(ctx->net.lik_kind) == kLikGauss;
-        const int mt0 = ctx->net.L[0].mt, f16 = ctx->net.l0_f16;
-        lp->fn_spec = n_cand == 1 ? (g ? pick_eval_d1_gauss_spec(mt0, f16) : pick_eval_d1_cat_spec(mt0, f16))
-                                  : (g ? pick_eval_d3_gauss_spec(mt0, f16) : pick_eval_d3_cat_spec(mt0, f16));
+    if (r.want_spec) {
+        const bool g = r.lk == kLikGauss;
+        lp->fn_spec = r.n_cand == 1 ? (g ? pick_eval_d1_gauss_spec(mt0, l0f16) : pick_eval_d1_cat_spec(mt0, l0f16))
+                                    : (g ? pick_eval_d3_gauss_spec(mt0, l0f16) : pick_eval_d3_cat_spec(mt0, l0f16));
     }
-    {
-        // A thin second round of tiles: when a workgroup's share is just over one tile per wave (config 5 with three candidates: 12.25
-        // tiles for 12 waves) the leftover tile runs alone after the others are through - a lone wave streams X at a ring's worth per
-        // memory latency.  Two waves fewer spread the leftovers over several SIMDs and give the first round less contention: measured
-        // 36.4 -> 33.4 us per pass there (9 or 10 waves; 11: 35.0, 8: 35.0, 7: 41.9); single-candidate launches and shares of two rounds
-        // or more are best at the build's full count (config 2: 30.6 us at 12 waves, 31.3 at 10).  NPBNN_WAVES: A/B switch.
-        int w_use = wpb;
-        const double share = (double)d.m->n_tiles / (double)(ctx->n_cu > 0 ? ctx->n_cu : 1);
-        if (n_cand > 1 && share > (double)w_use && share < 1.25 * (double)w_use && w_use - 2 >= 8) w_use -= 2;
-        if (const char* e = getenv("NPBNN_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= wpb) w_use = v; }
-        if (w_use != wpb) {
-            wpb = w_use;
-            lds = (size_t)n_cand * ctx->net.image_floats * 4 + (size_t)wpb * lay.wave_lds;
-        }
-    }
-    // (the tile schedule of eval_kernel needs a wave on every SIMD of the compute unit: networks that leave fewer run on the
-    // weight-streamed path - wide_needed - and a data set whose row-aux slots push a launch below that is refused rather than mis-summed)
-    if (wpb < 4)
-        return fail(ctx, NPBNN_E_ARG, "network too large for the LDS-resident path on this data set (%d waves beside a weight image of %d KiB); "
-                                      "NPBNN_OPT_WIDE = 1 runs it on the weight-streamed path", wpb, ctx->net.image_floats * 4 / 1024);
-    lp->wpb = wpb;
-    lp->lds = lds;
-    int grid = (d.m->n_tiles + wpb - 1) / wpb;
-    if (grid > ctx->n_cu) grid = ctx->n_cu;     // persistent: one workgroup per CU
-    if (grid < 1) grid = 1;
-    lp->grid = grid;
-    lp->n_waves = grid;            // one partial record per workgroup
-    lp->lds = lds + 64;            // (+ the flag word of the device-side waits, behind the images and the rings)
+    lp->wpb = r.waves;
+    lp->grid = r.grid;
+    lp->n_waves = r.grid;          // one partial record per workgroup
+    lp->lds = (size_t)r.lds_bytes;
     if (ctx->attr_fn != reinterpret_cast<const void*>(lp->fn) || ctx->attr_lds < lp->lds) {      // (not free: once per kernel and size)
         HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(lp->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lp->lds));
         if (lp->fn_spec)
@@ -740,10 +631,14 @@ int rebuild_net(npbnn_ctx* ctx, bool f16) {
     ctx->d_w2scale.reset();
     if (ctx->wide) return wide_build(ctx, f16);
     wide_free(ctx);
-    size_t lds = 0;
-    if (pick_waves_per_block(ctx, &lds, 1, make_wave_layout(true, false, ctx->net.k_targets, ctx->net.L[0].kt, ctx->net.lik_kind)) == 0)
-        return fail(ctx, NPBNN_E_ARG, "network too large: weight image of %d KiB does not fit the %zu KiB LDS of a CU",
-                    ctx->net.image_floats * 4 / 1024, ctx->lds_limit / 1024);
+    {   // (one candidate beside a wave with labels and targets)
+        npbnn_resident_launch r;
+        npbnn_resident_launch_req q{};
+        q.has_labels = 1; q.has_targets = 1; q.n_cu = 1; q.lds_limit = (int)ctx->lds_limit; q.want_cand = 1;
+        if (npbnn_resident_launch_of(&ctx->rlay, &q, &r) == NPBNN_RESIDENT_NO_FIT)
+            return fail(ctx, NPBNN_E_ARG, "network too large: weight image of %d KiB does not fit the %zu KiB LDS of a CU",
+                        ctx->net.image_floats * 4 / 1024, ctx->lds_limit / 1024);
+    }
     // (room for kMaxCand independent images: npbnn_predict_sets stages that many weight sets per pass)
     if (int rc2 = ctx->d_image.reserve(ctx, (size_t)kMaxCand * ctx->net.image_floats)) return rc2;
     HIP_TRY(ctx, hipMemset(ctx->d_image, 0, (size_t)kMaxCand * ctx->net.image_floats * sizeof(float)));
@@ -762,38 +657,9 @@ int rebuild_net(npbnn_ctx* ctx, bool f16) {
         for (int o = 0; o < L.out_dim; ++o)
             for (int j = 0; j < ld; ++j) {
                 const size_t wi = (size_t)L.w_off + (size_t)o * ld + j;
-                int pos;
-                const bool in_perm = l >= 1 && ctx->net.L[l - 1].out_perm;      // (a permuted layer has a single tile: o, c < 16)
-                const int rows = f16 ? ctx->net.l0_rows : 16;         // (NetMeta::l0_rows: layer 0's units per tile in this image)
-                if (L.has_bias && j == 0) pos = L.bias_off + (L.out_perm ? tile_pos(o) : (l == 0 && rows < 16) ? l0_pos_of_unit(o, rows) : o);
-                else {
-                    int c = in_perm ? tile_pos(j - L.has_bias) : j - L.has_bias;
-                    if (l == 1 && rows < 16) c = l0_pos_of_unit(c, rows);       // (the position layer 0 leaves that unit at)
-                    int mt = o / 16, u = L.out_perm ? tile_pos(o) : o % 16;
-                    if (l == 0 && f16) {
-                        mt = o / rows; u = o % rows;
-                        const int ks = c / 32, kg = (c % 32) / 8, jj = c % 8;
-                        if (ks < ctx->net.l0_begin[mt] || ks >= ctx->net.l0_end[mt]) pos = kSkipPos;     // outside the block structure: always 0
-                        else {
-                            const int slot = ctx->net.l0_base[mt] + ks - ctx->net.l0_begin[mt];
-                            const int half_index = 2 * L.frag_off + ((slot * 2) * (4 * rows) + kg * rows + u) * 8 + jj;
-                            pos = (int)(0x80000000u | (rows < 16 ? (unsigned)kPosCompact : 0u) | (unsigned)half_index);
-                        }
-                        scale[wi] = wscale[(size_t)c];
-                    } else if (l == 0) {
-                        const int kt = c / 16, kq = (c % 16) / 4, sidx = c % 4;
-                        if (kt < ctx->net.l0_begin[mt] || kt >= ctx->net.l0_end[mt]) pos = kSkipPos;
-                        else pos = L.frag_off + ((ctx->net.l0_base[mt] + kt - ctx->net.l0_begin[mt]) * 64 + kq * 16 + u) * 4 + sidx;
-                    } else if (l == 1 && ctx->net.l1_f16) {      // (layer 0 is not permuted: c is the unit; scale stays 1)
-                        const int t_in = c / 16, kq = (c % 16) / 4, q = t_in / 2, e = 4 * (t_in & 1) + c % 4;
-                        const int half_index = 2 * L.frag_off + ((q * 2) * 64 + kq * 16 + u) * 8 + e;
-                        pos = (int)(0x80000000u | (unsigned)half_index);
-                    } else {
-                        const int kt = c / 16, kq = (c % 16) / 4, sidx = c % 4;
-                        pos = L.frag_off + ((kt * L.mt + mt) * 64 + kq * 16 + u) * 4 + sidx;
-                    }
-                }
-                map[wi] = pos;
+                int scale_col;
+                map[wi] = npbnn_resident_pos(&ctx->rlay, l, o, j, &scale_col);
+                if (scale_col >= 0) scale[wi] = wscale[(size_t)scale_col];
             }
     }
     if (int rc2 = ctx->d_w2img.reserve(ctx, map.size())) return rc2;
@@ -1103,7 +969,6 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
         *out = what == NPBNN_INFO_WAVES_PER_BLOCK ? 4 : what == NPBNN_INFO_MAX_CANDIDATES ? 1 : 0;      // (group passes: one chain per pass; what a replay of stored sets carried: NPBNN_INFO_REPLAY_MAX_GROUP)
         return NPBNN_OK;
     }
-    if (what == NPBNN_INFO_WAVES_PER_BLOCK) { size_t lds = 0; *out = pick_waves_per_block(ctx, &lds, 1, layout_for(ctx, ctx->ds[0])); return NPBNN_OK; }
     if (what == NPBNN_INFO_N_CU) { *out = ctx->n_cu; return NPBNN_OK; }
     if (what == NPBNN_INFO_TURN_NS_OVERLAPPED || what == NPBNN_INFO_TURN_NS_BETWEEN) {
         *out = (int)(1000.0 * ctx->sched.turn_us[what == NPBNN_INFO_TURN_NS_BETWEEN ? 1 : 0]);
@@ -1114,19 +979,15 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
         *out = (int)(1000.0 * (c[0] > 0.0 ? c[0] : c[1]));
         return NPBNN_OK;
     }
-    if (what == NPBNN_INFO_MAX_CANDIDATES) {        // what plan_launch would give a chain pass that asks for as many as fit
-        *out = 1;
-        if (!ctx->arch_set || !ctx->ds[0].m->X) return NPBNN_OK;
-        int n = (max_inner_tiles(ctx->net) == 1 && !lik_needs_row_scratch(ctx->net.lik_kind)) ? kMaxCand : 1;
-        if (n > max_cand_for(ctx->net.L[0].mt)) n = max_cand_for(ctx->net.L[0].mt);
-        const WaveLayout lay = layout_for(ctx, ctx->ds[0], false);
-        const bool fast = fast_launch_ok(ctx, ctx->ds[0]);
-        size_t lds = 0;
-        while (n > 1 && pick_waves_per_block(ctx, &lds, n, lay, false, fast) < 8) --n;
-        *out = n;
+    if (what == NPBNN_INFO_WAVES_PER_BLOCK || what == NPBNN_INFO_MAX_CANDIDATES || what == NPBNN_INFO_FAST_TAILS) {
+        // what plan_launch gives a chain pass on the training table: of one candidate (the waves), of as many as fit (the other two)
+        npbnn_resident_launch r{};
+        r.n_cand = 1;
+        if (what == NPBNN_INFO_WAVES_PER_BLOCK || (ctx->arch_set && (what == NPBNN_INFO_FAST_TAILS || ctx->ds[0].m->X)))
+            resident_launch(ctx, ctx->ds[0], what == NPBNN_INFO_WAVES_PER_BLOCK ? 1 : kMaxCand, false, what != NPBNN_INFO_WAVES_PER_BLOCK, false, 0, &r);
+        *out = what == NPBNN_INFO_WAVES_PER_BLOCK ? r.waves_full : what == NPBNN_INFO_MAX_CANDIDATES ? r.n_cand : r.fast;
         return NPBNN_OK;
     }
-    if (what == NPBNN_INFO_FAST_TAILS) { *out = (ctx->arch_set && fast_launch_ok(ctx, ctx->ds[0])) ? 1 : 0; return NPBNN_OK; }
     return fail(ctx, NPBNN_E_ARG, "get_info: unknown item %d", what);
 }
 

@@ -182,7 +182,6 @@ struct ChainParams {
     NetMeta net;
 };
 
-constexpr int kSkipPos = 0x7fffffff;
 
 __device__ __forceinline__ double log_prior_density(int kind, double w, double scale) {
     if (kind == NPBNN_PRIOR_CAUCHY) return -log(3.14159265358979323846 * scale * (1.0 + (w / scale) * (w / scale)));

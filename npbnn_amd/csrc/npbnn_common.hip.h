@@ -5,62 +5,15 @@
 #include <stdint.h>
 #include <type_traits>
 #include "npbnn_hip.h"
+#include "npbnn_resident_plan.h"   // the build bounds, WaveLayout, LayerMeta and the image positions: one rule for kernels, host and CPU tests
 
 namespace npbnn {
 
-constexpr int kMaxLayers = NPBNN_MAX_LAYERS;
-// The LDS-resident path (eval_kernel) holds layers of up to kResidentMaxWidth nodes; wider ones - up to NPBNN_MAX_WIDTH - run on the
-// weight-streamed path (npbnn_wide.hip.h), as does any network whose image does not fit a compute unit's LDS.
-constexpr int kResidentMaxWidth = 128;
-constexpr int kMaxMT = kResidentMaxWidth / 16;   // 16-unit tiles per layer of the resident path
-#ifndef NPBNN_RING
-#define NPBNN_RING 4
-#endif
-constexpr int kRing = NPBNN_RING;              // X ring slots (1 KiB each) per wave; kRing-1 pieces stay in flight
 constexpr int kMaxWavesPerBlock = 16;
-// Per-wave row-aux slots (labels / instance weights / targets of a 16-row tile, fetched ahead of the tile's X pieces).  Their
-// number and size depend on the data set and the network: the host lays them out (WaveLayout) and hands the numbers to the
-// kernel, so that nothing is reserved that a run does not use - at config 2 this is what lets a 13th wave fit the LDS.
-struct WaveLayout {
-    int aux_slots;   // 2 when the ring never holds pieces of more than the next tile, else 4 (a power of two)
-    int aux_sz;      // bytes per slot
-    int off_w;       // instance weights inside a slot (labels, when present, sit at 0)
-    int off_t;       // targets inside a slot
-    int wave_lds;    // bytes of LDS per wave: ring + slots (+ row scratch of the float64 row-wise likelihoods)
-};
-// likelihoods that combine several outputs of one row (predicted sigma, count data) exchange them through 1 KiB of LDS
-__host__ __device__ inline bool lik_needs_row_scratch(int lik_kind) {
-    return lik_kind >= NPBNN_LIK_GAUSS_PRED_SIGMA && lik_kind <= NPBNN_LIK_NEGBIN_BASE10;
-}
-__host__ __device__ inline WaveLayout make_wave_layout(bool labels, bool inst_w, int k_targets, int kt0, int lik_kind) {
-    WaveLayout L;
-    L.off_w = labels ? 64 : 0;
-    L.off_t = L.off_w + (inst_w ? 64 : 0);
-    L.aux_sz = L.off_t + 64 * k_targets;
-    L.aux_slots = kt0 >= kRing ? 2 : 4;
-    L.wave_lds = kRing * 1024 + L.aux_slots * L.aux_sz + (lik_needs_row_scratch(lik_kind) ? 1024 : 0);
-    return L;
-}
 constexpr int kPartialStride = 1 + 2 * NPBNN_MAX_TARGETS;   // loglik, sum_r[16], sum_r2[16]
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-struct LayerMeta {
-    int kt;        // 16-wide k tiles of the input dimension
-    int mt;        // 16-wide tiles of the output dimension
-    int frag_off;  // float offset of the fragment block in the image
-    int bias_off;  // float offset of the padded bias (16*mt floats)
-    int in_dim, out_dim, has_bias;
-    int w_off;     // double offset of the layer matrix in the packed weights
-    // Narrow hidden layers (one output tile, not the last layer): unit u sits at position 4 (u % 4) + u / 4 of the tile instead of u
-    // (tile_pos).  A lane (row n, k-group kq) holds positions 4 kq + i in register i, and the next layer's i-th float32 MFMA contracts
-    // the positions {i, 4 + i, 8 + i, 12 + i}: with the units transposed like this the first ceil(out / 4) registers hold all of them,
-    // and the next layer skips the MFMAs of the others - they would multiply the zeros of the padding (in_live of that layer).
-    int out_perm;  // this layer's units are placed like that
-    int in_live;   // float32 MFMAs per input tile this layer needs (4 unless the layer before it has out_perm)
-};
-__host__ __device__ inline int tile_pos(int u) { return 4 * (u & 3) + (u >> 2); }      // (its own inverse: a 4 x 4 transpose)
 
 struct NetMeta {
     int n_layers;
@@ -92,18 +45,15 @@ struct NetMeta {
                         // lanes of the padding rows read the tile's last real row (finite values that meet zero weights in layer 1).
                         // The reference's default [50, 5] on 256 features: 57 KB instead of 70 KB per candidate - two fit the LDS
 };
-// the layer-0 unit at output position `pos` of such an image (-1: a padding position), and the other way round
+// the layer-0 unit at output position `pos` of such an image (-1: a padding position); the other way round: l0_pos_of_unit
 __host__ __device__ inline int l0_unit_at(int pos, int rows, int out_dim) {
     const int t = pos >> 4, u = pos & 15;
     if (u >= rows) return -1;
     const int o = t * rows + u;
     return o < out_dim ? o : -1;
 }
-__host__ __device__ inline int l0_pos_of_unit(int o, int rows) { return (o / rows) * 16 + o % rows; }
-constexpr int kPosCompact = 0x40000000;      // (image positions of fp16-split entries, bit 30: the low part sits 32 * l0_rows halves behind the high part, not 512)
 
 constexpr float kPadLogit = -3.0e38f;     // finite: (pad - max) stays finite, exp of it is exactly 0
-constexpr int kMaxCand = 3;    // candidates evaluated per pass over X by a speculative chain
 
 // One pass of a device-resident chain evaluates, against a single streaming read of X, the proposal of iteration t0 and
 // the proposals of iterations t0+1 .. t0+n_cand-1 *under the assumption that the earlier ones are rejected* (each is the

@@ -56,7 +56,7 @@ static inline eval_fn_t npbnn_pick_eval_kernel(int mt0, int mti, int f16, int n_
     using namespace npbnn;
     if (fast) {
         const bool g = lk == kLikGauss;
-        if (blocked) f16 = 2;                 // (fast_launch_ok: block structure only on the fp16-split path)
+        if (blocked) f16 = 2;                 // (npbnn_resident_fast_ok: block structure only on the fp16-split path)
         if (n_cand <= 1 && plain) return g ? pick_eval_d1_gauss_plain(mt0, f16) : pick_eval_d1_cat_plain(mt0, f16);
         if (n_cand <= 1) return g ? pick_eval_d1_gauss_fast(mt0, f16) : pick_eval_d1_cat_fast(mt0, f16);
         if (n_cand == 2) return g ? pick_eval_d2_gauss_fast(mt0, f16) : pick_eval_d2_cat_fast(mt0, f16);
@@ -154,6 +154,7 @@ struct npbnn_ctx : npbnn_ctx_streams {
     bool arch_set = false;
     npbnn_arch arch{};
     NetMeta net{};
+    npbnn_resident_layout rlay{};  // the resident image's layout behind `net` (npbnn_resident_plan.h: what the launch rule reads); unused on the weight-streamed path
     int n_weights = 0;
     int mt0_template = 1;
     int l0_option = 0;             // NPBNN_L0_AUTO / _F32 / _F16
@@ -294,7 +295,8 @@ struct LaunchPlan {
 };
 
 // ---- weight-streamed path (npbnn_wide.hip) ----
-bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16);
+// rc, lay: what npbnn_resident_layout_of said of the network on this layer-0 layout
+bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, int rc, const npbnn_resident_layout& lay);
 int wide_build(npbnn_ctx* ctx, bool f16);
 void wide_free(npbnn_ctx* ctx);
 // predict: a predicting launch - its weight sets are independent (stored samples that share their slopes), not a chain's candidates
@@ -319,13 +321,9 @@ float* pass_image(npbnn_ctx* ctx, const LaunchPlan& lp, int j);
 // the fp16 range repeats alone).  The caller zeroes them.
 void launch_pack_group(npbnn_ctx* ctx, const LaunchPlan& lp, const double* d_w, const double* d_col_override, int g);
 
-int max_inner_tiles(const NetMeta& net);
 WaveLayout layout_for(const npbnn_ctx* ctx, const Dataset& d, bool predict_only = false);
-int pick_waves_per_block(const npbnn_ctx* ctx, size_t* lds_bytes, int n_cand, const WaveLayout& lay, bool predict_only = false, bool fast = false);
 int ensure_x16(npbnn_ctx* ctx, int which, int* usable);
 int rebuild_net(npbnn_ctx* ctx, bool f16);
-bool l0_blocked(const NetMeta& net);
-bool fast_launch_ok(const npbnn_ctx* ctx, const Dataset& d);
 // lik_only: the caller wants the likelihood terms and nothing else from the launch (no statistics, no predictions)
 // plain: the launch is a plain evaluation - no pass descriptor, no chain (the builds without that code)
 int plan_launch(npbnn_ctx* ctx, int which, LaunchPlan* lp, int force_f32 = 0, int want_cand = 1, bool predict_only = false, bool lik_only = false,

@@ -18,10 +18,6 @@ namespace npbnn {
 //         each class keeps different per-lane accumulators alive through the whole kernel (and lgamma is register hungry).
 // ------------------------------------------------------------------------------------------------
 typedef void (*eval_fn_t)(const EvalParams*, int, int);
-constexpr int kLikCat = 0, kLikGauss = 1, kLikGen = 2;
-__host__ __device__ inline int lik_class(int lik_kind) {
-    return lik_needs_row_scratch(lik_kind) ? kLikGen : (lik_kind == NPBNN_LIK_GAUSS ? kLikGauss : kLikCat);
-}
 
 template <int LK>
 struct TileAcc {            // per-candidate float64 accumulators of one wave: sum of the per-row log-likelihood terms ...
@@ -31,11 +27,6 @@ template <>
 struct TileAcc<kLikGauss> { // ... or, for the Gaussian likelihood, residual moments of the 4 target columns this lane owns
     double s1[4], s2[4];
 };
-// The fast Gaussian builds are for <= kFastGaussTargets target columns (every BASELINE regression shape: 1 or 2): all of them
-// belong to the lanes of the first quarter (kq = 0) and the moments of columns 2 and 3 of a lane, 8 float64 registers per
-// candidate that the general build carries through the whole kernel, are never touched.
-constexpr int kFastGaussTargets = 2;
-
 // A value every lane of the wave holds identically, moved to scalar registers.  The kernel reads its launch-invariant
 // parameters through pointers that other code inlined into it (the chain step) writes through, and its first branch is
 // lane dependent (the diagnostic stamps), so the compiler no longer proves them uniform by itself - and a loop bound it
@@ -64,11 +55,6 @@ __device__ __forceinline__ T* uni(T* ptr) { return reinterpret_cast<T*>(uni((lon
 #ifndef NPBNN_LAUNDER_TAIL
 #define NPBNN_LAUNDER_TAIL (FAST && !SPEC && (BLK || (LK == kLikGauss && MT0 >= 2) || MT0 >= 3))
 #endif
-#ifndef NPBNN_FAST3_WAVES
-#define NPBNN_FAST3_WAVES 12
-#endif
-constexpr int kFastMaxMT0 = 4;      // fast builds exist for layer 0 of up to 16 * kFastMaxMT0 nodes
-constexpr int kFastLayers = 3;      // networks of up to this many layers have shape-specialised tails
 struct HotParams {
     const int* labels;
     const float* targets;
@@ -426,24 +412,6 @@ __device__ __forceinline__ void tile_tail(const NetMeta& net, const HotParams& h
     }
 }
 
-// software-pipelined layer 0 (the fragments of K-step s+1 are read from LDS while the MFMAs of step s run): builds whose two
-// fragment sets fit the register budget of their launch bounds
-__host__ __device__ constexpr bool pipelined_l0(int mt0, int mti, bool f16, int d, bool fast_dense = false) {
-    // (two candidates: one tile - or, in the fast builds of dense first layers, three and four: 158 registers, nothing spilled, the
-    // reference's default [50, 5] +3-5 %; with two tiles the second fragment set does not fit, nor in the other builds of three and more)
-    return f16 && mti == 1 && ((d == 3 && mt0 <= 2) || (d == 2 && (mt0 <= 1 || (fast_dense && (mt0 == 3 || mt0 == 4)))) || (d == 1 && mt0 <= 2));
-}
-// candidates per pass a layer-0 width is built for: three sets of accumulators and tails side by side spill INSIDE the tile loop from
-// three output tiles on (tools/check_hot_loop_spills.sh; measured on 100k x 64, hidden [50, 5]: 30.3 us for three candidates
-// against 18.1 us for two, chain 65-81 k against 91 k it/s) - plan_launch asks for no more, and no such build is instantiated
-__host__ __device__ constexpr int max_cand_for(int mt0) { return mt0 <= 2 ? 3 : 2; }
-// waves per workgroup a build is compiled for: more candidates keep more accumulators and weight fragments alive.  The
-// three-candidate categorical build of the narrow networks (the chain kernel of config 2) fits 128 VGPRs, i.e. 13 waves:
-// with 24-25 tiles per workgroup that is two rounds of tiles per wave instead of three for some.
-// The fast three-candidate builds take 12 (three per SIMD, 168 registers): with all three tails unrolled side by side 128 spill.
-__host__ __device__ constexpr int max_waves_for(int mt0, int mti, bool f16, int d, int lk, bool fast = false) {
-    return mti != 1 ? 8 : d == 1 ? 16 : d == 2 ? (fast ? 12 : 14) : fast ? (NPBNN_FAST3_WAVES) : (lk == kLikCat && pipelined_l0(mt0, mti, f16, d)) ? 13 : 11;
-}
 // s_waitcnt lgkmcnt(0) as an instruction the compiler's own wait-count bookkeeping sees (the builtin, not inline assembly): with an
 // opaque asm statement the compiler added a full wait of its own in front of every unit's first MFMA - behind the LDS reads just
 // requested for the NEXT unit, which therefore never ran underneath the MFMAs - and moved the statement itself up between them
@@ -468,7 +436,7 @@ __device__ __forceinline__ void warm_scalar_cache(const EvalParams* pp) {
 }
 
 // FAST: the build for launches that want nothing but the likelihood terms of a 2- or 3-layer network with narrow later layers
-// (`fast_launch_ok` below says which: every chain pass and plain evaluation of the BASELINE configs).  It holds only the
+// (npbnn_resident_fast_ok says which: every chain pass and plain evaluation of the BASELINE configs).  It holds only the
 // shape-specialised tails and none of the scalars the general epilogue keeps alive (statistics, predictions, row weights ...),
 // which is what brings the tile loop's scalar registers back under the file's size.  Same arithmetic, same bits.
 // BLK (fast builds only): layer 0 has a block structure (NetMeta::l0_begin ...) and the loop skips the (K-unit, tile) pairs
@@ -614,7 +582,7 @@ __global__ void __launch_bounds__(max_waves_for(MT0, MTI, F16, D, LK, FAST) * 64
     hp.k_targets = uni(net.k_targets); hp.act_kind = uni(net.act_kind);
 #pragma unroll
     for (int l = 1; l < kFastLayers; ++l) { hp.frag_off[l - 1] = 0; hp.bias_off[l - 1] = 0; hp.act_prm[l - 1] = 0.f; hp.in_live[l - 1] = 4; }
-    if constexpr (FAST) {       // (fast_launch_ok: the host has checked all of this)
+    if constexpr (FAST) {       // (npbnn_resident_fast_ok: the host has checked all of this)
         hp.labels = LK == kLikCat ? uni(p.labels) : nullptr;
         hp.targets = LK == kLikGauss ? uni(p.targets) : nullptr;
         hp.inst_w = nullptr; hp.confusion = nullptr; hp.y_out = nullptr;

@@ -24,6 +24,7 @@
 #include "numpy/random/bitgen.h"
 #include "numpy/random/distributions.h"
 
+#include "npbnn_resident_plan.h"
 #include "npbnn_sched_plan.h"
 #include "npbnn_wide_plan.h"
 
@@ -713,3 +714,42 @@ int npbnn_host_sched_passes_segment(int seg_len, int D, int overlap, double its_
     return npbnn_sched_passes_segment(seg_len, D, overlap, its_per_pass, slack);
 }
 int npbnn_host_sched_passes_group(int rem, double acc) { return npbnn_sched_passes_group(rem, acc); }
+
+/* The LDS-resident path's layout and launch rule (npbnn_resident_plan.h: what the HIP library builds its weight image and plans its
+ * passes by), exported for the CPU tests of that rule.  opts: f16, class weights present, slopes option, then the four A/B switches
+ * in the order of npbnn_resident_req; l0_blocks: the layer-0 block table or NULL.  Return: the rule's own codes. */
+static npbnn_resident_req resident_req(const npbnn_arch* arch, const int32_t* opts, const unsigned char* l0_blocks) {
+    const npbnn_resident_req r = {arch, opts[0], l0_blocks, opts[1], opts[2], opts[3], opts[4], opts[5], opts[6]};
+    return r;
+}
+int npbnn_host_resident_layout(const npbnn_arch* arch, const int32_t* opts, const unsigned char* l0_blocks, npbnn_resident_layout* out) {
+    if (!opts) return NPBNN_RESIDENT_E_ARG;
+    const npbnn_resident_req r = resident_req(arch, opts, l0_blocks);
+    return npbnn_resident_layout_of(&r, out);
+}
+/* pos[n_weights]: the image position of every packed weight; scale_col[n_weights]: the input column whose fp16-split scale it is stored under, or -1 */
+int npbnn_host_resident_map(const npbnn_resident_layout* y, int32_t* pos, int32_t* scale_col) {
+    if (!y || !pos || !scale_col) return NPBNN_RESIDENT_E_ARG;
+    for (int l = 0; l < y->n_layers; ++l) {
+        const LayerMeta* L = &y->L[l];
+        const int ld = L->in_dim + L->has_bias;
+        for (int o = 0; o < L->out_dim; ++o)
+            for (int j = 0; j < ld; ++j) {
+                int c;
+                pos[(size_t)L->w_off + (size_t)o * ld + j] = npbnn_resident_pos(y, l, o, j, &c);
+                scale_col[(size_t)L->w_off + (size_t)o * ld + j] = c;
+            }
+    }
+    return NPBNN_RESIDENT_OK;
+}
+long long npbnn_host_resident_path_bytes(const npbnn_resident_layout* y, int has_classw, int waves) {
+    return y ? npbnn_resident_path_bytes(y, has_classw, waves) : -1;
+}
+/* req: the fields of npbnn_resident_launch_req in their order */
+int npbnn_host_resident_launch(const npbnn_resident_layout* y, const int32_t* req, npbnn_resident_launch* out) {
+    if (!req) return NPBNN_RESIDENT_E_ARG;
+    const npbnn_resident_launch_req q = {req[0], req[1], req[2], req[3], req[4], req[5], req[6], req[7], req[8], req[9], req[10], req[11]};
+    return npbnn_resident_launch_of(y, &q, out);
+}
+int npbnn_host_resident_max_waves(int mt0, int mti, int f16, int d, int lk, int fast) { return max_waves_for(mt0, mti, f16, d, lk, fast); }
+int npbnn_host_resident_max_cand(int mt0) { return max_cand_for(mt0) < kMaxCand ? max_cand_for(mt0) : kMaxCand; }

@@ -110,46 +110,6 @@ int stages_env() {
     return v;
 }
 
-// bytes of LDS the resident path would need for this network with one candidate and `waves` waves (build_net's layout arithmetic)
-size_t resident_lds_bytes(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16, int waves) {
-    long long off = 0;
-    int in = a->in_dim;
-    bool narrow_later = a->n_layers >= 2;
-    for (int l = 1; l < a->n_layers; ++l) narrow_later = narrow_later && a->out_dim[l] <= 16;
-    const bool l1_f16 = f16 && narrow_later && a->act_kind == NPBNN_ACT_TANH && a->out_dim[0] > 16 && !a->final_act;
-    for (int l = 0; l < a->n_layers; ++l) {
-        const int out = a->out_dim[l], mt = (out + 15) / 16;
-        if (l == 0) {
-            const int units = f16 ? (in + 31) / 32 : (in + 15) / 16;
-            int rows = 16;
-            if (f16 && ctx->l0_blocks.empty() && a->n_layers >= 2 && mt >= 3 && out % 16 != 0) rows = (out + mt - 1) / mt;
-            long long slots = (long long)mt * units;
-            if (!ctx->l0_blocks.empty()) {       // block-structured first layer (npbnn_set_layer_mask): per output tile the hull of its K-units
-                const int g16 = (in + 15) / 16, per_unit = f16 ? 2 : 1;
-                slots = 0;
-                for (int t = 0; t < mt; ++t) {
-                    int b = units, e = 0;
-                    for (int g = 0; g < g16; ++g)
-                        if (ctx->l0_blocks[(size_t)t * g16 + g]) { const int u = g / per_unit; if (u < b) b = u; if (u + 1 > e) e = u + 1; }
-                    if (e > b) slots += e - b;
-                }
-            }
-            off += slots * (f16 ? 32 * rows : 256);
-        } else if (l == 1 && l1_f16) {
-            off += ((a->out_dim[0] + 15) / 16 + 1) / 2 * 512;
-        } else {
-            off += (long long)((in + 15) / 16) * mt * 256;
-        }
-        off += 16 * mt;
-        in = out;
-    }
-    if (ctx->n_classw > 0) off += kResidentMaxWidth;
-    off += kMaxLayers + 64;
-    const int kt0 = f16 ? 2 * ((a->in_dim + 31) / 32) : (a->in_dim + 15) / 16;
-    const WaveLayout lay = make_wave_layout(true, true, a->n_targets, kt0, a->lik_kind);
-    return (size_t)off * 4 + (size_t)waves * lay.wave_lds + 64;
-}
-
 }  // namespace
 
 // Does this network run on the weight-streamed path on this layer-0 layout?  A layer the resident builds have no tiles for, or an
@@ -158,11 +118,10 @@ size_t resident_lds_bytes(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16, i
 // candidates per read of X, the persistent schedules - e.g. [32, 8] on 1024 features, 7 waves: 10.2 k against 6.6 k it/s;
 // NPBNN_WIDE_MIN_WAVES: A/B switch).  Asked per layout: the float32 image of a first layer is larger than its fp16-split one
 // (no compact rows), so a network may run resident on the fp16-split path and streamed on the float32 fallback.
-bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
+bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, int rc, const npbnn_resident_layout& lay) {
     if (ctx->wide_option == 1) return true;
     if (const char* e = getenv("NPBNN_FORCE_WIDE")) { if (atoi(e) != 0) return true; }
-    for (int l = 0; l < a->n_layers; ++l)
-        if (a->out_dim[l] > kResidentMaxWidth) return true;
+    if (rc != NPBNN_RESIDENT_OK) return true;       // (a layer wider than kResidentMaxWidth)
     static const int min_waves = getenv("NPBNN_WIDE_MIN_WAVES") ? atoi(getenv("NPBNN_WIDE_MIN_WAVES")) : kMinResidentWaves;
     // (never fewer than four: the resident kernel deals a workgroup's tiles to the four SIMDs of its compute unit and, there, to the
     // waves of that SIMD - with fewer than four waves the tiles of the SIMDs without one are never computed.  Until this round such
@@ -182,7 +141,7 @@ bool wide_needed(const npbnn_ctx* ctx, const npbnn_arch* a, bool f16) {
     // (the row count of the training matrix: npbnn_set_data rebuilds the net on a new one, so the path does not depend on whether
     // the architecture or the data came first)
     if (!getenv("NPBNN_WIDE_MIN_WAVES") && fusable && a->out_dim[0] <= 32 && ctx->ds[0].m->X != nullptr && ctx->ds[0].m->n_rows >= 65536 && w < 8) w = 8;
-    return resident_lds_bytes(ctx, a, f16, w) > ctx->lds_limit;
+    return npbnn_resident_path_bytes(&lay, ctx->n_classw > 0, w) > (long long)ctx->lds_limit;
 }
 
 void wide_free(npbnn_ctx* ctx) {
