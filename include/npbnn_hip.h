@@ -203,7 +203,10 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
        NPBNN_INFO_REPLAY_PASSES = 22, NPBNN_INFO_REPLAY_MAX_GROUP = 23, NPBNN_INFO_L0_OPTION = 24,
        NPBNN_INFO_CALIBRATION_FINAL_NS = 25,
        /* the route that served the last npbnn_predict_ale (1 or 2; 0 before any call, and after one that was refused) */
-       NPBNN_INFO_ALE_ROUTE = 26 };
+       NPBNN_INFO_ALE_ROUTE = 26,
+       /* the route that served the last npbnn_predict_saliency (1 or 2; 0 before any call, and after one that was refused), and with
+        * NPBNN_FI_TIMING=1 the device time in nanoseconds of its phase 2: the fold and reduce kernels of every launch (0 otherwise) */
+       NPBNN_INFO_SALIENCY_ROUTE = 27, NPBNN_INFO_SALIENCY_FOLD_NS = 28 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -272,6 +275,33 @@ int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const double* act_pr
  * are not finite or not strictly increasing. */
 int npbnn_predict_ale(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int32_t focal, const double* edges,
                       int32_t n_bins, const double* col_override, int which, int apply_out_fn, int64_t* out_counts, double* out_effect);
+
+/* Input-gradient saliency of the stored weight sets; np_bnn has no counterpart.  With G[s][i][c][j] = d f_s(x~_i)_c / d x_ij - x~_i the row i
+ * of the resident matrix `which` after col_override, f the network's output (through the output function with apply_out_fn = 1, the last
+ * layer's values with 0) - the three outputs, each [n_sets][out_dim][in_dim], are means over the n rows:
+ *   out_mean  (1/n) sum_i G      the average marginal effect
+ *   out_abs   (1/n) sum_i |G|    the saliency
+ *   out_sq    (1/n) sum_i G^2    the rows' spread
+ * A column col_override gives a constant has gradient 0, exactly.  The chain rule runs over the code of the forward pass: ReLU 1 for
+ * z > 0, else 0; leaky slope for z < 0, else 1, each set with its own slope per layer (act_prm_sets as in npbnn_predict_sets);
+ * swish s (1 + z (1 - s)), s = sigma(z); tanh 1 - t^2; the last layer's activation where arch.final_act is set; softmax p_c (delta_ck -
+ * p_k); softplus-half sigma(z_c) on the outputs c >= out_dim / 2; biases contribute nothing.  G never leaves the device and is never
+ * stored whole.  A launch has two phases over a chunk of rows: phase 1, one thread per row, runs forward and then, per output, back to
+ * layer 0's pre-activation, D[c][row][h] = d f_c / d z0_h; phase 2 forms G = D_c W0^T per tile of 32 rows x 32 features on the float32
+ * matrix instruction and folds it at once.  NPBNN_INFO_SALIENCY_ROUTE tells which phase 1 served the call:
+ *   1  networks inside npbnn_predict_pdp's route-1 envelope (limits a - d above): layer 0 from a weight image in LDS, one read of X per
+ *      group of sets, the later layers in registers;
+ *   2  every other network the library takes (layers up to NPBNN_MAX_WIDTH, any in_dim, the weight-streamed path's): a plain kernel
+ *      with runtime widths whose activations live in a device scratch.  NPBNN_SALIENCY_PLAIN=1 (environment) forces it, and so does
+ *      NPBNN_FORCE_WIDE=1.
+ * Both read the float32 matrix only: NPBNN_OPT_L0_PRECISION plays no part, and there is no fp16-range repeat.  Sums over rows run in
+ * float32 inside one tile of 32 rows at most, from there on in float64: in row order over a wave's 256 rows, then over the waves in a
+ * fixed order, without floating-point atomics: the same input gives the same bits on every call.  D and the partial sums have a byte
+ * budget (128 MiB; NPBNN_SALIENCY_SCRATCH_BYTES in the environment overrides it): a larger table runs in chunks of rows.
+ * NPBNN_E_ARG, before any launch: a null W_sets, out_mean, out_abs or out_sq, n_sets < 1, a table without rows.  NPBNN_E_STATE without
+ * npbnn_set_arch or without data on `which`. */
+int npbnn_predict_saliency(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, const double* col_override, int which,
+                           int apply_out_fn, double* out_mean, double* out_abs, double* out_sq);
 
 /* Posterior credible intervals: calcHPD (np_bnn/BNN_lib.py:286-302) applied to every (row, output) of the n_sets stored samples'
  * predictions, as its summary code does once per row (np_bnn/BNN_plot.py:73-75).  The sets replay as in npbnn_predict_sets, but

@@ -40,6 +40,8 @@ INFO_REPLAY_PASSES, INFO_REPLAY_MAX_GROUP = 22, 23
 INFO_L0_OPTION = 24
 INFO_CALIBRATION_FINAL_NS = 25
 INFO_ALE_ROUTE = 26
+INFO_SALIENCY_ROUTE = 27
+INFO_SALIENCY_FOLD_NS = 28
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
 E_STATE = -2
@@ -149,6 +151,7 @@ SIGNATURES = {
     "npbnn_predict_pdp": (C.c_int, [_P, _DP, _DP, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _DP, C.c_int32, _DP, C.c_int,
                                     C.c_int, _DP]),
     "npbnn_predict_ale": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int32, _DP, C.c_int32, _DP, C.c_int, C.c_int, C.POINTER(C.c_int64), _DP]),
+    "npbnn_predict_saliency": (C.c_int, [_P, _DP, _DP, C.c_int32, _DP, C.c_int, C.c_int, _DP, _DP, _DP]),
     "npbnn_predict_sets_hpd": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
     "npbnn_permute_columns": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_int32]),
     "npbnn_predict_sets_summary": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _DP,

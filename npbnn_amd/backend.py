@@ -586,6 +586,18 @@ class HipContext:
                                               counts.ctypes.data_as(C.POINTER(C.c_int64)), capi.dptr(effects)))
         return counts, effects
 
+    def predict_saliency(self, weight_sets, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
+        """Input gradients on the resident matrix (npbnn_predict_saliency): ``(mean, abs, sq)``, each [S, n_out, F] - per weight
+        set, output and feature the mean over the rows of the derivative of the output with respect to the feature, of its absolute
+        value and of its square.  A column ``col_override`` gives a constant (NaN = none) has gradient 0.
+        NPBNN_INFO_SALIENCY_ROUTE: the route taken."""
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_saliency")
+        co = None if col_override is None else capi.as_f64(np.asarray(col_override, dtype=np.float64).ravel())
+        out = [np.zeros((n_sets, self.n_out, int(self.arch.in_dim)), dtype=np.float64) for _ in range(3)]
+        self._chk(self._lib.npbnn_predict_saliency(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, capi.dptr(co), which,
+                                                   1 if apply_out_fn else 0, capi.dptr(out[0]), capi.dptr(out[1]), capi.dptr(out[2])))
+        return tuple(out)
+
     def time_eval(self, weights, iters=20):
         w = one_vector(weights)
         a, b = C.c_double(0), C.c_double(0)

@@ -246,6 +246,8 @@ struct npbnn_ctx : npbnn_ctx_streams {
     int replay_passes = 0, replay_max_group = 0;  // the last replay_sets: passes over X (float32 repeats included), most sets in one (NPBNN_INFO_REPLAY_*)
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     int ale_route = 0;             // route of the last npbnn_predict_ale: 1 both edges from one read of X, 2 per edge; 0 none, or refused (NPBNN_INFO_ALE_ROUTE)
+    int saliency_route = 0;        // route of the last npbnn_predict_saliency: 1 phase 1 in registers, 2 the plain kernel; 0 none, or refused (NPBNN_INFO_SALIENCY_ROUTE)
+    int saliency_ns = 0;           // NPBNN_FI_TIMING: the last npbnn_predict_saliency's fold and reduce kernels (NPBNN_INFO_SALIENCY_FOLD_NS)
     // weight-streamed path (npbnn_wide.hip): the network does not fit a compute unit's LDS (or NPBNN_OPT_WIDE asks for it)
     bool wide = false;
     int wide_option = 0;           // NPBNN_OPT_WIDE: 0 when the resident path cannot hold the network, 1 always

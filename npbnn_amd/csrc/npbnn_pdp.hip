@@ -16,7 +16,10 @@
 // the two edges of its own bin only.  Route 1 (ale_kernel) is pdp_kernel's layer 0 followed by two runs of the later layers per row
 // and set; route 2 (ale_pick_kernel) picks each pass's predictions by bin.  Either way the differences are added per (bin, output)
 // over a workgroup's rows in row order, then over the workgroups in a fixed order (ale_reduce_kernel), in float64 and without atomics.
-#include "npbnn_sets.hip.h"
+//
+// Route 1's float32 blocks, its layer-0 stage and its host set-up (pdp_prep_kernel, pdp_layer0, pdp_dense, plan_route1, prepare_route1)
+// are in npbnn_route1.hip.h, which npbnn_saliency.hip includes too.
+#include "npbnn_route1.hip.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -27,72 +30,8 @@ namespace npbnn_api {
 
 namespace {
 
-constexpr int kPdpRows = 256;                    // rows of a workgroup of pdp_kernel (one per thread)
-constexpr int kPdpTail = 32;                     // widest later layer (and output) route 1 takes
-constexpr int kPdpMaxH0 = 64;                    // widest first layer route 1 takes
-constexpr size_t kPdpW0Lds = 64 * 1024;          // LDS bytes for one set's first-layer weights (Fp x H0P floats)
-constexpr size_t kPdpTailLds = 32 * 1024;        // LDS bytes for the later layers of the sets of one launch
 constexpr size_t kPdpAccBytes = 512ull << 20;    // device budget of the float32 accumulator [grid points][rows][outputs]: larger grids
                                                  // run in chunks of grid points, each chunk one more read of X per set group
-
-struct PdpParams {
-    const float* X;
-    long long n_rows;
-    int Fp;
-    const float* w0t;      // [set][Fp][H0P]: layer 0 transposed, zero on the focal and overridden columns
-    const float* bias;     // [set][n_grid][H0P]: layer-0 bias + the override and grid-point fold
-    const float* tail;     // [set][tail_floats]: later layer l at t_off[l]: bias (outputs padded to 4), then W [out][t_inp[l]]
-    const float* slopes;   // [set][kMaxLayers]
-    int set0, n_set, g0, n_g, n_grid, tail_floats;
-    int n_layers, act_kind, final_act, out_kind, apply_out, C, accumulate;
-    int t_out[kMaxLayers], t_inp[kMaxLayers], t_off[kMaxLayers];
-    float* acc;            // [n_g][n_rows][C]
-};
-
-struct PdpPrep {
-    int F, Fp, H0, H0P, hb0, n_layers, n_grid, wn, tail_floats;
-    int l_in[kMaxLayers], l_out[kMaxLayers], l_hb[kMaxLayers], l_woff[kMaxLayers], t_inp[kMaxLayers], t_off[kMaxLayers];
-};
-
-template <int KIND, int N>
-__device__ __forceinline__ void pdp_act_k(float (&h)[N], float prm) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) h[i] = act_apply(h[i], KIND, prm);
-}
-
-template <int N>
-__device__ __forceinline__ void pdp_act(float (&h)[N], int kind, float prm) {
-    switch (kind) {
-        case NPBNN_ACT_RELU: pdp_act_k<NPBNN_ACT_RELU>(h, prm); break;
-        case NPBNN_ACT_LEAKY: pdp_act_k<NPBNN_ACT_LEAKY>(h, prm); break;
-        case NPBNN_ACT_SWISH: pdp_act_k<NPBNN_ACT_SWISH>(h, prm); break;
-        default: pdp_act_k<NPBNN_ACT_TANH>(h, prm); break;
-    }
-}
-
-// out[o] = w_bias[o] + sum_i W[o][i] in[i] for o < n_out (0 above); inp: the layer's inputs padded to 8 (zero weights on the padding).
-// The weights are LDS reads at one address for the whole wave (broadcasts); the guards are wave-uniform.
-template <int IN, int OUT>
-__device__ __forceinline__ void pdp_dense(const float (&in)[IN], float (&out)[OUT], const float* w, int n_out, int inp) {
-    const float* wm = w + ((n_out + 3) & ~3);
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) {
-        float a = 0.f;
-        if (o < n_out) {
-            a = w[o];
-            const float* r = wm + o * inp;
-#pragma unroll
-            for (int i = 0; i < IN; i += 8)
-                if (i < inp) {
-                    const float4 u = *reinterpret_cast<const float4*>(r + i);
-                    const float4 v = *reinterpret_cast<const float4*>(r + i + 4);
-                    a = fmaf(in[i], u.x, a); a = fmaf(in[i + 1], u.y, a); a = fmaf(in[i + 2], u.z, a); a = fmaf(in[i + 3], u.w, a);
-                    a = fmaf(in[i + 4], v.x, a); a = fmaf(in[i + 5], v.y, a); a = fmaf(in[i + 6], v.z, a); a = fmaf(in[i + 7], v.w, a);
-                }
-        }
-        out[o] = a;
-    }
-}
 
 // layer 0's pre-activation h (bias and grid shift included) -> the prediction y (first C entries; output function when asked)
 template <int H0P>
@@ -132,45 +71,6 @@ __device__ __forceinline__ void pdp_forward(const PdpParams& p, float (&h)[H0P],
 #pragma unroll
         for (int c = 0; c < kPdpTail; ++c)
             if (c < p.C && c >= p.C / 2) y[c] = softplus_f(y[c]);
-    }
-}
-
-// layer 0 without bias of set S (and, recursively, of the sets after it) for this thread's row: the set's weights are staged in LDS
-// by the whole workgroup, then every thread reads its row of X once.  (A recursion rather than a loop: z0[S] needs a constant index
-// to stay in registers.)
-template <int S, int H0P, int NS>
-__device__ __forceinline__ void pdp_layer0(const PdpParams& p, float (&z0)[NS][H0P], bool live, long long row) {
-    if constexpr (S < NS) {
-        extern __shared__ float4 pdp_lds[];
-        const float* sw0 = reinterpret_cast<const float*>(pdp_lds);
-        float (&z)[H0P] = z0[S];
-#pragma unroll
-        for (int h = 0; h < H0P; ++h) z[h] = 0.f;
-        if (S < p.n_set) {                                            // (block-uniform)
-            __syncthreads();
-            const float4* src = reinterpret_cast<const float4*>(p.w0t + (size_t)(p.set0 + S) * p.Fp * H0P);
-            for (int i = threadIdx.x; i < p.Fp * H0P / 4; i += kPdpRows) pdp_lds[i] = src[i];
-            __syncthreads();
-            if (live) {
-                const float4* xr = reinterpret_cast<const float4*>(p.X + row * p.Fp);
-                for (int f4 = 0; f4 < p.Fp / 4; ++f4) {
-                    const float4 x = xr[f4];
-                    const float* w = sw0 + (size_t)f4 * 4 * H0P;
-#pragma unroll
-                    for (int h = 0; h < H0P; h += 4) {
-                        const float4 a = *reinterpret_cast<const float4*>(w + h);
-                        const float4 b = *reinterpret_cast<const float4*>(w + H0P + h);
-                        const float4 c = *reinterpret_cast<const float4*>(w + 2 * H0P + h);
-                        const float4 d = *reinterpret_cast<const float4*>(w + 3 * H0P + h);
-                        z[h] = fmaf(x.w, d.x, fmaf(x.z, c.x, fmaf(x.y, b.x, fmaf(x.x, a.x, z[h]))));
-                        z[h + 1] = fmaf(x.w, d.y, fmaf(x.z, c.y, fmaf(x.y, b.y, fmaf(x.x, a.y, z[h + 1]))));
-                        z[h + 2] = fmaf(x.w, d.z, fmaf(x.z, c.z, fmaf(x.y, b.z, fmaf(x.x, a.z, z[h + 2]))));
-                        z[h + 3] = fmaf(x.w, d.w, fmaf(x.z, c.w, fmaf(x.y, b.w, fmaf(x.x, a.w, z[h + 3]))));
-                    }
-                }
-            }
-        }
-        pdp_layer0<S + 1>(p, z0, live, row);
     }
 }
 
@@ -217,50 +117,6 @@ __global__ __launch_bounds__(kPdpRows) void pdp_kernel(const PdpParams p) {
 #pragma unroll
         for (int c = 0; c < kPdpTail; ++c)
             if (c < p.C) a[c] = p.accumulate ? a[c] + ys[c] : ys[c];
-    }
-}
-
-// grid (n_sets), block 256: a set's float64 weights -> route 1's float32 blocks.  co_all [n_grid][F]: per grid point the constant of
-// every overridden column (NaN = the data); the overridden columns are the same for every grid point.
-__global__ __launch_bounds__(256) void pdp_prep_kernel(const PdpPrep q, const double* W, const double* co_all, float* w0t, float* bias,
-                                                       float* tail) {
-    const int s = blockIdx.x;
-    const double* w = W + (size_t)s * q.wn;
-    const int in0 = q.F + q.hb0;
-    float* dw = w0t + (size_t)s * q.Fp * q.H0P;
-    for (int i = threadIdx.x; i < q.Fp * q.H0P; i += blockDim.x) {
-        const int f = i / q.H0P, h = i % q.H0P;
-        float v = 0.f;
-        if (f < q.F && h < q.H0 && __builtin_isnan(co_all[f])) v = (float)w[(size_t)h * in0 + q.hb0 + f];
-        dw[i] = v;
-    }
-    float* db = bias + (size_t)s * q.n_grid * q.H0P;
-    for (int i = threadIdx.x; i < q.n_grid * q.H0P; i += blockDim.x) {
-        const int g = i / q.H0P, h = i % q.H0P;
-        double a = 0.0;
-        if (h < q.H0) {
-            const double* wr = w + (size_t)h * in0;
-            const double* co = co_all + (size_t)g * q.F;
-            if (q.hb0) a = wr[0];
-            for (int f = 0; f < q.F; ++f)
-                if (!__builtin_isnan(co[f])) a += co[f] * wr[q.hb0 + f];
-        }
-        db[i] = (float)a;
-    }
-    float* dt = tail + (size_t)s * q.tail_floats;
-    for (int l = 1; l < q.n_layers; ++l) {
-        const int n_out = q.l_out[l], inp = q.t_inp[l], hb = q.l_hb[l], stride = q.l_in[l] + hb, r4 = (n_out + 3) & ~3;
-        const double* wl = w + q.l_woff[l];
-        for (int i = threadIdx.x; i < r4 + n_out * inp; i += blockDim.x) {
-            float v = 0.f;
-            if (i < r4) {
-                if (i < n_out && hb) v = (float)wl[(size_t)i * stride];
-            } else {
-                const int j = i - r4, o = j / inp, k = j % inp;
-                if (k < q.l_in[l]) v = (float)wl[(size_t)o * stride + hb + k];
-            }
-            dt[q.t_off[l] + i] = v;
-        }
     }
 }
 
@@ -440,85 +296,7 @@ __global__ __launch_bounds__(256) void ale_reduce_kernel(const double* part, int
     *dst = v;
 }
 
-bool env_on(const char* name) {
-    const char* e = getenv(name);
-    return e && *e && strcmp(e, "0") != 0;
-}
-
-size_t env_bytes(const char* name, size_t otherwise) {
-    if (const char* e = getenv(name)) { const long long v = atoll(e); if (v > 0) return (size_t)v; }
-    return otherwise;
-}
-
 // ---- what npbnn_predict_pdp and npbnn_predict_ale share on the host
-
-// Route 1's shapes for a network and n_points shifted biases (grid points, or bin edges), and whether the network is inside its
-// envelope (include/npbnn_hip.h); `off`: the environment variable that forces route 2.
-struct Route1Plan {
-    PdpPrep q{};
-    int H0P = 32, NS = 2;
-    bool fits = false;
-};
-
-Route1Plan plan_route1(const npbnn_ctx* ctx, int Fp, int n_points, const char* off) {
-    Route1Plan r;
-    const int F = ctx->arch.in_dim, L = ctx->net.n_layers, H0 = ctx->arch.out_dim[0];
-    r.H0P = H0 <= 32 ? 32 : 64;
-    r.NS = 64 / r.H0P;
-    r.fits = !ctx->wide && !env_on(off) && H0 <= kPdpMaxH0 && (size_t)Fp * r.H0P * 4 <= kPdpW0Lds;
-    PdpPrep& q = r.q;
-    q.F = F; q.Fp = Fp; q.H0 = H0; q.H0P = r.H0P; q.hb0 = ctx->arch.has_bias[0]; q.n_layers = L; q.n_grid = n_points; q.wn = ctx->n_weights;
-    int woff = H0 * (F + q.hb0), toff = 0;
-    for (int l = 1; l < L; ++l) {
-        q.l_in[l] = ctx->arch.out_dim[l - 1];
-        q.l_out[l] = ctx->arch.out_dim[l];
-        q.l_hb[l] = ctx->arch.has_bias[l];
-        q.l_woff[l] = woff;
-        woff += q.l_out[l] * (q.l_in[l] + q.l_hb[l]);
-        q.t_inp[l] = round_up(q.l_in[l], 8);
-        q.t_off[l] = toff;
-        toff += round_up(q.l_out[l], 4) + q.l_out[l] * q.t_inp[l];
-        if (q.l_out[l] > kPdpTail) r.fits = false;
-    }
-    q.tail_floats = toff;
-    if (L == 1 && ctx->net.n_out > kPdpTail) r.fits = false;
-    if ((size_t)r.NS * q.tail_floats * 4 > kPdpTailLds) r.fits = false;
-    return r;
-}
-
-struct Route1Blocks {
-    DevBuf<float> w0t, bias, tail, slopes;
-};
-
-// Route 1's float32 blocks of every set (pdp_prep_kernel, enqueued on ctx->stream) and the kernel parameters that do not change from
-// launch to launch; d_w [n_sets][n_weights], d_co [n_points][F] on the device.
-int prepare_route1(npbnn_ctx* ctx, const Route1Plan& r, const FeatureTable& m, const double* d_w, const double* d_co, const double* act_prm_sets,
-                   int n_sets, int apply_out_fn, Route1Blocks* b, PdpParams* out) {
-    const PdpPrep& q = r.q;
-    const int L = q.n_layers, n_act = L - 1;
-    int rc;
-    if ((rc = dev_alloc(ctx, b->w0t, (size_t)n_sets * q.Fp * q.H0P))) return rc;
-    if ((rc = dev_alloc(ctx, b->bias, (size_t)n_sets * q.n_grid * q.H0P))) return rc;
-    if ((rc = dev_alloc(ctx, b->tail, (size_t)n_sets * q.tail_floats))) return rc;
-    if ((rc = dev_alloc(ctx, b->slopes, (size_t)n_sets * kMaxLayers))) return rc;
-    std::vector<float> slopes((size_t)n_sets * kMaxLayers, 0.f);
-    if (act_prm_sets)
-        for (int s = 0; s < n_sets; ++s)
-            for (int l = 0; l < n_act; ++l) slopes[(size_t)s * kMaxLayers + l] = (float)act_prm_sets[(size_t)s * n_act + l];
-    // (pageable memory: the copy has left `slopes` when the call returns)
-    HIP_TRY(ctx, hipMemcpyAsync(b->slopes.get(), slopes.data(), slopes.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(pdp_prep_kernel, dim3(n_sets), dim3(256), 0, ctx->stream, q, d_w, d_co, b->w0t.get(), b->bias.get(), b->tail.get());
-    HIP_TRY(ctx, hipGetLastError());
-    PdpParams p{};
-    p.X = m.X; p.n_rows = m.n_rows; p.Fp = q.Fp;
-    p.w0t = b->w0t.get(); p.bias = b->bias.get(); p.tail = b->tail.get(); p.slopes = b->slopes.get();
-    p.n_grid = q.n_grid; p.tail_floats = q.tail_floats;
-    p.n_layers = L; p.act_kind = ctx->arch.act_kind; p.final_act = ctx->arch.final_act; p.out_kind = ctx->arch.out_kind;
-    p.apply_out = apply_out_fn ? 1 : 0; p.C = ctx->net.n_out;
-    for (int l = 1; l < L; ++l) { p.t_out[l] = q.l_out[l]; p.t_inp[l] = q.t_inp[l]; p.t_off[l] = q.t_off[l]; }
-    *out = p;
-    return NPBNN_OK;
-}
 
 // Route 2: one pass of the evaluation kernels per (point, group of sets), the point's constants d_co [n_points][F] folded into layer
 // 0's bias; sets that share their activation slopes travel together, as many as one pass carries.  on_pass(p0, i, s0, ng): the float32
