@@ -206,7 +206,10 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
        NPBNN_INFO_ALE_ROUTE = 26,
        /* the route that served the last npbnn_predict_saliency (1 or 2; 0 before any call, and after one that was refused), and with
         * NPBNN_FI_TIMING=1 the device time in nanoseconds of its phase 2: the fold and reduce kernels of every launch (0 otherwise) */
-       NPBNN_INFO_SALIENCY_ROUTE = 27, NPBNN_INFO_SALIENCY_FOLD_NS = 28 };
+       NPBNN_INFO_SALIENCY_ROUTE = 27, NPBNN_INFO_SALIENCY_FOLD_NS = 28,
+       /* the route that served the last npbnn_predict_shapley (1 or 2; 0 before any call, and after one that was refused), and with
+        * NPBNN_FI_TIMING=1 the device time in nanoseconds of its walk kernels (0 otherwise) */
+       NPBNN_INFO_SHAPLEY_ROUTE = 29, NPBNN_INFO_SHAPLEY_WALK_NS = 30 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -302,6 +305,47 @@ int npbnn_predict_ale(npbnn_ctx* ctx, const double* W_sets, const double* act_pr
  * npbnn_set_arch or without data on `which`. */
 int npbnn_predict_saliency(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, const double* col_override, int which,
                            int apply_out_fn, double* out_mean, double* out_abs, double* out_sq);
+
+/* Permutation-sampling Shapley attributions of single rows, per stored weight set; np_bnn has no counterpart.  f_s is the network of set s
+ * (through the output function with apply_out_fn = 1, the last layer's values with 0), x_e row rows[e] of the resident matrix `which`, b row
+ * bg_rows[.] of the resident matrix `which_bg`, both after col_override.  A player is a group of columns: player_of [in_dim] names every
+ * column's player (NULL: column j is player j, and n_players must be in_dim).  Each row of perms [n_perm][n_players] is a permutation pi of
+ * the players.  A walk (s, e, b, pi) starts at b and at step k sets every column of player pi[k] to x_e's value;
+ *   phi_walk[pi[k]][c] = f_s(after step k)_c - f_s(before step k)_c,   phi[s][e][p][c] = mean over the n_bg n_perm walks of phi_walk[p][c],
+ * so sum_p phi[s][e][p][c] = f_s(x_e)_c - mean_b f_s(b)_c for any permutations, and with all n_players! of them phi is the exact
+ * interventional Shapley value over the background rows.  A player whose columns are all overridden is exactly 0.  The outputs:
+ *   out_mean  [n_explain][n_players][C]           mean over the sets of phi
+ *   out_sq    [n_explain][n_players][C]           mean over the sets of phi^2
+ *   out_abs   [n_sets][n_players][C]              mean over the explained rows of |phi|
+ *   out_fx    [n_sets][n_explain][C]              f_s(x_e), one direct forward pass
+ *   out_base  [n_sets][C]                         mean_b f_s(b)
+ *   out_phi   [n_sets][n_explain][n_players][C]   phi itself, or NULL: not wanted.  NPBNN_E_NOMEM when it is over its byte budget (256 MiB;
+ *             NPBNN_SHAPLEY_PHI_BYTES in the environment overrides it); the message names the largest n_explain that fits.
+ * The tables, the hybrid rows and the walks' differences stay on the device.  A step moves layer 0's pre-activation by W0[:, j] (x_ej - b_j)
+ * per column of its player and runs the later layers again.  A lane owns one explained row and the 64 lanes of a wave share (set, b, pi);
+ * z0(b) is computed once per (set, b).  The W = n_bg n_perm walks, b-major, are cut into n_split runs of consecutive walks, one wave each;
+ * n_split depends on the sizes, the device's compute units and the scratch budget below: another budget or device gives other splits, so the
+ * same values to rounding, not the same bits.  NPBNN_INFO_SHAPLEY_ROUTE tells which kernels served the call:
+ *   1  networks inside npbnn_predict_pdp's route-1 envelope (limits a - d above): the set's transposed first layer in LDS, z0 in registers,
+ *      the later layers in registers from LDS broadcasts;
+ *   2  every other network the library takes: plain kernels with runtime widths whose z0 and activations live in a device scratch
+ *      [unit][value][lane].  NPBNN_SHAPLEY_PLAIN=1 (environment) forces it, and so does NPBNN_FORCE_WIDE=1.
+ * Both read the float32 matrix only: NPBNN_OPT_L0_PRECISION plays no part, and there is no fp16-range repeat.  Arithmetic is float32 inside a
+ * walk, the difference of two float32 predictions included.  Every sum is float64: a wave adds its walks' differences in walk order, the
+ * splits are added in split order, the sets in set order, the rows of |phi| per thread in row order, then over the workgroup and the chunks in
+ * a fixed order; out_base is the float64 mean of the float32 f_s(b).  No floating-point atomics: the same input gives the same bits on every
+ * call.  The waves' partial sums (and route 2's scratch) have a byte budget (128 MiB; NPBNN_SHAPLEY_SCRATCH_BYTES in the environment overrides
+ * it): a larger job runs in chunks of explained rows, and launches of fewer sets.  With NPBNN_FI_TIMING=1 the device time of the walk kernels
+ * goes to NPBNN_INFO_SHAPLEY_WALK_NS (an int: it ends at 2147 ms).  Measured on an MI355X (tools/time_shapley.py, tests/test_hip_shapley.py -s;
+ * NOTES 8.14): config 2's shapes, 100 sets, 64 rows x 4 backgrounds x 2 permutations 21.4 ms against 600.5 ms through a table of hybrid rows and
+ * npbnn_predict_sets; 256 x 20 x 8 1584 ms under the default budget, whose 102 waves at once bound it, 114.8 ms under 4 GiB; largest error
+ * against float64 1.9e-06 of an array's largest entry on either route.  NPBNN_E_ARG, before any launch: a null required pointer; n_sets, n_explain, n_bg, n_perm or n_players
+ * below 1; a row index outside its table; a player_of entry outside 0 .. n_players - 1; a player without a column; a row of perms that is not
+ * a permutation.  NPBNN_E_STATE without npbnn_set_arch or without data on either table.  A refused call leaves the outputs untouched. */
+int npbnn_predict_shapley(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, const double* col_override, int which,
+                          const int64_t* rows, int32_t n_explain, int which_bg, const int64_t* bg_rows, int32_t n_bg, const int32_t* player_of,
+                          int32_t n_players, const int32_t* perms, int32_t n_perm, int apply_out_fn, double* out_mean, double* out_sq,
+                          double* out_abs, double* out_fx, double* out_base, double* out_phi);
 
 /* Posterior credible intervals: calcHPD (np_bnn/BNN_lib.py:286-302) applied to every (row, output) of the n_sets stored samples'
  * predictions, as its summary code does once per row (np_bnn/BNN_plot.py:73-75).  The sets replay as in npbnn_predict_sets, but

@@ -42,6 +42,8 @@ INFO_CALIBRATION_FINAL_NS = 25
 INFO_ALE_ROUTE = 26
 INFO_SALIENCY_ROUTE = 27
 INFO_SALIENCY_FOLD_NS = 28
+INFO_SHAPLEY_ROUTE = 29
+INFO_SHAPLEY_WALK_NS = 30
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
 E_STATE = -2
@@ -152,6 +154,9 @@ SIGNATURES = {
                                     C.c_int, _DP]),
     "npbnn_predict_ale": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int32, _DP, C.c_int32, _DP, C.c_int, C.c_int, C.POINTER(C.c_int64), _DP]),
     "npbnn_predict_saliency": (C.c_int, [_P, _DP, _DP, C.c_int32, _DP, C.c_int, C.c_int, _DP, _DP, _DP]),
+    "npbnn_predict_shapley": (C.c_int, [_P, _DP, _DP, C.c_int32, _DP, C.c_int, C.POINTER(C.c_int64), C.c_int32, C.c_int, C.POINTER(C.c_int64),
+                                        C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int, _DP, _DP, _DP,
+                                        _DP, _DP, _DP]),
     "npbnn_predict_sets_hpd": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
     "npbnn_permute_columns": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64), C.c_int32]),
     "npbnn_predict_sets_summary": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _DP,

@@ -598,6 +598,37 @@ class HipContext:
                                                    1 if apply_out_fn else 0, capi.dptr(out[0]), capi.dptr(out[1]), capi.dptr(out[2])))
         return tuple(out)
 
+    def predict_shapley(self, weight_sets, rows, bg_rows, perms, player_of=None, act_prm_sets=None, col_override=None, which=capi.TRAIN,
+                        which_bg=None, apply_out_fn=True, want_phi=False):
+        """Permutation-sampling Shapley attributions (npbnn_predict_shapley) of the rows ``rows`` of the resident matrix ``which``
+        against the rows ``bg_rows`` of the resident matrix ``which_bg`` (default: the same), along the permutations ``perms``
+        [n_perm, P] of the P players; ``player_of`` [F] names every column's player (None: a column is a player).  A dict:
+        ``mean`` and ``sq`` [E, P, n_out], the means over the weight sets of phi and phi^2; ``abs`` [S, P, n_out], the mean over
+        the rows of |phi|; ``fx`` [S, E, n_out]; ``base`` [S, n_out]; ``phi`` [S, E, P, n_out] with ``want_phi``, else None.
+        NPBNN_INFO_SHAPLEY_ROUTE: the route taken."""
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, "predict_shapley")
+        i64, i32 = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        rows = np.ascontiguousarray(rows, dtype=np.int64).ravel()
+        bg = np.ascontiguousarray(bg_rows, dtype=np.int64).ravel()
+        pm = np.ascontiguousarray(perms, dtype=np.int32)
+        if pm.ndim != 2:
+            raise ValueError("predict_shapley: perms must be [n_perm, n_players]")
+        n_perm, n_players = pm.shape
+        po = None if player_of is None else np.ascontiguousarray(player_of, dtype=np.int32).ravel()
+        if po is not None and len(po) != int(self.arch.in_dim):
+            raise ValueError("predict_shapley: player_of needs one entry per feature column")
+        co = None if col_override is None else capi.as_f64(np.asarray(col_override, dtype=np.float64).ravel())
+        e, n_out = len(rows), self.n_out
+        res = dict(mean=np.zeros((e, n_players, n_out)), sq=np.zeros((e, n_players, n_out)), abs=np.zeros((n_sets, n_players, n_out)),
+                   fx=np.zeros((n_sets, e, n_out)), base=np.zeros((n_sets, n_out)),
+                   phi=np.zeros((n_sets, e, n_players, n_out)) if want_phi else None)
+        self._chk(self._lib.npbnn_predict_shapley(
+            self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, capi.dptr(co), which, rows.ctypes.data_as(i64), e,
+            which if which_bg is None else which_bg, bg.ctypes.data_as(i64), len(bg), None if po is None else po.ctypes.data_as(i32), n_players,
+            pm.ctypes.data_as(i32), n_perm, 1 if apply_out_fn else 0, capi.dptr(res["mean"]), capi.dptr(res["sq"]), capi.dptr(res["abs"]),
+            capi.dptr(res["fx"]), capi.dptr(res["base"]), capi.dptr(res["phi"])))
+        return res
+
     def time_eval(self, weights, iters=20):
         w = one_vector(weights)
         a, b = C.c_double(0), C.c_double(0)

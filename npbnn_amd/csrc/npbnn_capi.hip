@@ -963,6 +963,8 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     if (what == NPBNN_INFO_ALE_ROUTE) { *out = ctx->ale_route; return NPBNN_OK; }
     if (what == NPBNN_INFO_SALIENCY_ROUTE) { *out = ctx->saliency_route; return NPBNN_OK; }
     if (what == NPBNN_INFO_SALIENCY_FOLD_NS) { *out = ctx->saliency_ns; return NPBNN_OK; }
+    if (what == NPBNN_INFO_SHAPLEY_ROUTE) { *out = ctx->shapley_route; return NPBNN_OK; }
+    if (what == NPBNN_INFO_SHAPLEY_WALK_NS) { *out = ctx->shapley_ns; return NPBNN_OK; }
     if (what == NPBNN_INFO_REPLAY_PASSES) { *out = ctx->replay_passes; return NPBNN_OK; }
     if (what == NPBNN_INFO_REPLAY_MAX_GROUP) { *out = ctx->replay_max_group; return NPBNN_OK; }
     if (what == NPBNN_INFO_CALIBRATION_FINAL_NS) { *out = ctx->calibration_ns; return NPBNN_OK; }

@@ -248,6 +248,8 @@ struct npbnn_ctx : npbnn_ctx_streams {
     int ale_route = 0;             // route of the last npbnn_predict_ale: 1 both edges from one read of X, 2 per edge; 0 none, or refused (NPBNN_INFO_ALE_ROUTE)
     int saliency_route = 0;        // route of the last npbnn_predict_saliency: 1 phase 1 in registers, 2 the plain kernel; 0 none, or refused (NPBNN_INFO_SALIENCY_ROUTE)
     int saliency_ns = 0;           // NPBNN_FI_TIMING: the last npbnn_predict_saliency's fold and reduce kernels (NPBNN_INFO_SALIENCY_FOLD_NS)
+    int shapley_route = 0;         // route of the last npbnn_predict_shapley: 1 the walks in registers, 2 the plain kernels; 0 none, or refused (NPBNN_INFO_SHAPLEY_ROUTE)
+    int shapley_ns = 0;            // NPBNN_FI_TIMING: the last npbnn_predict_shapley's walk kernels (NPBNN_INFO_SHAPLEY_WALK_NS)
     // weight-streamed path (npbnn_wide.hip): the network does not fit a compute unit's LDS (or NPBNN_OPT_WIDE asks for it)
     bool wide = false;
     int wide_option = 0;           // NPBNN_OPT_WIDE: 0 when the resident path cannot hold the network, 1 always

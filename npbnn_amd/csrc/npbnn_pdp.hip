@@ -17,8 +17,8 @@
 // and set; route 2 (ale_pick_kernel) picks each pass's predictions by bin.  Either way the differences are added per (bin, output)
 // over a workgroup's rows in row order, then over the workgroups in a fixed order (ale_reduce_kernel), in float64 and without atomics.
 //
-// Route 1's float32 blocks, its layer-0 stage and its host set-up (pdp_prep_kernel, pdp_layer0, pdp_dense, plan_route1, prepare_route1)
-// are in npbnn_route1.hip.h, which npbnn_saliency.hip includes too.
+// Route 1's float32 blocks, its layer-0 stage, the later layers and its host set-up (pdp_prep_kernel, pdp_layer0, pdp_dense, pdp_forward,
+// plan_route1, prepare_route1) are in npbnn_route1.hip.h, which npbnn_saliency.hip and npbnn_shapley.hip include too.
 #include "npbnn_route1.hip.h"
 
 #include <cmath>
@@ -32,47 +32,6 @@ namespace {
 
 constexpr size_t kPdpAccBytes = 512ull << 20;    // device budget of the float32 accumulator [grid points][rows][outputs]: larger grids
                                                  // run in chunks of grid points, each chunk one more read of X per set group
-
-// layer 0's pre-activation h (bias and grid shift included) -> the prediction y (first C entries; output function when asked)
-template <int H0P>
-__device__ __forceinline__ void pdp_forward(const PdpParams& p, float (&h)[H0P], const float* w, const float* sl, float (&y)[kPdpTail]) {
-    static_assert(H0P >= kPdpTail, "layer 0 is at least as wide as the later layers' bound");
-    const int L = p.n_layers;
-    if (L == 1) {
-        if (p.final_act) pdp_act(h, p.act_kind, sl[0]);
-#pragma unroll
-        for (int c = 0; c < kPdpTail; ++c) y[c] = h[c];
-    } else {
-        pdp_act(h, p.act_kind, sl[0]);
-        pdp_dense<H0P, kPdpTail>(h, y, w + p.t_off[1], p.t_out[1], p.t_inp[1]);
-        for (int l = 2; l < L; ++l) {
-            pdp_act(y, p.act_kind, sl[l - 1]);
-            float nx[kPdpTail];
-            pdp_dense<kPdpTail, kPdpTail>(y, nx, w + p.t_off[l], p.t_out[l], p.t_inp[l]);
-#pragma unroll
-            for (int c = 0; c < kPdpTail; ++c) y[c] = nx[c];
-        }
-        if (p.final_act) pdp_act(y, p.act_kind, sl[L - 1]);
-    }
-    if (!p.apply_out) return;
-    if (p.out_kind == NPBNN_OUT_SOFTMAX) {           // SoftMax (BNN_lib.py:166-168)
-        float m = -3.402823466e38f;
-#pragma unroll
-        for (int c = 0; c < kPdpTail; ++c)
-            if (c < p.C) m = fmaxf(m, y[c]);
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < kPdpTail; ++c)
-            if (c < p.C) { y[c] = __expf(y[c] - m); s += y[c]; }
-        const float r = 1.f / s;
-#pragma unroll
-        for (int c = 0; c < kPdpTail; ++c) y[c] *= r;
-    } else if (p.out_kind == NPBNN_OUT_SOFTPLUS_HALF) {   // RegressTransformError (BNN_lib.py:177-182)
-#pragma unroll
-        for (int c = 0; c < kPdpTail; ++c)
-            if (c < p.C && c >= p.C / 2) y[c] = softplus_f(y[c]);
-    }
-}
 
 // grid point g for set S (and, recursively, the sets after it): shifted bias, later layers, output function, summed into ys
 template <int S, int H0P, int NS>

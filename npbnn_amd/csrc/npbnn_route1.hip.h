@@ -1,7 +1,8 @@
-// Route 1 of npbnn_predict_pdp, npbnn_predict_ale (npbnn_pdp.hip) and npbnn_predict_saliency (npbnn_saliency.hip): what they share.  A
-// set's float64 weights as float32 blocks (pdp_prep_kernel: layer 0 transposed with zero rows on the overridden columns, its bias
-// with the overrides folded in, the later layers), the layer-0 product of one thread per row from a weight image staged in LDS
-// (pdp_layer0), the later layers from LDS broadcasts (pdp_dense), the envelope (plan_route1) and the host set-up (prepare_route1).
+// Route 1 of npbnn_predict_pdp, npbnn_predict_ale (npbnn_pdp.hip), npbnn_predict_saliency (npbnn_saliency.hip) and
+// npbnn_predict_shapley (npbnn_shapley.hip): what they share.  A set's float64 weights as float32 blocks (pdp_prep_kernel: layer 0
+// transposed with zero rows on the overridden columns, its bias with the overrides folded in, the later layers), the layer-0 product
+// of one thread per row from a weight image staged in LDS (pdp_layer0), the later layers from LDS broadcasts (pdp_dense), the
+// prediction from layer 0's pre-activation (pdp_forward), the envelope (plan_route1) and the host set-up (prepare_route1).
 // Every unit that includes this header gets its own copy of the kernels.  Not part of the ABI.
 #pragma once
 #include "npbnn_sets.hip.h"
@@ -76,6 +77,47 @@ __device__ __forceinline__ void pdp_dense(const float (&in)[IN], float (&out)[OU
                 }
         }
         out[o] = a;
+    }
+}
+
+// layer 0's pre-activation h (bias and grid shift included) -> the prediction y (first C entries; output function when asked)
+template <int H0P>
+__device__ __forceinline__ void pdp_forward(const PdpParams& p, float (&h)[H0P], const float* w, const float* sl, float (&y)[kPdpTail]) {
+    static_assert(H0P >= kPdpTail, "layer 0 is at least as wide as the later layers' bound");
+    const int L = p.n_layers;
+    if (L == 1) {
+        if (p.final_act) pdp_act(h, p.act_kind, sl[0]);
+#pragma unroll
+        for (int c = 0; c < kPdpTail; ++c) y[c] = h[c];
+    } else {
+        pdp_act(h, p.act_kind, sl[0]);
+        pdp_dense<H0P, kPdpTail>(h, y, w + p.t_off[1], p.t_out[1], p.t_inp[1]);
+        for (int l = 2; l < L; ++l) {
+            pdp_act(y, p.act_kind, sl[l - 1]);
+            float nx[kPdpTail];
+            pdp_dense<kPdpTail, kPdpTail>(y, nx, w + p.t_off[l], p.t_out[l], p.t_inp[l]);
+#pragma unroll
+            for (int c = 0; c < kPdpTail; ++c) y[c] = nx[c];
+        }
+        if (p.final_act) pdp_act(y, p.act_kind, sl[L - 1]);
+    }
+    if (!p.apply_out) return;
+    if (p.out_kind == NPBNN_OUT_SOFTMAX) {           // SoftMax (BNN_lib.py:166-168)
+        float m = -3.402823466e38f;
+#pragma unroll
+        for (int c = 0; c < kPdpTail; ++c)
+            if (c < p.C) m = fmaxf(m, y[c]);
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < kPdpTail; ++c)
+            if (c < p.C) { y[c] = __expf(y[c] - m); s += y[c]; }
+        const float r = 1.f / s;
+#pragma unroll
+        for (int c = 0; c < kPdpTail; ++c) y[c] *= r;
+    } else if (p.out_kind == NPBNN_OUT_SOFTPLUS_HALF) {   // RegressTransformError (BNN_lib.py:177-182)
+#pragma unroll
+        for (int c = 0; c < kPdpTail; ++c)
+            if (c < p.C && c >= p.C / 2) y[c] = softplus_f(y[c]);
     }
 }
 
