@@ -24,6 +24,7 @@
 #include "numpy/random/bitgen.h"
 #include "numpy/random/distributions.h"
 
+#include "npbnn_attrib_plan.h"
 #include "npbnn_resident_plan.h"
 #include "npbnn_sched_plan.h"
 #include "npbnn_wide_plan.h"
@@ -753,3 +754,31 @@ int npbnn_host_resident_launch(const npbnn_resident_layout* y, const int32_t* re
 }
 int npbnn_host_resident_max_waves(int mt0, int mti, int f16, int d, int lk, int fast) { return max_waves_for(mt0, mti, f16, d, lk, fast); }
 int npbnn_host_resident_max_cand(int mt0) { return max_cand_for(mt0) < kMaxCand ? max_cand_for(mt0) : kMaxCand; }
+
+/* The work plan of the attribution entries (npbnn_attrib_plan.h: what the HIP library chooses its route, cuts its jobs and sizes its
+ * buffers by), exported for the CPU tests of that rule.  req: the request's numbers in the order of its struct's fields after the
+ * pointer.  Return: 0, or the Shapley plan's refusal. */
+int npbnn_host_attrib_route(const npbnn_arch* arch, const int32_t* req, npbnn_attrib_route* out) {
+    if (!arch || !req || !out) return -1;
+    const npbnn_attrib_route_req r = {arch, req[0], req[1], req[2], req[3], req[4], req[5]};
+    npbnn_attrib_route_of(&r, out);
+    return 0;
+}
+int npbnn_host_attrib_saliency(const npbnn_attrib_route* r, const int64_t* req, npbnn_attrib_sal* out) {
+    if (!r || !req || !out) return -1;
+    const npbnn_attrib_sal_req s = {r, (int)req[0], (int)req[1], req[2], (int)req[3], req[4], req[5]};
+    npbnn_attrib_sal_of(&s, out);
+    return 0;
+}
+int npbnn_host_attrib_shapley(const npbnn_attrib_route* r, const int64_t* req, npbnn_attrib_shap* out) {
+    if (!r || !req || !out) return -1;
+    const npbnn_attrib_shap_req s = {r, (int)req[0], (int)req[1], (int)req[2], (int)req[3], (int)req[4], (int)req[5], (int)req[6], (int)req[7],
+                                     req[8], req[9], req[10]};
+    return npbnn_attrib_shap_of(&s, out);
+}
+int npbnn_host_attrib_pdp_g_chunk(int n_grid, int64_t n_rows, int C, int64_t acc_bytes) { return npbnn_attrib_pdp_g_chunk(n_grid, n_rows, C, acc_bytes); }
+int npbnn_host_attrib_ale(const npbnn_attrib_route* r, int K, int C, int64_t n_rows, int64_t part_bytes, npbnn_attrib_ale* out) {
+    if (!r || !out) return -1;
+    npbnn_attrib_ale_of(r, K, C, n_rows, part_bytes, out);
+    return 0;
+}

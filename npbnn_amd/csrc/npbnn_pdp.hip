@@ -17,8 +17,9 @@
 // and set; route 2 (ale_pick_kernel) picks each pass's predictions by bin.  Either way the differences are added per (bin, output)
 // over a workgroup's rows in row order, then over the workgroups in a fixed order (ale_reduce_kernel), in float64 and without atomics.
 //
-// Route 1's float32 blocks, its layer-0 stage, the later layers and its host set-up (pdp_prep_kernel, pdp_layer0, pdp_dense, pdp_forward,
-// plan_route1, prepare_route1) are in npbnn_route1.hip.h, which npbnn_saliency.hip and npbnn_shapley.hip include too.
+// Route 1's layer-0 stage, the later layers and the entries' shared host steps (pdp_layer0, pdp_dense, pdp_forward, plan_route,
+// upload_sets, Route1Kernel) are in npbnn_route1.hip.h, which npbnn_saliency.hip and npbnn_shapley.hip include too.  The preparation
+// of route 1's float32 blocks (pdp_prep_kernel, prepare_route1) is below, for all of them.
 #include "npbnn_route1.hip.h"
 
 #include <cmath>
@@ -76,6 +77,50 @@ __global__ __launch_bounds__(kPdpRows) void pdp_kernel(const PdpParams p) {
 #pragma unroll
         for (int c = 0; c < kPdpTail; ++c)
             if (c < p.C) a[c] = p.accumulate ? a[c] + ys[c] : ys[c];
+    }
+}
+
+// grid (n_sets), block 256: a set's float64 weights -> route 1's float32 blocks.  co_all [n_grid][F]: per grid point the constant of
+// every overridden column (NaN = the data); the overridden columns are the same for every grid point.
+__global__ __launch_bounds__(256) void pdp_prep_kernel(const PdpPrep q, const double* W, const double* co_all, float* w0t, float* bias,
+                                                       float* tail) {
+    const int s = blockIdx.x;
+    const double* w = W + (size_t)s * q.wn;
+    const int in0 = q.F + q.hb0;
+    float* dw = w0t + (size_t)s * q.Fp * q.H0P;
+    for (int i = threadIdx.x; i < q.Fp * q.H0P; i += blockDim.x) {
+        const int f = i / q.H0P, h = i % q.H0P;
+        float v = 0.f;
+        if (f < q.F && h < q.H0 && __builtin_isnan(co_all[f])) v = (float)w[(size_t)h * in0 + q.hb0 + f];
+        dw[i] = v;
+    }
+    float* db = bias + (size_t)s * q.n_grid * q.H0P;
+    for (int i = threadIdx.x; i < q.n_grid * q.H0P; i += blockDim.x) {
+        const int g = i / q.H0P, h = i % q.H0P;
+        double a = 0.0;
+        if (h < q.H0) {
+            const double* wr = w + (size_t)h * in0;
+            const double* co = co_all + (size_t)g * q.F;
+            if (q.hb0) a = wr[0];
+            for (int f = 0; f < q.F; ++f)
+                if (!__builtin_isnan(co[f])) a += co[f] * wr[q.hb0 + f];
+        }
+        db[i] = (float)a;
+    }
+    float* dt = tail + (size_t)s * q.tail_floats;
+    for (int l = 1; l < q.n_layers; ++l) {
+        const int n_out = q.l_out[l], inp = q.t_inp[l], hb = q.l_hb[l], stride = q.l_in[l] + hb, r4 = (n_out + 3) & ~3;
+        const double* wl = w + q.l_woff[l];
+        for (int i = threadIdx.x; i < r4 + n_out * inp; i += blockDim.x) {
+            float v = 0.f;
+            if (i < r4) {
+                if (i < n_out && hb) v = (float)wl[(size_t)i * stride];
+            } else {
+                const int j = i - r4, o = j / inp, k = j % inp;
+                if (k < q.l_in[l]) v = (float)wl[(size_t)o * stride + hb + k];
+            }
+            dt[q.t_off[l] + i] = v;
+        }
     }
 }
 
@@ -317,20 +362,36 @@ int run_point_passes(npbnn_ctx* ctx, const char* who, int which, const Dataset& 
     return NPBNN_OK;
 }
 
-// per point, every column's constant: col_override's where it has one (it applies after the point's values), else the point's value
-// on a focal column, else NaN
-std::vector<double> point_constants(int F, const double* col_override, const int32_t* focal, int n_focal, const double* values, int n_points) {
-    std::vector<double> co_all((size_t)n_points * F);
-    for (int g = 0; g < n_points; ++g) {
-        double* co = co_all.data() + (size_t)g * F;
-        for (int f = 0; f < F; ++f) co[f] = col_override ? col_override[f] : NAN;
-        for (int k = 0; k < n_focal; ++k)
-            if (std::isnan(col_override ? col_override[focal[k]] : NAN)) co[focal[k]] = values[(size_t)g * n_focal + k];
-    }
-    return co_all;
-}
-
 }  // namespace
+
+// (npbnn_route1.hip.h)
+int prepare_route1(npbnn_ctx* ctx, const npbnn_attrib_route& r, const FeatureTable& m, const double* d_w, const double* d_co, const double* act_prm_sets,
+                   int n_sets, int apply_out_fn, Route1Blocks* b, PdpParams* out) {
+    const PdpPrep& q = r.q;
+    const int L = q.n_layers, n_act = L - 1;
+    int rc;
+    if ((rc = dev_alloc(ctx, b->w0t, (size_t)n_sets * q.Fp * q.H0P))) return rc;
+    if ((rc = dev_alloc(ctx, b->bias, (size_t)n_sets * q.n_grid * q.H0P))) return rc;
+    if ((rc = dev_alloc(ctx, b->tail, (size_t)n_sets * q.tail_floats))) return rc;
+    if ((rc = dev_alloc(ctx, b->slopes, (size_t)n_sets * kMaxLayers))) return rc;
+    std::vector<float> slopes((size_t)n_sets * kMaxLayers, 0.f);
+    if (act_prm_sets)
+        for (int s = 0; s < n_sets; ++s)
+            for (int l = 0; l < n_act; ++l) slopes[(size_t)s * kMaxLayers + l] = (float)act_prm_sets[(size_t)s * n_act + l];
+    // (pageable memory: the copy has left `slopes` when the call returns)
+    HIP_TRY(ctx, hipMemcpyAsync(b->slopes.get(), slopes.data(), slopes.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(pdp_prep_kernel, dim3(n_sets), dim3(256), 0, ctx->stream, q, d_w, d_co, b->w0t.get(), b->bias.get(), b->tail.get());
+    HIP_TRY(ctx, hipGetLastError());
+    PdpParams p{};
+    p.X = m.X; p.n_rows = m.n_rows; p.Fp = q.Fp;
+    p.w0t = b->w0t.get(); p.bias = b->bias.get(); p.tail = b->tail.get(); p.slopes = b->slopes.get();
+    p.n_grid = q.n_grid; p.tail_floats = q.tail_floats;
+    p.n_layers = L; p.act_kind = ctx->arch.act_kind; p.final_act = ctx->arch.final_act; p.out_kind = ctx->arch.out_kind;
+    p.apply_out = apply_out_fn ? 1 : 0; p.C = ctx->net.n_out;
+    for (int l = 1; l < L; ++l) { p.t_out[l] = q.l_out[l]; p.t_inp[l] = q.t_inp[l]; p.t_off[l] = q.t_off[l]; }
+    *out = p;
+    return NPBNN_OK;
+}
 
 }  // namespace npbnn_api
 
@@ -349,21 +410,16 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
         if (focal[k] < 0 || focal[k] >= F) return fail(ctx, NPBNN_E_ARG, "predict_pdp: focal column %d outside 0..%d", focal[k], F - 1);
     const int C = ctx->net.n_out;
     const long long n_rows = tb.n_rows;
-    const size_t wn = (size_t)ctx->n_weights;
     const size_t per_set = (size_t)n_rows * C;
 
     const std::vector<double> co_all = point_constants(F, col_override, focal, n_focal, grid, n_grid);
-    const size_t budget = env_bytes("NPBNN_PDP_ACC_BYTES", kPdpAccBytes);
-    const size_t chunk_bytes = per_set * sizeof(float);
-    const int g_chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_grid, budget / std::max<size_t>(chunk_bytes, 1)));
+    const npbnn_attrib_route r1 = plan_route(ctx, NPBNN_ATTRIB_PDP, d.m->Fp, n_grid, "NPBNN_PDP_PER_GRID");
+    const int g_chunk = npbnn_attrib_pdp_g_chunk(n_grid, n_rows, C, (long long)env_bytes("NPBNN_PDP_ACC_BYTES", kPdpAccBytes));
 
     DevBuf<double> d_w, d_co;
     DevBuf<float> d_acc;
-    if ((rc = dev_alloc(ctx, d_w, (size_t)n_sets * wn))) return rc;
-    if ((rc = dev_alloc(ctx, d_co, co_all.size()))) return rc;
+    if ((rc = upload_sets(ctx, W_sets, n_sets, co_all, d_w, d_co))) return rc;
     if ((rc = dev_alloc(ctx, d_acc, (size_t)g_chunk * per_set))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(d_w.get(), W_sets, (size_t)n_sets * wn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_co.get(), co_all.data(), co_all.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     std::vector<float> host_acc((size_t)g_chunk * per_set);
     const double inv_sets = 1.0 / (double)n_sets;
     auto take_chunk = [&](int g0, int n_g) -> int {        // accumulator of grid points g0 .. g0 + n_g - 1 -> out_mean
@@ -375,16 +431,14 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
     };
 
     // ---- route 1: the grid-batched kernel
-    const Route1Plan r1 = plan_route1(ctx, d.m->Fp, n_grid, "NPBNN_PDP_PER_GRID");
     if (r1.fits) {
-        const int H0P = r1.H0P, NS = r1.NS;
+        const int NS = r1.NS;
         Route1Blocks blocks1;
         PdpParams p{};
         if ((rc = prepare_route1(ctx, r1, *d.m, d_w.get(), d_co.get(), act_prm_sets, n_sets, apply_out_fn, &blocks1, &p))) return rc;
         p.acc = d_acc.get();
-        const void* fn = H0P == 32 ? reinterpret_cast<const void*>(pdp_kernel<32, 2>) : reinterpret_cast<const void*>(pdp_kernel<64, 1>);
-        const size_t lds = ((size_t)p.Fp * H0P + (size_t)NS * p.tail_floats) * sizeof(float);
-        HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        Route1Kernel<PdpParams> kern;
+        if ((rc = kern.pick(ctx, r1.H0P, pdp_kernel<32, 2>, pdp_kernel<64, 1>, r1.lds_bytes))) return rc;
         const unsigned blocks = (unsigned)((n_rows + kPdpRows - 1) / kPdpRows);
         for (int g0 = 0; g0 < n_grid; g0 += g_chunk) {
             p.g0 = g0;
@@ -393,8 +447,7 @@ extern "C" int npbnn_predict_pdp(npbnn_ctx* ctx, const double* W_sets, const dou
                 p.set0 = s0;
                 p.n_set = std::min(NS, n_sets - s0);
                 p.accumulate = s0 > 0;
-                if (H0P == 32) hipLaunchKernelGGL((pdp_kernel<32, 2>), dim3(blocks), dim3(kPdpRows), lds, ctx->stream, p);
-                else hipLaunchKernelGGL((pdp_kernel<64, 1>), dim3(blocks), dim3(kPdpRows), lds, ctx->stream, p);
+                kern.launch(dim3(blocks), ctx->stream, p);
                 HIP_TRY(ctx, hipGetLastError());
             }
             if ((rc = take_chunk(g0, p.n_g))) return rc;
@@ -440,8 +493,11 @@ extern "C" int npbnn_predict_ale(npbnn_ctx* ctx, const double* W_sets, const dou
     if (focal < 0 || focal >= F) return fail(ctx, NPBNN_E_ARG, "predict_ale: focal column %d outside 0..%d", focal, F - 1);
     const long long n_rows = tb.n_rows;
     if (n_rows < 1) return fail(ctx, NPBNN_E_ARG, "predict_ale: the table has no rows");
-    const size_t wn = (size_t)ctx->n_weights, n_eff = (size_t)n_sets * K * C;
-    const unsigned n_wg = (unsigned)((n_rows + kPdpRows - 1) / kPdpRows);
+    const size_t n_eff = (size_t)n_sets * K * C;
+    const npbnn_attrib_route r1 = plan_route(ctx, NPBNN_ATTRIB_PDP, d.m->Fp, K + 1, "NPBNN_ALE_PER_EDGE");
+    npbnn_attrib_ale ap;
+    npbnn_attrib_ale_of(&r1, K, C, n_rows, (long long)env_bytes("NPBNN_ALE_PART_BYTES", kAlePartBytes), &ap);
+    const unsigned n_wg = (unsigned)ap.n_wg;
     hipStream_t st = ctx->stream;
 
     const std::vector<double> co_all = point_constants(F, col_override, &focal, 1, edges, K + 1);
@@ -451,14 +507,12 @@ extern "C" int npbnn_predict_ale(npbnn_ctx* ctx, const double* W_sets, const dou
     DevBuf<float> d_edges;
     DevBuf<int> d_bin;
     DevBuf<unsigned long long> d_counts;
-    if ((rc = dev_alloc(ctx, d_w, (size_t)n_sets * wn))) return rc;
-    if ((rc = dev_alloc(ctx, d_co, co_all.size()))) return rc;
+    if ((rc = upload_sets(ctx, W_sets, n_sets, co_all, d_w, d_co))) return rc;
     if ((rc = dev_alloc(ctx, d_acc, n_eff))) return rc;
+    if ((rc = dev_alloc(ctx, d_part, (size_t)ap.n_part))) return rc;
     if ((rc = dev_alloc(ctx, d_edges, edges_f.size()))) return rc;
     if ((rc = dev_alloc(ctx, d_bin, (size_t)n_rows))) return rc;
     if ((rc = dev_alloc(ctx, d_counts, (size_t)K))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(d_w.get(), W_sets, (size_t)n_sets * wn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_co.get(), co_all.data(), co_all.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_edges.get(), edges_f.data(), edges_f.size() * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetAsync(d_counts.get(), 0, (size_t)K * sizeof(unsigned long long), st));
     HIP_TRY(ctx, hipMemsetAsync(d_acc.get(), 0, n_eff * sizeof(double), st));
@@ -480,31 +534,23 @@ extern "C" int npbnn_predict_ale(npbnn_ctx* ctx, const double* W_sets, const dou
     };
 
     // ---- route 1: both edges of a row's bin from one read of X
-    const Route1Plan r1 = plan_route1(ctx, d.m->Fp, K + 1, "NPBNN_ALE_PER_EDGE");
     if (r1.fits) {
-        const int H0P = r1.H0P, NS = r1.NS;
+        const int NS = r1.NS;
+        const unsigned wg_chunk = (unsigned)ap.wg_chunk;
         Route1Blocks blocks1;
         PdpParams p{};
         if ((rc = prepare_route1(ctx, r1, *d.m, d_w.get(), d_co.get(), act_prm_sets, n_sets, apply_out_fn, &blocks1, &p))) return rc;
         AleParams a{};
-        a.bin = d_bin.get(); a.K = K;
-        a.stride = C | 1;
-        a.stage_floats = std::max(p.Fp * H0P, kPdpRows * (a.stride + 1));
-        const size_t wg_bytes = (size_t)NS * K * C * sizeof(double);
-        const unsigned wg_chunk = (unsigned)std::max<size_t>(1, std::min<size_t>(n_wg, env_bytes("NPBNN_ALE_PART_BYTES", kAlePartBytes) / wg_bytes));
-        if ((rc = dev_alloc(ctx, d_part, (size_t)wg_chunk * NS * K * C))) return rc;
-        a.part = d_part.get();
-        const void* fn = H0P == 32 ? reinterpret_cast<const void*>(ale_kernel<32, 2>) : reinterpret_cast<const void*>(ale_kernel<64, 1>);
-        const size_t lds = ((size_t)a.stage_floats + (size_t)NS * p.tail_floats) * sizeof(float);
-        HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        a.bin = d_bin.get(); a.K = K; a.stride = ap.stride; a.stage_floats = ap.stage_floats; a.part = d_part.get();
+        Route1Kernel<PdpParams, AleParams> kern;
+        if ((rc = kern.pick(ctx, r1.H0P, ale_kernel<32, 2>, ale_kernel<64, 1>, ap.lds_bytes))) return rc;
         for (int s0 = 0; s0 < n_sets; s0 += NS) {
             p.set0 = s0;
             p.n_set = std::min(NS, n_sets - s0);
             for (unsigned w0 = 0; w0 < n_wg; w0 += wg_chunk) {
                 const unsigned wgs = std::min(wg_chunk, n_wg - w0);
                 a.row0 = (long long)w0 * kPdpRows;
-                if (H0P == 32) hipLaunchKernelGGL((ale_kernel<32, 2>), dim3(wgs), dim3(kPdpRows), lds, st, p, a);
-                else hipLaunchKernelGGL((ale_kernel<64, 1>), dim3(wgs), dim3(kPdpRows), lds, st, p, a);
+                kern.launch(dim3(wgs), st, p, a);
                 HIP_TRY(ctx, hipGetLastError());
                 reduce(p.n_set, (int)wgs, K, s0, 0, 0, w0 + wgs == n_wg ? 1 : 0);
                 HIP_TRY(ctx, hipGetLastError());
@@ -514,7 +560,6 @@ extern "C" int npbnn_predict_ale(npbnn_ctx* ctx, const double* W_sets, const dou
     }
 
     // ---- route 2: one pass of the evaluation kernels per (edge, group of sets)
-    if ((rc = dev_alloc(ctx, d_part, (size_t)kMaxCand * n_wg * 2 * C))) return rc;
     rc = run_point_passes(ctx, "predict_ale", which, d, d_w.get(), d_co.get(), K + 1, K + 1, act_prm_sets, n_sets, apply_out_fn,
                           [&](int, int k, int s0, int ng) -> int {
                               if (k == 0 && s0 == 0)      // (the first pass of the call, or of its repeat on the float32 path)

@@ -1,25 +1,21 @@
-// Route 1 of npbnn_predict_pdp, npbnn_predict_ale (npbnn_pdp.hip), npbnn_predict_saliency (npbnn_saliency.hip) and
-// npbnn_predict_shapley (npbnn_shapley.hip): what they share.  A set's float64 weights as float32 blocks (pdp_prep_kernel: layer 0
-// transposed with zero rows on the overridden columns, its bias with the overrides folded in, the later layers), the layer-0 product
-// of one thread per row from a weight image staged in LDS (pdp_layer0), the later layers from LDS broadcasts (pdp_dense), the
-// prediction from layer 0's pre-activation (pdp_forward), the envelope (plan_route1) and the host set-up (prepare_route1).
-// Every unit that includes this header gets its own copy of the kernels.  Not part of the ABI.
+// What npbnn_predict_pdp, npbnn_predict_ale (npbnn_pdp.hip), npbnn_predict_saliency (npbnn_saliency.hip) and npbnn_predict_shapley
+// (npbnn_shapley.hip) share.  Route 1: a set's float64 weights as float32 blocks (prepare_route1: layer 0 transposed with zero rows on
+// the overridden columns, its bias with the overrides folded in, the later layers), the layer-0 product of one thread per row from a
+// weight image staged in LDS (pdp_layer0), the later layers from LDS broadcasts (pdp_dense), the prediction from layer 0's
+// pre-activation (pdp_forward).  Route 2 of saliency and Shapley: the same blocks behind one runtime-width network (PlainNet,
+// plain_later_layers).  Both: the output function (out_function), the plan (plan_route over npbnn_attrib_plan.h) and the entries' host
+// steps (upload_sets, Route1Kernel).  The device routines here are inlined into the kernels of the unit that includes this header;
+// the preparation kernel and prepare_route1 live in npbnn_pdp.hip alone.  Not part of the ABI.
 #pragma once
+#include "npbnn_attrib_plan.h"
 #include "npbnn_sets.hip.h"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 namespace npbnn_api {
-
-namespace {
-
-constexpr int kPdpRows = 256;                    // rows of a workgroup of pdp_kernel (one per thread)
-constexpr int kPdpTail = 32;                     // widest later layer (and output) route 1 takes
-constexpr int kPdpMaxH0 = 64;                    // widest first layer route 1 takes
-constexpr size_t kPdpW0Lds = 64 * 1024;          // LDS bytes for one set's first-layer weights (Fp x H0P floats)
-constexpr size_t kPdpTailLds = 32 * 1024;        // LDS bytes for the later layers of the sets of one launch
 
 struct PdpParams {
     const float* X;
@@ -35,10 +31,16 @@ struct PdpParams {
     float* acc;            // [n_g][n_rows][C]
 };
 
-struct PdpPrep {
-    int F, Fp, H0, H0P, hb0, n_layers, n_grid, wn, tail_floats;
-    int l_in[kMaxLayers], l_out[kMaxLayers], l_hb[kMaxLayers], l_woff[kMaxLayers], t_inp[kMaxLayers], t_off[kMaxLayers];
+struct Route1Blocks {
+    DevBuf<float> w0t, bias, tail, slopes;
 };
+
+// Route 1's float32 blocks of every set (a preparation kernel, enqueued on ctx->stream) and the kernel parameters that do not change
+// from launch to launch; d_w [n_sets][n_weights], d_co [n_points][F] on the device.  (npbnn_pdp.hip)
+int prepare_route1(npbnn_ctx* ctx, const npbnn_attrib_route& r, const FeatureTable& m, const double* d_w, const double* d_co,
+                   const double* act_prm_sets, int n_sets, int apply_out_fn, Route1Blocks* b, PdpParams* out);
+
+namespace {
 
 template <int KIND, int N>
 __device__ __forceinline__ void pdp_act_k(float (&h)[N], float prm) {
@@ -80,6 +82,37 @@ __device__ __forceinline__ void pdp_dense(const float (&in)[IN], float (&out)[OU
     }
 }
 
+// f(c) for the outputs c < C.  N > 0: the values are registers, so the loop runs to N unrolled and c is a constant in every copy.
+template <int N, class F>
+__device__ __forceinline__ void each_output(int C, F f) {
+    if constexpr (N > 0) {
+#pragma unroll
+        for (int c = 0; c < N; ++c)
+            if (c < C) f(c);
+    } else {
+        for (int c = 0; c < C; ++c) f(c);
+    }
+}
+
+// v(c), c < C, in place: the softmax probabilities (SoftMax, BNN_lib.py:166-168)
+template <int N, class V>
+__device__ __forceinline__ void out_softmax(int C, V v) {
+    float m = -3.402823466e38f;
+    each_output<N>(C, [&](int c) { m = fmaxf(m, v(c)); });
+    float s = 0.f;
+    each_output<N>(C, [&](int c) { v(c) = __expf(v(c) - m); s += v(c); });
+    const float r = 1.f / s;
+    each_output<N>(C, [&](int c) { v(c) *= r; });
+}
+
+// the output function on v(c), c < C, in place: softmax, or softplus on the second half (RegressTransformError, BNN_lib.py:177-182)
+template <int N, class V>
+__device__ __forceinline__ void out_function(int out_kind, int C, V v) {
+    if (out_kind == NPBNN_OUT_SOFTMAX) out_softmax<N>(C, v);
+    else if (out_kind == NPBNN_OUT_SOFTPLUS_HALF)
+        each_output<N>(C, [&](int c) { if (c >= C / 2) v(c) = softplus_f(v(c)); });
+}
+
 // layer 0's pre-activation h (bias and grid shift included) -> the prediction y (first C entries; output function when asked)
 template <int H0P>
 __device__ __forceinline__ void pdp_forward(const PdpParams& p, float (&h)[H0P], const float* w, const float* sl, float (&y)[kPdpTail]) {
@@ -102,7 +135,9 @@ __device__ __forceinline__ void pdp_forward(const PdpParams& p, float (&h)[H0P],
         if (p.final_act) pdp_act(y, p.act_kind, sl[L - 1]);
     }
     if (!p.apply_out) return;
-    if (p.out_kind == NPBNN_OUT_SOFTMAX) {           // SoftMax (BNN_lib.py:166-168)
+    // out_function's arithmetic on the registers, spelled out: through out_function the compiler allots the walk kernels' registers
+    // differently (shap_walk_kernel<32> 215 -> 201 VGPRs) and npbnn_predict_shapley's route 1 takes 7.6 % longer (NOTES 8.15)
+    if (p.out_kind == NPBNN_OUT_SOFTMAX) {
         float m = -3.402823466e38f;
 #pragma unroll
         for (int c = 0; c < kPdpTail; ++c)
@@ -114,7 +149,7 @@ __device__ __forceinline__ void pdp_forward(const PdpParams& p, float (&h)[H0P],
         const float r = 1.f / s;
 #pragma unroll
         for (int c = 0; c < kPdpTail; ++c) y[c] *= r;
-    } else if (p.out_kind == NPBNN_OUT_SOFTPLUS_HALF) {   // RegressTransformError (BNN_lib.py:177-182)
+    } else if (p.out_kind == NPBNN_OUT_SOFTPLUS_HALF) {
 #pragma unroll
         for (int c = 0; c < kPdpTail; ++c)
             if (c < p.C && c >= p.C / 2) y[c] = softplus_f(y[c]);
@@ -160,50 +195,6 @@ __device__ __forceinline__ void pdp_layer0(const PdpParams& p, float (&z0)[NS][H
     }
 }
 
-// grid (n_sets), block 256: a set's float64 weights -> route 1's float32 blocks.  co_all [n_grid][F]: per grid point the constant of
-// every overridden column (NaN = the data); the overridden columns are the same for every grid point.
-__global__ __launch_bounds__(256) void pdp_prep_kernel(const PdpPrep q, const double* W, const double* co_all, float* w0t, float* bias,
-                                                       float* tail) {
-    const int s = blockIdx.x;
-    const double* w = W + (size_t)s * q.wn;
-    const int in0 = q.F + q.hb0;
-    float* dw = w0t + (size_t)s * q.Fp * q.H0P;
-    for (int i = threadIdx.x; i < q.Fp * q.H0P; i += blockDim.x) {
-        const int f = i / q.H0P, h = i % q.H0P;
-        float v = 0.f;
-        if (f < q.F && h < q.H0 && __builtin_isnan(co_all[f])) v = (float)w[(size_t)h * in0 + q.hb0 + f];
-        dw[i] = v;
-    }
-    float* db = bias + (size_t)s * q.n_grid * q.H0P;
-    for (int i = threadIdx.x; i < q.n_grid * q.H0P; i += blockDim.x) {
-        const int g = i / q.H0P, h = i % q.H0P;
-        double a = 0.0;
-        if (h < q.H0) {
-            const double* wr = w + (size_t)h * in0;
-            const double* co = co_all + (size_t)g * q.F;
-            if (q.hb0) a = wr[0];
-            for (int f = 0; f < q.F; ++f)
-                if (!__builtin_isnan(co[f])) a += co[f] * wr[q.hb0 + f];
-        }
-        db[i] = (float)a;
-    }
-    float* dt = tail + (size_t)s * q.tail_floats;
-    for (int l = 1; l < q.n_layers; ++l) {
-        const int n_out = q.l_out[l], inp = q.t_inp[l], hb = q.l_hb[l], stride = q.l_in[l] + hb, r4 = (n_out + 3) & ~3;
-        const double* wl = w + q.l_woff[l];
-        for (int i = threadIdx.x; i < r4 + n_out * inp; i += blockDim.x) {
-            float v = 0.f;
-            if (i < r4) {
-                if (i < n_out && hb) v = (float)wl[(size_t)i * stride];
-            } else {
-                const int j = i - r4, o = j / inp, k = j % inp;
-                if (k < q.l_in[l]) v = (float)wl[(size_t)o * stride + hb + k];
-            }
-            dt[q.t_off[l] + i] = v;
-        }
-    }
-}
-
 bool env_on(const char* name) {
     const char* e = getenv(name);
     return e && *e && strcmp(e, "0") != 0;
@@ -214,72 +205,120 @@ size_t env_bytes(const char* name, size_t otherwise) {
     return otherwise;
 }
 
-// Route 1's shapes for a network and n_points shifted biases (grid points, or bin edges), and whether the network is inside its
-// envelope (include/npbnn_hip.h); `off`: the environment variable that forces route 2.
-struct Route1Plan {
-    PdpPrep q{};
-    int H0P = 32, NS = 2;
-    bool fits = false;
-};
-
-Route1Plan plan_route1(const npbnn_ctx* ctx, int Fp, int n_points, const char* off) {
-    Route1Plan r;
-    const int F = ctx->arch.in_dim, L = ctx->net.n_layers, H0 = ctx->arch.out_dim[0];
-    r.H0P = H0 <= 32 ? 32 : 64;
-    r.NS = 64 / r.H0P;
-    r.fits = !ctx->wide && !env_on(off) && H0 <= kPdpMaxH0 && (size_t)Fp * r.H0P * 4 <= kPdpW0Lds;
-    PdpPrep& q = r.q;
-    q.F = F; q.Fp = Fp; q.H0 = H0; q.H0P = r.H0P; q.hb0 = ctx->arch.has_bias[0]; q.n_layers = L; q.n_grid = n_points; q.wn = ctx->n_weights;
-    int woff = H0 * (F + q.hb0), toff = 0;
-    for (int l = 1; l < L; ++l) {
-        q.l_in[l] = ctx->arch.out_dim[l - 1];
-        q.l_out[l] = ctx->arch.out_dim[l];
-        q.l_hb[l] = ctx->arch.has_bias[l];
-        q.l_woff[l] = woff;
-        woff += q.l_out[l] * (q.l_in[l] + q.l_hb[l]);
-        q.t_inp[l] = round_up(q.l_in[l], 8);
-        q.t_off[l] = toff;
-        toff += round_up(q.l_out[l], 4) + q.l_out[l] * q.t_inp[l];
-        if (q.l_out[l] > kPdpTail) r.fits = false;
-    }
-    q.tail_floats = toff;
-    if (L == 1 && ctx->net.n_out > kPdpTail) r.fits = false;
-    if ((size_t)r.NS * q.tail_floats * 4 > kPdpTailLds) r.fits = false;
+// The route and route 1's shapes for the context's network and n_points shifted biases (grid points, bin edges, or 1);
+// `off`: the entry's environment variable that forces route 2.
+npbnn_attrib_route plan_route(const npbnn_ctx* ctx, int entry, int Fp, int n_points, const char* off) {
+    const npbnn_attrib_route_req req = {&ctx->arch, ctx->n_weights, Fp, n_points, ctx->wide ? 1 : 0, env_on(off) ? 1 : 0, entry};
+    npbnn_attrib_route r{};
+    npbnn_attrib_route_of(&req, &r);
     return r;
 }
 
-struct Route1Blocks {
-    DevBuf<float> w0t, bias, tail, slopes;
+// per point, every column's constant: col_override's where it has one (it applies after the point's values), else the point's value
+// on a focal column, else NaN
+std::vector<double> point_constants(int F, const double* col_override, const int32_t* focal, int n_focal, const double* values, int n_points) {
+    std::vector<double> co_all((size_t)n_points * F);
+    for (int g = 0; g < n_points; ++g) {
+        double* co = co_all.data() + (size_t)g * F;
+        for (int f = 0; f < F; ++f) co[f] = col_override ? col_override[f] : NAN;
+        for (int k = 0; k < n_focal; ++k)
+            if (std::isnan(col_override ? col_override[focal[k]] : NAN)) co[focal[k]] = values[(size_t)g * n_focal + k];
+    }
+    return co_all;
+}
+
+// The sets' float64 weights and the points' constants on the device, enqueued on ctx->stream (co_all outlives the copy: the entries
+// end with a wait for the stream).
+int upload_sets(npbnn_ctx* ctx, const double* W_sets, int n_sets, const std::vector<double>& co_all, DevBuf<double>& d_w, DevBuf<double>& d_co) {
+    const size_t n_w = (size_t)n_sets * ctx->n_weights;
+    int rc;
+    if ((rc = dev_alloc(ctx, d_w, n_w))) return rc;
+    if ((rc = dev_alloc(ctx, d_co, co_all.size()))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(d_w.get(), W_sets, n_w * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_co.get(), co_all.data(), co_all.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    return NPBNN_OK;
+}
+
+// A route-1 kernel at the plan's H0P: the <32, ...> or the <64, ...> instantiation with its dynamic LDS, allowed once, then launched
+// by blocks of 256 threads.
+template <class... A>
+struct Route1Kernel {
+    void (*fn)(A...) = nullptr;
+    size_t lds = 0;
+    int pick(npbnn_ctx* ctx, int H0P, void (*k32)(A...), void (*k64)(A...), long long lds_bytes) {
+        fn = H0P == 32 ? k32 : k64;
+        lds = (size_t)lds_bytes;
+        if (lds) HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        return NPBNN_OK;
+    }
+    void launch(dim3 grid, hipStream_t st, A... args) const { hipLaunchKernelGGL(fn, grid, dim3(256), lds, st, args...); }
 };
 
-// Route 1's float32 blocks of every set (pdp_prep_kernel, enqueued on ctx->stream) and the kernel parameters that do not change from
-// launch to launch; d_w [n_sets][n_weights], d_co [n_points][F] on the device.
-int prepare_route1(npbnn_ctx* ctx, const Route1Plan& r, const FeatureTable& m, const double* d_w, const double* d_co, const double* act_prm_sets,
-                   int n_sets, int apply_out_fn, Route1Blocks* b, PdpParams* out) {
-    const PdpPrep& q = r.q;
-    const int L = q.n_layers, n_act = L - 1;
-    int rc;
-    if ((rc = dev_alloc(ctx, b->w0t, (size_t)n_sets * q.Fp * q.H0P))) return rc;
-    if ((rc = dev_alloc(ctx, b->bias, (size_t)n_sets * q.n_grid * q.H0P))) return rc;
-    if ((rc = dev_alloc(ctx, b->tail, (size_t)n_sets * q.tail_floats))) return rc;
-    if ((rc = dev_alloc(ctx, b->slopes, (size_t)n_sets * kMaxLayers))) return rc;
-    std::vector<float> slopes((size_t)n_sets * kMaxLayers, 0.f);
-    if (act_prm_sets)
-        for (int s = 0; s < n_sets; ++s)
-            for (int l = 0; l < n_act; ++l) slopes[(size_t)s * kMaxLayers + l] = (float)act_prm_sets[(size_t)s * n_act + l];
-    // (pageable memory: the copy has left `slopes` when the call returns)
-    HIP_TRY(ctx, hipMemcpyAsync(b->slopes.get(), slopes.data(), slopes.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(pdp_prep_kernel, dim3(n_sets), dim3(256), 0, ctx->stream, q, d_w, d_co, b->w0t.get(), b->bias.get(), b->tail.get());
-    HIP_TRY(ctx, hipGetLastError());
-    PdpParams p{};
-    p.X = m.X; p.n_rows = m.n_rows; p.Fp = q.Fp;
-    p.w0t = b->w0t.get(); p.bias = b->bias.get(); p.tail = b->tail.get(); p.slopes = b->slopes.get();
-    p.n_grid = q.n_grid; p.tail_floats = q.tail_floats;
-    p.n_layers = L; p.act_kind = ctx->arch.act_kind; p.final_act = ctx->arch.final_act; p.out_kind = ctx->arch.out_kind;
-    p.apply_out = apply_out_fn ? 1 : 0; p.C = ctx->net.n_out;
-    for (int l = 1; l < L; ++l) { p.t_out[l] = q.l_out[l]; p.t_inp[l] = q.t_inp[l]; p.t_off[l] = q.t_off[l]; }
-    *out = p;
-    return NPBNN_OK;
+// ---- route 2 of saliency and Shapley: one network at run-time widths behind route 1's float32 blocks
+
+struct PlainNet {
+    const float* w0t;      // [prepared set][Fp][H0P], bias [.][H0P], later layers [.][tail_floats], slopes [.][kMaxLayers]
+    const float* bias;
+    const float* tail;
+    const float* slopes;
+    int Fp, H0P, tail_floats;
+    int n_layers, act_kind, final_act, out_kind, apply_out, C, max_w;
+    int width[kMaxLayers], t_inp[kMaxLayers], t_off[kMaxLayers];
+};
+
+PlainNet plain_net(const PdpParams& p, const npbnn_attrib_route& r) {
+    PlainNet n{};
+    n.w0t = p.w0t; n.bias = p.bias; n.tail = p.tail; n.slopes = p.slopes; n.Fp = p.Fp; n.H0P = r.H0P; n.tail_floats = p.tail_floats;
+    n.n_layers = p.n_layers; n.act_kind = p.act_kind; n.final_act = p.final_act; n.out_kind = p.out_kind; n.apply_out = p.apply_out;
+    n.C = p.C; n.max_w = r.max_w;
+    for (int l = 0; l < p.n_layers; ++l) { n.width[l] = l ? r.q.l_out[l] : r.q.H0; n.t_inp[l] = p.t_inp[l]; n.t_off[l] = p.t_off[l]; }
+    return n;
+}
+
+// a'(z) on the branch act_apply takes
+template <int KIND>
+__device__ __forceinline__ float dact_k(float z, float prm) {
+    if (KIND == NPBNN_ACT_RELU) return z > 0.f ? 1.f : 0.f;
+    if (KIND == NPBNN_ACT_LEAKY) return z < 0.f ? prm : 1.f;
+    if (KIND == NPBNN_ACT_SWISH) {
+        const float s = __builtin_amdgcn_rcpf(1.f + __expf(-z));
+        return s * (1.f + z * (1.f - s));
+    }
+    const float t = act_apply(z, NPBNN_ACT_TANH, prm);
+    return 1.f - t * t;
+}
+
+__device__ __forceinline__ float dact(float z, int kind, float prm) {
+    switch (kind) {
+        case NPBNN_ACT_RELU: return dact_k<NPBNN_ACT_RELU>(z, prm);
+        case NPBNN_ACT_LEAKY: return dact_k<NPBNN_ACT_LEAKY>(z, prm);
+        case NPBNN_ACT_SWISH: return dact_k<NPBNN_ACT_SWISH>(z, prm);
+        default: return dact_k<NPBNN_ACT_TANH>(z, prm);
+    }
+}
+
+// The later layers of one thread's row.  A value sits `stride` floats from the next unit's; layer l's units start at unit at(l) of
+// val, layer 0's hold its values after the activation.  der (or nullptr), laid out like val: a'(z), 1 where the layer has no
+// activation.  Bias first, inputs ascending; the weights are read at wave-uniform addresses.
+template <class At>
+__device__ __forceinline__ void plain_later_layers(const PlainNet& n, const float* tail, const float* sl, float* val, float* der, size_t stride, At at) {
+    const int L = n.n_layers, kind = n.act_kind;
+    for (int l = 1; l < L; ++l) {
+        const int n_in = n.width[l - 1], n_out = n.width[l], inp = n.t_inp[l];
+        const float* wb = tail + n.t_off[l];
+        const float* wm = wb + ((n_out + 3) & ~3);
+        const float* in = val + (size_t)at(l - 1) * stride;
+        const size_t out = (size_t)at(l) * stride;
+        const bool has_act = l < L - 1 || n.final_act;
+        const float prm = sl[l];
+        for (int o = 0; o < n_out; ++o) {
+            float z = wb[o];
+            const float* wr = wm + (size_t)o * inp;
+            for (int i = 0; i < n_in; ++i) z = fmaf(in[(size_t)i * stride], wr[i], z);
+            val[out + (size_t)o * stride] = has_act ? act_apply(z, kind, prm) : z;
+            if (der) der[out + (size_t)o * stride] = has_act ? dact(z, kind, prm) : 1.f;
+        }
+    }
 }
 
 }  // namespace

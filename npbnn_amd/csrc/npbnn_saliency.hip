@@ -26,39 +26,17 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kSalWaveRows = 256;                // rows a wave of sal_fold_kernel folds: eight tiles of 32
 constexpr int kSalNB = 4;                        // feature tiles of 32 a wave of sal_fold_kernel carries
 constexpr size_t kSalScratchBytes = 128ull << 20;   // device budget of D, the partials and phase 1's scratches: a larger table runs in
                                                     // chunks of rows (and, on route 2, a wide output layer in chunks of outputs)
 constexpr size_t kSalPrepBytes = 256ull << 20;   // device budget of the float32 blocks: more sets are prepared group after group
-
-// a'(z) on the branch act_apply takes
-template <int KIND>
-__device__ __forceinline__ float sal_dact_k(float z, float prm) {
-    if (KIND == NPBNN_ACT_RELU) return z > 0.f ? 1.f : 0.f;
-    if (KIND == NPBNN_ACT_LEAKY) return z < 0.f ? prm : 1.f;
-    if (KIND == NPBNN_ACT_SWISH) {
-        const float s = __builtin_amdgcn_rcpf(1.f + __expf(-z));
-        return s * (1.f + z * (1.f - s));
-    }
-    const float t = act_apply(z, NPBNN_ACT_TANH, prm);
-    return 1.f - t * t;
-}
-
-__device__ __forceinline__ float sal_dact(float z, int kind, float prm) {
-    switch (kind) {
-        case NPBNN_ACT_RELU: return sal_dact_k<NPBNN_ACT_RELU>(z, prm);
-        case NPBNN_ACT_LEAKY: return sal_dact_k<NPBNN_ACT_LEAKY>(z, prm);
-        case NPBNN_ACT_SWISH: return sal_dact_k<NPBNN_ACT_SWISH>(z, prm);
-        default: return sal_dact_k<NPBNN_ACT_TANH>(z, prm);
-    }
-}
+// (NPBNN_SALIENCY_SCRATCH_BYTES and NPBNN_SALIENCY_PREP_BYTES override them; the cut itself is npbnn_attrib_sal_of's)
 
 template <int KIND, int N>
 __device__ __forceinline__ void sal_act_d_k(float (&h)[N], float (&d)[N], float prm) {
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        d[i] = sal_dact_k<KIND>(h[i], prm);
+        d[i] = dact_k<KIND>(h[i], prm);
         h[i] = act_apply(h[i], KIND, prm);
     }
 }
@@ -149,19 +127,7 @@ __device__ __forceinline__ void sal_sets(const PdpParams& p, const SalParams& a,
             // the output side, in place: softmax - the probabilities; softplus-half - the factor sigma(z) (1 on the first half); else 1
             const int out_kind = p.apply_out ? p.out_kind : NPBNN_OUT_IDENTITY;
             if (out_kind == NPBNN_OUT_SOFTMAX) {
-                float m = -3.402823466e38f;
-#pragma unroll
-                for (int c = 0; c < kPdpTail; ++c)
-                    if (c < C) m = fmaxf(m, y[c]);
-                float s = 0.f;
-#pragma unroll
-                for (int c = 0; c < kPdpTail; ++c) {
-                    y[c] = c < C ? __expf(y[c] - m) : 0.f;
-                    s += y[c];
-                }
-                const float rs = 1.f / s;
-#pragma unroll
-                for (int c = 0; c < kPdpTail; ++c) y[c] *= rs;
+                out_softmax<kPdpTail>(C, [&](int c) -> float& { return y[c]; });
             } else {
 #pragma unroll
                 for (int c = 0; c < kPdpTail; ++c) y[c] = (out_kind == NPBNN_OUT_SOFTPLUS_HALF && c >= C / 2) ? sal_sigmoid(y[c]) : 1.f;
@@ -226,14 +192,10 @@ __global__ __launch_bounds__(kPdpRows) void sal_route1_kernel(const PdpParams p,
 struct SalPlain {
     const float* X;
     long long n_rows, row0;
-    int rows_cap, Fp;
-    const float* w0t;      // [Fp][H0P] of the launch's set, and its bias [H0P], later layers and slopes [kMaxLayers]
-    const float* bias;
-    const float* tail;
-    const float* slopes;
-    int n_layers, act_kind, final_act, out_kind, apply_out, C, H0P, max_w;
+    int rows_cap;
+    int set0;              // the launch's set among the prepared ones
     int c0, n_c;           // the outputs of this launch; the forward pass runs with c0 == 0 and stays in the scratches
-    int width[kMaxLayers], t_inp[kMaxLayers], t_off[kMaxLayers], a_off[kMaxLayers];
+    int a_off[kMaxLayers];
     float* act;            // [a_off[l] + unit][rows_cap]: a layer's values after its activation (the last layer's: the output side)
     float* fac;            // likewise: a'(z), 1 where the layer has no activation
     float* g;              // [2][max_w][rows_cap]: the gradient at two neighbouring layers
@@ -242,27 +204,31 @@ struct SalPlain {
 
 // grid (ceil(rows of the chunk / 256)), block 256: one thread per row, every width at run time; the weights are read at wave-uniform
 // addresses, the scratches at consecutive ones.
-__global__ __launch_bounds__(256) void sal_plain_kernel(const SalPlain p) {
+__global__ __launch_bounds__(256) void sal_plain_kernel(const PlainNet p, const SalPlain a) {
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long row = p.row0 + r;
-    if (r >= p.rows_cap || row >= p.n_rows) return;
-    const size_t R = (size_t)p.rows_cap;
+    const long long row = a.row0 + r;
+    if (r >= a.rows_cap || row >= a.n_rows) return;
+    const size_t R = (size_t)a.rows_cap;
     const int L = p.n_layers, C = p.C, kind = p.act_kind;
-    float* act = p.act + r;
-    float* fac = p.fac + r;
-    float* y = act + (size_t)p.a_off[L - 1] * R;
+    const float* tail = p.tail + (size_t)a.set0 * p.tail_floats;
+    float* act = a.act + r;
+    float* fac = a.fac + r;
+    float* y = act + (size_t)a.a_off[L - 1] * R;
     const int out_kind = p.apply_out ? p.out_kind : NPBNN_OUT_IDENTITY;
-    if (p.c0 == 0) {
-        const float4* xr = reinterpret_cast<const float4*>(p.X + row * p.Fp);
+    if (a.c0 == 0) {
+        const float4* xr = reinterpret_cast<const float4*>(a.X + row * p.Fp);
+        const float* w0t = p.w0t + (size_t)a.set0 * p.Fp * p.H0P;
+        const float* bias = p.bias + (size_t)a.set0 * p.H0P;
+        const float* sl = p.slopes + (size_t)a.set0 * kMaxLayers;
         const bool act0 = L > 1 || p.final_act;
         const int H0 = p.width[0];
         for (int h0 = 0; h0 < H0; h0 += 8) {
             float z[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) z[e] = p.bias[h0 + e];
+            for (int e = 0; e < 8; ++e) z[e] = bias[h0 + e];
             for (int f4 = 0; f4 < p.Fp / 4; ++f4) {
                 const float4 x = xr[f4];
-                const float* w = p.w0t + (size_t)f4 * 4 * p.H0P + h0;
+                const float* w = w0t + (size_t)f4 * 4 * p.H0P + h0;
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
                     z[e] = fmaf(x.w, w[3 * p.H0P + e], fmaf(x.z, w[2 * p.H0P + e], fmaf(x.y, w[p.H0P + e], fmaf(x.x, w[e], z[e]))));
@@ -270,44 +236,21 @@ __global__ __launch_bounds__(256) void sal_plain_kernel(const SalPlain p) {
 #pragma unroll
             for (int e = 0; e < 8; ++e)
                 if (h0 + e < H0) {
-                    act[(size_t)(h0 + e) * R] = act0 ? act_apply(z[e], kind, p.slopes[0]) : z[e];
-                    fac[(size_t)(h0 + e) * R] = act0 ? sal_dact(z[e], kind, p.slopes[0]) : 1.f;
+                    act[(size_t)(h0 + e) * R] = act0 ? act_apply(z[e], kind, sl[0]) : z[e];
+                    fac[(size_t)(h0 + e) * R] = act0 ? dact(z[e], kind, sl[0]) : 1.f;
                 }
         }
-        for (int l = 1; l < L; ++l) {
-            const int n_in = p.width[l - 1], n_out = p.width[l], inp = p.t_inp[l];
-            const float* wb = p.tail + p.t_off[l];
-            const float* wm = wb + ((n_out + 3) & ~3);
-            const float* in = act + (size_t)p.a_off[l - 1] * R;
-            const bool has_act = l < L - 1 || p.final_act;
-            const float prm = p.slopes[l];
-            for (int o = 0; o < n_out; ++o) {
-                float z = wb[o];
-                const float* wr = wm + (size_t)o * inp;
-                for (int i = 0; i < n_in; ++i) z = fmaf(in[(size_t)i * R], wr[i], z);
-                act[(size_t)(p.a_off[l] + o) * R] = has_act ? act_apply(z, kind, prm) : z;
-                fac[(size_t)(p.a_off[l] + o) * R] = has_act ? sal_dact(z, kind, prm) : 1.f;
-            }
-        }
+        plain_later_layers(p, tail, sl, act, fac, R, [&](int l) { return a.a_off[l]; });
         // the output side, in place: softmax - the probabilities; softplus-half - the factor sigma(z) (1 on the first half); else 1
         if (out_kind == NPBNN_OUT_SOFTMAX) {
-            float m = -3.402823466e38f;
-            for (int k = 0; k < C; ++k) m = fmaxf(m, y[(size_t)k * R]);
-            float s = 0.f;
-            for (int k = 0; k < C; ++k) {
-                const float e = __expf(y[(size_t)k * R] - m);
-                y[(size_t)k * R] = e;
-                s += e;
-            }
-            const float rs = 1.f / s;
-            for (int k = 0; k < C; ++k) y[(size_t)k * R] *= rs;
+            out_softmax<0>(C, [&](int c) -> float& { return y[(size_t)c * R]; });
         } else {
-            for (int k = 0; k < C; ++k) y[(size_t)k * R] = (out_kind == NPBNN_OUT_SOFTPLUS_HALF && k >= C / 2) ? sal_sigmoid(y[(size_t)k * R]) : 1.f;
+            for (int c = 0; c < C; ++c) y[(size_t)c * R] = (out_kind == NPBNN_OUT_SOFTPLUS_HALF && c >= C / 2) ? sal_sigmoid(y[(size_t)c * R]) : 1.f;
         }
     }
-    const float* f_last = fac + (size_t)p.a_off[L - 1] * R;
-    for (int c = p.c0; c < p.c0 + p.n_c; ++c) {
-        float* g = p.g + r;
+    const float* f_last = fac + (size_t)a.a_off[L - 1] * R;
+    for (int c = a.c0; c < a.c0 + a.n_c; ++c) {
+        float* g = a.g + r;
         float* gn = g + (size_t)p.max_w * R;
         const float yc = y[(size_t)c * R];
         for (int k = 0; k < C; ++k) {
@@ -316,8 +259,8 @@ __global__ __launch_bounds__(256) void sal_plain_kernel(const SalPlain p) {
         }
         for (int l = L - 1; l >= 1; --l) {
             const int n_in = p.width[l - 1], n_out = p.width[l], inp = p.t_inp[l];
-            const float* wm = p.tail + p.t_off[l] + ((n_out + 3) & ~3);
-            const float* fp = fac + (size_t)p.a_off[l - 1] * R;
+            const float* wm = tail + p.t_off[l] + ((n_out + 3) & ~3);
+            const float* fp = fac + (size_t)a.a_off[l - 1] * R;
             for (int i = 0; i < n_in; ++i) {
                 float s = 0.f;
                 for (int o = 0; o < n_out; ++o) s = fmaf(wm[(size_t)o * inp + i], g[(size_t)o * R], s);
@@ -325,7 +268,7 @@ __global__ __launch_bounds__(256) void sal_plain_kernel(const SalPlain p) {
             }
             float* t = g; g = gn; gn = t;
         }
-        float* d = p.D + ((size_t)(c - p.c0) * R + r) * p.H0P;
+        float* d = a.D + ((size_t)(c - a.c0) * R + r) * p.H0P;
         for (int h = 0; h < p.H0P; ++h) d[h] = h < p.width[0] ? g[(size_t)h * R] : 0.f;
     }
 }
@@ -487,71 +430,39 @@ extern "C" int npbnn_predict_saliency(npbnn_ctx* ctx, const double* W_sets, cons
     Dataset& d = *tb.d;
     const long long n_rows = tb.n_rows;
     if (n_rows < 1) return fail(ctx, NPBNN_E_ARG, "predict_saliency: the table has no rows");
-    const int F = ctx->arch.in_dim, C = ctx->net.n_out, L = ctx->net.n_layers, n_act = L - 1, Fp = d.m->Fp, Fq = round_up(F, 32);
+    const int F = ctx->arch.in_dim, C = ctx->net.n_out, n_act = ctx->net.n_layers - 1, Fp = d.m->Fp;
     const size_t wn = (size_t)ctx->n_weights, n_res = (size_t)n_sets * C * F;
     hipStream_t st = ctx->stream;
 
-    // ---- the route and its shapes
-    Route1Plan r1 = plan_route1(ctx, Fp, 1, "NPBNN_SALIENCY_PLAIN");
-    const int route = r1.fits ? 1 : 2;
-    if (route == 2) {
-        r1.H0P = round_up(ctx->arch.out_dim[0], 32);
-        r1.q.H0P = r1.H0P;
-        r1.NS = 1;
-    }
-    const int H0P = r1.H0P, NS = r1.NS;
-    int sum_w = 0, max_w = 0;
-    for (int l = 0; l < L; ++l) {
-        sum_w += ctx->arch.out_dim[l];
-        max_w = std::max(max_w, ctx->arch.out_dim[l]);
-    }
-    // Scratch bytes per row of a chunk: what does not depend on the outputs of a launch (route 1: the later layers' factors; route 2:
-    // activations, factors and two gradients), and per (set, output) of a launch D's H0P floats and the row's share of a wave's partials
-    const size_t budget = env_bytes("NPBNN_SALIENCY_SCRATCH_BYTES", kSalScratchBytes);
-    const size_t row_fixed = route == 1 ? (size_t)L * kPdpTail * sizeof(float) : (size_t)(2 * sum_w + 2 * max_w) * sizeof(float);
-    const size_t row_pair = (size_t)H0P * sizeof(float) + (3 * (size_t)Fq * sizeof(double) + kSalWaveRows - 1) / kSalWaveRows;
-    const long long rows_all = (n_rows + kSalWaveRows - 1) / kSalWaveRows * kSalWaveRows;
-    int n_c = C;                                       // outputs of a launch
-    long long rows_cap = (long long)(budget / (row_fixed + (size_t)NS * C * row_pair)) / kSalWaveRows * kSalWaveRows;
-    if (rows_cap < kSalWaveRows) {
-        rows_cap = kSalWaveRows;
-        if (route == 2) {                              // (route 1's pairs of a launch are 64 at most: they stay together)
-            const size_t per_row = budget / kSalWaveRows;
-            n_c = (int)std::max<size_t>(1, std::min<size_t>((size_t)C, per_row > row_fixed ? (per_row - row_fixed) / row_pair : 0));
-        }
-    }
-    rows_cap = std::min<long long>(std::min(rows_cap, rows_all), 1ll << 24);      // (a chunk's row indices are ints)
-    const int n_slot_cap = (int)(rows_cap / kSalWaveRows);
-    const size_t pairs_cap = (size_t)NS * n_c;
+    // ---- the route, the cut of the job and the buffers it needs (npbnn_attrib_plan.h)
+    const npbnn_attrib_route r1 = plan_route(ctx, NPBNN_ATTRIB_SALIENCY, Fp, 1, "NPBNN_SALIENCY_PLAIN");
+    const npbnn_attrib_sal_req req = {&r1, C, F, n_rows, n_sets, (long long)env_bytes("NPBNN_SALIENCY_SCRATCH_BYTES", kSalScratchBytes),
+                                      (long long)env_bytes("NPBNN_SALIENCY_PREP_BYTES", kSalPrepBytes)};
+    npbnn_attrib_sal cut;
+    npbnn_attrib_sal_of(&req, &cut);
+    const int route = r1.route, H0P = r1.H0P, NS = r1.NS, Fq = cut.Fq, n_c = cut.n_c, rows_cap = cut.rows_cap, prep_sets = cut.prep_sets;
 
-    const size_t set_floats = (size_t)Fp * H0P + H0P + r1.q.tail_floats + kMaxLayers;
-    const int prep_sets = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sets, kSalPrepBytes / (set_floats * sizeof(float))));
-
-    std::vector<double> co((size_t)F);
-    for (int f = 0; f < F; ++f) co[f] = col_override ? col_override[f] : NAN;
     DevBuf<double> d_w, d_co, d_acc, d_part;
     DevBuf<float> d_D, d_fac, d_act, d_g;
-    if ((rc = dev_alloc(ctx, d_w, (size_t)n_sets * wn))) return rc;
-    if ((rc = dev_alloc(ctx, d_co, co.size()))) return rc;
+    const std::vector<double> co = point_constants(F, col_override, nullptr, 0, nullptr, 1);
+    if ((rc = upload_sets(ctx, W_sets, n_sets, co, d_w, d_co))) return rc;
     if ((rc = dev_alloc(ctx, d_acc, 3 * n_res))) return rc;
-    if ((rc = dev_alloc(ctx, d_D, pairs_cap * rows_cap * H0P))) return rc;
-    if ((rc = dev_alloc(ctx, d_part, pairs_cap * n_slot_cap * 3 * Fq))) return rc;
-    if (route == 1) {
-        if ((rc = dev_alloc(ctx, d_fac, (size_t)rows_cap * L * kPdpTail))) return rc;
-    } else {
-        if ((rc = dev_alloc(ctx, d_fac, (size_t)rows_cap * sum_w))) return rc;
-        if ((rc = dev_alloc(ctx, d_act, (size_t)rows_cap * sum_w))) return rc;
-        if ((rc = dev_alloc(ctx, d_g, (size_t)rows_cap * 2 * max_w))) return rc;
+    if ((rc = dev_alloc(ctx, d_D, (size_t)cut.n_D))) return rc;
+    if ((rc = dev_alloc(ctx, d_part, (size_t)cut.n_part))) return rc;
+    if ((rc = dev_alloc(ctx, d_fac, (size_t)cut.n_fac))) return rc;
+    if (route == 2) {
+        if ((rc = dev_alloc(ctx, d_act, (size_t)cut.n_act))) return rc;
+        if ((rc = dev_alloc(ctx, d_g, (size_t)cut.n_g))) return rc;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(d_w.get(), W_sets, (size_t)n_sets * wn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_co.get(), co.data(), co.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetAsync(d_acc.get(), 0, 3 * n_res * sizeof(double), st));
 
-    const size_t lds = ((size_t)Fp * H0P + (size_t)NS * r1.q.tail_floats) * sizeof(float);
-    if (route == 1) {
-        const void* fn = H0P == 32 ? reinterpret_cast<const void*>(sal_route1_kernel<32, 2>) : reinterpret_cast<const void*>(sal_route1_kernel<64, 1>);
-        HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    Route1Kernel<PdpParams, SalParams> kern;
+    if (route == 1 && (rc = kern.pick(ctx, H0P, sal_route1_kernel<32, 2>, sal_route1_kernel<64, 1>, cut.lds_bytes))) return rc;
+    SalParams a{};
+    a.D = d_D.get(); a.fac = d_fac.get(); a.rows_cap = rows_cap;
+    SalPlain k{};
+    k.rows_cap = rows_cap; k.act = d_act.get(); k.fac = d_fac.get(); k.g = d_g.get(); k.D = d_D.get();
+    for (int l = 0; l < r1.q.n_layers; ++l) k.a_off[l] = cut.a_off[l];
     FiTimer tm;
     double fold_ns = 0.0;
     Route1Blocks blocks1;
@@ -561,38 +472,27 @@ extern "C" int npbnn_predict_saliency(npbnn_ctx* ctx, const double* W_sets, cons
         if ((rc = prepare_route1(ctx, r1, *d.m, d_w.get() + (size_t)g0 * wn, d_co.get(), act_prm_sets ? act_prm_sets + (size_t)g0 * n_act : nullptr, ng,
                                  apply_out_fn, &blocks1, &p)))
             return rc;
+        const PlainNet net = plain_net(p, r1);
+        k.X = p.X; k.n_rows = n_rows;
         for (int s0 = 0; s0 < ng; s0 += NS) {
-            p.set0 = s0;
+            p.set0 = k.set0 = s0;
             p.n_set = std::min(NS, ng - s0);
             for (long long row0 = 0; row0 < n_rows; row0 += rows_cap) {
                 const int rows = (int)std::min<long long>(rows_cap, n_rows - row0);
                 const unsigned wgs = (unsigned)((rows + kPdpRows - 1) / kPdpRows);
                 const int n_slot = (rows + kSalWaveRows - 1) / kSalWaveRows;
+                a.row0 = k.row0 = row0;
                 for (int c0 = 0; c0 < C; c0 += n_c) {
                     const int nc = std::min(n_c, C - c0);
                     if (route == 1) {
-                        SalParams a{};
-                        a.D = d_D.get(); a.fac = d_fac.get(); a.row0 = row0; a.rows_cap = (int)rows_cap;
-                        if (H0P == 32) hipLaunchKernelGGL((sal_route1_kernel<32, 2>), dim3(wgs), dim3(kPdpRows), lds, st, p, a);
-                        else hipLaunchKernelGGL((sal_route1_kernel<64, 1>), dim3(wgs), dim3(kPdpRows), lds, st, p, a);
+                        kern.launch(dim3(wgs), st, p, a);
                     } else {
-                        SalPlain k{};
-                        k.X = p.X; k.n_rows = n_rows; k.row0 = row0; k.rows_cap = (int)rows_cap; k.Fp = Fp;
-                        k.w0t = p.w0t + (size_t)s0 * Fp * H0P; k.bias = p.bias + (size_t)s0 * H0P;
-                        k.tail = p.tail + (size_t)s0 * p.tail_floats; k.slopes = p.slopes + (size_t)s0 * kMaxLayers;
-                        k.n_layers = L; k.act_kind = p.act_kind; k.final_act = p.final_act; k.out_kind = p.out_kind; k.apply_out = p.apply_out;
-                        k.C = C; k.H0P = H0P; k.max_w = max_w; k.c0 = c0; k.n_c = nc;
-                        int off = 0;
-                        for (int l = 0; l < L; ++l) {
-                            k.width[l] = ctx->arch.out_dim[l]; k.t_inp[l] = p.t_inp[l]; k.t_off[l] = p.t_off[l]; k.a_off[l] = off;
-                            off += k.width[l];
-                        }
-                        k.act = d_act.get(); k.fac = d_fac.get(); k.g = d_g.get(); k.D = d_D.get();
-                        hipLaunchKernelGGL(sal_plain_kernel, dim3(wgs), dim3(256), 0, st, k);
+                        k.c0 = c0; k.n_c = nc;
+                        hipLaunchKernelGGL(sal_plain_kernel, dim3(wgs), dim3(256), 0, st, net, k);
                     }
                     HIP_TRY(ctx, hipGetLastError());
                     SalFold q{};
-                    q.D = d_D.get(); q.w0t = p.w0t; q.part = d_part.get(); q.rows = rows; q.rows_cap = (int)rows_cap; q.H0P = H0P; q.Fp = Fp;
+                    q.D = d_D.get(); q.w0t = p.w0t; q.part = d_part.get(); q.rows = rows; q.rows_cap = rows_cap; q.H0P = H0P; q.Fp = Fp;
                     q.Fq = Fq; q.n_c = nc; q.set0 = s0; q.n_slot = n_slot;
                     const int n_sc = p.n_set * nc;
                     const dim3 grid((unsigned)((n_slot + 3) / 4), (unsigned)((Fq + 32 * kSalNB - 1) / (32 * kSalNB)), (unsigned)n_sc);

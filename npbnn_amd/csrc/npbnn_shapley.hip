@@ -27,7 +27,7 @@ constexpr size_t kShapScratchBytes = 128ull << 20;   // device budget of the wal
                                                      // in chunks of explained rows and launches of fewer sets
 constexpr size_t kShapPhiBytes = 256ull << 20;       // budget of out_phi on the device
 constexpr size_t kShapPrepBytes = 256ull << 20;      // device budget of the float32 blocks: more sets are prepared group after group
-constexpr int kShapWavesPerCu = 8;                   // waves the splits of the walks aim at, per compute unit
+// (NPBNN_SHAPLEY_SCRATCH_BYTES, NPBNN_SHAPLEY_PHI_BYTES and NPBNN_SHAPLEY_PREP_BYTES override them; the cut itself is npbnn_attrib_shap_of's)
 
 // dst [Fp][cap] <- the rows `rows` [n] of X [.][Fp_src], transposed; 0 on the padding (features from F on, rows from n on)
 __global__ __launch_bounds__(256) void shap_gather_kernel(const float* X, int Fp_src, int F, const long long* rows, int n, int cap, int Fp, float* dst) {
@@ -155,66 +155,32 @@ __global__ __launch_bounds__(256) void shap_direct_kernel(const PdpParams p, con
 // ---- route 2: runtime widths, the values of a wave's 64 rows in a scratch [unit][value][lane]
 
 struct ShapPlain {
-    const float* w0t;      // [prepared set][Fp][H0P], bias [.][H0P], later layers [.][tail_floats], slopes [.][kMaxLayers]
-    const float* bias;
-    const float* tail;
-    const float* slopes;
-    int set0, Fp, H0P, tail_floats;
-    int n_layers, act_kind, final_act, out_kind, apply_out, C, max_w;
-    int width[kMaxLayers], t_inp[kMaxLayers], t_off[kMaxLayers];
+    int set0;              // the launch's first set among the prepared ones
     float* scr;            // [unit][H0 + 2 max_w + C][64]: z0, two layers' values, the previous step's outputs
 };
 
-// z0 [H0][64] -> the prediction, in a or b (each [max_w][64]); returns where.  Every address but the lane's offset is wave-uniform.
-__device__ __forceinline__ float* shap_plain_forward(const ShapPlain& k, int set, const float* z0, float* a, float* b) {
-    const int L = k.n_layers, C = k.C, kind = k.act_kind;
+// z0 [H0][64] -> the prediction, in va [2][max_w][64]; returns where.  Every address but the lane's offset is wave-uniform.
+__device__ __forceinline__ float* shap_plain_forward(const PlainNet& k, int set, const float* z0, float* va) {
+    const int L = k.n_layers, max_w = k.max_w;
     const float* sl = k.slopes + (size_t)set * kMaxLayers;
-    const float* tail = k.tail + (size_t)set * k.tail_floats;
     const bool act0 = L > 1 || k.final_act;
-    for (int i = 0; i < k.width[0]; ++i) a[i * 64] = act0 ? act_apply(z0[i * 64], kind, sl[0]) : z0[i * 64];
-    float* cur = a;
-    float* nxt = b;
-    for (int l = 1; l < L; ++l) {
-        const int n_in = k.width[l - 1], n_out = k.width[l], inp = k.t_inp[l];
-        const float* wb = tail + k.t_off[l];
-        const float* wm = wb + ((n_out + 3) & ~3);
-        const bool has_act = l < L - 1 || k.final_act;
-        for (int o = 0; o < n_out; ++o) {
-            float z = wb[o];
-            const float* wr = wm + (size_t)o * inp;
-            for (int i = 0; i < n_in; ++i) z = fmaf(cur[i * 64], wr[i], z);
-            nxt[o * 64] = has_act ? act_apply(z, kind, sl[l]) : z;
-        }
-        float* t = cur; cur = nxt; nxt = t;
-    }
-    if (!k.apply_out) return cur;
-    if (k.out_kind == NPBNN_OUT_SOFTMAX) {
-        float m = -3.402823466e38f;
-        for (int c = 0; c < C; ++c) m = fmaxf(m, cur[c * 64]);
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float v = __expf(cur[c * 64] - m);
-            cur[c * 64] = v;
-            s += v;
-        }
-        const float r = 1.f / s;
-        for (int c = 0; c < C; ++c) cur[c * 64] *= r;
-    } else if (k.out_kind == NPBNN_OUT_SOFTPLUS_HALF) {
-        for (int c = C / 2; c < C; ++c) cur[c * 64] = softplus_f(cur[c * 64]);
-    }
+    for (int i = 0; i < k.width[0]; ++i) va[i * 64] = act0 ? act_apply(z0[i * 64], k.act_kind, sl[0]) : z0[i * 64];
+    // (layer l's values go to the half of va the layer before it did not write)
+    plain_later_layers(k, k.tail + (size_t)set * k.tail_floats, sl, va, nullptr, 64, [&](int l) { return (l & 1) * max_w; });
+    float* cur = va + (size_t)((L - 1) & 1) * max_w * 64;
+    if (k.apply_out) out_function<0>(k.out_kind, k.C, [&](int c) -> float& { return cur[c * 64]; });
     return cur;
 }
 
 // grid (ceil(n / 256), sets of the launch), block 256: shap_direct_kernel with runtime widths; wave (set, 64 rows) owns scratch unit
 // (blockIdx.y gridDim.x + blockIdx.x) 4 + wave
-__global__ __launch_bounds__(256) void shap_direct_plain_kernel(const ShapPlain k, const ShapDirect a) {
+__global__ __launch_bounds__(256) void shap_direct_plain_kernel(const PlainNet k, const ShapPlain u, const ShapDirect a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
-    const int set = k.set0 + blockIdx.y, H0 = k.width[0], H0P = k.H0P;
+    const int set = u.set0 + blockIdx.y, H0 = k.width[0], H0P = k.H0P;
     const size_t unit = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6);
-    float* z0 = k.scr + unit * (size_t)(H0 + 2 * k.max_w + k.C) * 64 + (threadIdx.x & 63);
+    float* z0 = u.scr + unit * (size_t)(H0 + 2 * k.max_w + k.C) * 64 + (threadIdx.x & 63);
     float* va = z0 + (size_t)H0 * 64;
-    float* vb = va + (size_t)k.max_w * 64;
     const float* w0 = k.w0t + (size_t)set * k.Fp * H0P;
     const float* bias = k.bias + (size_t)set * H0P;
     for (int h0 = 0; h0 < H0; h0 += 8) {                              // (H0P is a multiple of 32: h0 + 7 < H0P)
@@ -234,25 +200,24 @@ __global__ __launch_bounds__(256) void shap_direct_plain_kernel(const ShapPlain 
                 if (a.z0out) a.z0out[((size_t)set * a.n + i) * H0P + h0 + u] = z[u];
             }
     }
-    const float* y = shap_plain_forward(k, set, z0, va, vb);
+    const float* y = shap_plain_forward(k, set, z0, va);
     float* fo = a.fout + (((size_t)a.f_set0 + blockIdx.y) * a.f_stride + a.f_row0 + i) * k.C;
     for (int c = 0; c < k.C; ++c) fo[c] = y[c * 64];
 }
 
 // grid (ceil(n_rb n_split / 4), sets of the launch), block 256: shap_walk_kernel with runtime widths; wave (set, unit) owns scratch
 // unit blockIdx.y n_rb n_split + unit
-__global__ __launch_bounds__(256) void shap_walk_plain_kernel(const ShapPlain k, const ShapWalk a) {
+__global__ __launch_bounds__(256) void shap_walk_plain_kernel(const PlainNet k, const ShapPlain u, const ShapWalk a) {
     const int unit = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     if (unit >= a.n_rb * a.n_split) return;                           // (wave-uniform; the kernel has no barrier)
     const int lane = threadIdx.x & 63, rb = unit / a.n_split, q = unit % a.n_split;
     const int e = rb * 64 + lane;
     const bool live = e < a.rows;
-    const int set = k.set0 + blockIdx.y, C = k.C, P = a.P, H0 = k.width[0], H0P = k.H0P;
+    const int set = u.set0 + blockIdx.y, C = k.C, P = a.P, H0 = k.width[0], H0P = k.H0P;
     const size_t su = (size_t)blockIdx.y * a.n_rb * a.n_split + unit;
-    float* z0 = k.scr + su * (size_t)(H0 + 2 * k.max_w + C) * 64 + lane;
+    float* z0 = u.scr + su * (size_t)(H0 + 2 * k.max_w + C) * 64 + lane;
     float* va = z0 + (size_t)H0 * 64;
-    float* vb = va + (size_t)k.max_w * 64;
-    float* prev = vb + (size_t)k.max_w * 64;
+    float* prev = va + 2 * (size_t)k.max_w * 64;
     const float* w0 = k.w0t + (size_t)set * k.Fp * H0P;
     const float* xe = a.xeT + e;
     double* dst = a.part + (((size_t)blockIdx.y * a.n_rb + rb) * a.n_split + q) * ((size_t)P * C * 64) + lane;
@@ -263,7 +228,7 @@ __global__ __launch_bounds__(256) void shap_walk_plain_kernel(const ShapPlain k,
         const float* zb = a.z0b + ((size_t)set * a.n_bg + b) * H0P;
         for (int u = 0; u < H0; ++u) z0[u * 64] = zb[u];
         {
-            const float* y = shap_plain_forward(k, set, z0, va, vb);
+            const float* y = shap_plain_forward(k, set, z0, va);
             for (int c = 0; c < C; ++c) prev[c * 64] = y[c * 64];
         }
         for (int s = 0; s < P; ++s) {
@@ -280,7 +245,7 @@ __global__ __launch_bounds__(256) void shap_walk_plain_kernel(const ShapPlain k,
                 const float* wj = w0 + (size_t)j * H0P;
                 for (int u = 0; u < H0; ++u) z0[u * 64] = fmaf(wj[u], dx, z0[u * 64]);
             }
-            const float* y = shap_plain_forward(k, set, z0, va, vb);
+            const float* y = shap_plain_forward(k, set, z0, va);
             for (int c = 0; c < C; ++c) {
                 const float yc = y[c * 64];
                 const double diff = (double)(yc - prev[c * 64]);
@@ -351,7 +316,7 @@ extern "C" int npbnn_predict_shapley(npbnn_ctx* ctx, const double* W_sets, const
     if ((rc = open_sets_table(ctx, "predict_shapley", which_bg, &tg))) return rc;
     const FeatureTable& mx = *tb.d->m;
     const FeatureTable& mb = *tg.d->m;
-    const int F = ctx->arch.in_dim, C = ctx->net.n_out, L = ctx->net.n_layers, n_act = L - 1, Fp = mx.Fp, P = n_players;
+    const int F = ctx->arch.in_dim, C = ctx->net.n_out, n_act = ctx->net.n_layers - 1, Fp = mx.Fp, P = n_players;
     for (int i = 0; i < n_explain; ++i)
         if (rows[i] < 0 || rows[i] >= tb.n_rows) return fail(ctx, NPBNN_E_ARG, "predict_shapley: rows[%d] = %lld is outside the table's %lld rows", i, (long long)rows[i], tb.n_rows);
     for (int i = 0; i < n_bg; ++i)
@@ -387,45 +352,25 @@ extern "C" int npbnn_predict_shapley(npbnn_ctx* ctx, const double* W_sets, const
         }
     }
     const size_t PC = (size_t)P * C, E = (size_t)n_explain, wn = (size_t)ctx->n_weights;
-    if (out_phi) {
-        const size_t budget = env_bytes("NPBNN_SHAPLEY_PHI_BYTES", kShapPhiBytes), per_row = (size_t)n_sets * PC * sizeof(double);
-        if (E > budget / per_row)
-            return fail(ctx, NPBNN_E_NOMEM, "predict_shapley: out_phi of %d sets x %d rows x %d players x %d outputs is over its budget of %zu bytes; at most %zu explained rows fit",
-                        n_sets, n_explain, P, C, budget, budget / per_row);
-    }
     hipStream_t st = ctx->stream;
 
-    // ---- the route and its shapes
-    Route1Plan r1 = plan_route1(ctx, Fp, 1, "NPBNN_SHAPLEY_PLAIN");
-    const int route = r1.fits ? 1 : 2;
-    if (route == 2) {
-        r1.H0P = round_up(ctx->arch.out_dim[0], 32);
-        r1.q.H0P = r1.H0P;
+    // ---- the route, the cut of the job and the buffers it needs (npbnn_attrib_plan.h)
+    const npbnn_attrib_route r1 = plan_route(ctx, NPBNN_ATTRIB_SHAPLEY, Fp, 1, "NPBNN_SHAPLEY_PLAIN");
+    const npbnn_attrib_shap_req req = {&r1, C, P, n_explain, n_bg, n_perm, n_sets, ctx->n_cu, out_phi ? 1 : 0,
+                                       (long long)env_bytes("NPBNN_SHAPLEY_SCRATCH_BYTES", kShapScratchBytes),
+                                       (long long)env_bytes("NPBNN_SHAPLEY_PREP_BYTES", kShapPrepBytes),
+                                       (long long)env_bytes("NPBNN_SHAPLEY_PHI_BYTES", kShapPhiBytes)};
+    npbnn_attrib_shap cut;
+    switch (npbnn_attrib_shap_of(&req, &cut)) {
+        case NPBNN_ATTRIB_E_PHI:
+            return fail(ctx, NPBNN_E_NOMEM, "predict_shapley: out_phi of %d sets x %d rows x %d players x %d outputs is over its budget of %zu bytes; at most %zu explained rows fit",
+                        n_sets, n_explain, P, C, (size_t)req.phi_bytes, (size_t)cut.phi_rows_fit);
+        case NPBNN_ATTRIB_E_WALKS:
+            return fail(ctx, NPBNN_E_ARG, "predict_shapley: n_bg x n_perm = %lld walks are more than %d", cut.walks, INT_MAX);
+        default: break;
     }
-    const int H0P = r1.H0P, H0 = ctx->arch.out_dim[0];
-    int max_w = 0;
-    for (int l = 0; l < L; ++l) max_w = std::max(max_w, ctx->arch.out_dim[l]);
-    // A unit is one wave of the walk kernel: 64 rows x one split of the W walks.  Its partials take PC x 64 doubles, on route 2 its
-    // scratch (H0 + 2 max_w + C) x 64 floats more.  The splits aim at kShapWavesPerCu waves per compute unit over all the sets and
-    // rows; the budget then bounds the row blocks of a chunk, and the sets of a launch.
-    const size_t budget = env_bytes("NPBNN_SHAPLEY_SCRATCH_BYTES", kShapScratchBytes);
-    const size_t scr_unit = route == 2 ? (size_t)(H0 + 2 * max_w + C) * 64 : 0;
-    const size_t unit_bytes = PC * 64 * sizeof(double) + scr_unit * sizeof(float);
-    const long long max_units = std::max<long long>(1, (long long)(budget / unit_bytes));
-    const long long W = (long long)n_bg * n_perm;
-    if (W > INT_MAX) return fail(ctx, NPBNN_E_ARG, "predict_shapley: n_bg x n_perm = %lld walks are more than %d", W, INT_MAX);
-    const long long n_rb_all = ((long long)n_explain + 63) / 64;
-    const long long want = (long long)kShapWavesPerCu * ctx->n_cu / (n_rb_all * n_sets);
-    const int n_split = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(W, want), max_units));
-    const int rb_cap = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(n_rb_all, max_units / n_split), 1 << 16));
-    const int nsl = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(n_sets, max_units / ((long long)n_split * rb_cap)), 65535));   // (a launch's sets are its grid's second dimension)
-    const int e_cap = rb_cap * 64, b_cap = round_up(n_bg, 64), bg_blocks = (n_bg + 255) / 256, ex_blocks = (e_cap + 255) / 256;
+    const int route = r1.route, H0P = r1.H0P, n_split = cut.n_split, nsl = cut.nsl, e_cap = cut.e_cap, b_cap = cut.b_cap, prep_sets = cut.prep_sets;
 
-    const size_t set_floats = (size_t)Fp * H0P + H0P + r1.q.tail_floats + kMaxLayers;
-    const int prep_sets = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_sets, kShapPrepBytes / (set_floats * sizeof(float))));
-
-    std::vector<double> co((size_t)F);
-    for (int f = 0; f < F; ++f) co[f] = col_override ? col_override[f] : NAN;
     std::vector<int> ints;                                            // perms | pstart | pcols | pskip
     ints.insert(ints.end(), perms, perms + (size_t)n_perm * P);
     ints.insert(ints.end(), pstart.begin(), pstart.end());
@@ -439,61 +384,55 @@ extern "C" int npbnn_predict_shapley(npbnn_ctx* ctx, const double* W_sets, const
     DevBuf<float> d_xeT, d_xbT, d_z0b, d_fx, d_fb, d_scr;
     DevBuf<int> d_ints;
     DevBuf<long long> d_idx;
-    if ((rc = dev_alloc(ctx, d_w, (size_t)n_sets * wn))) return rc;
-    if ((rc = dev_alloc(ctx, d_co, co.size()))) return rc;
+    const std::vector<double> co = point_constants(F, col_override, nullptr, 0, nullptr, 1);
+    if ((rc = upload_sets(ctx, W_sets, n_sets, co, d_w, d_co))) return rc;
     if ((rc = dev_alloc(ctx, d_ints, ints.size()))) return rc;
     if ((rc = dev_alloc(ctx, d_idx, idx.size()))) return rc;
-    if ((rc = dev_alloc(ctx, d_xeT, (size_t)Fp * e_cap))) return rc;
-    if ((rc = dev_alloc(ctx, d_xbT, (size_t)Fp * b_cap))) return rc;
-    if ((rc = dev_alloc(ctx, d_z0b, (size_t)prep_sets * n_bg * H0P))) return rc;
-    if ((rc = dev_alloc(ctx, d_fx, (size_t)n_sets * E * C))) return rc;
-    if ((rc = dev_alloc(ctx, d_fb, (size_t)n_sets * n_bg * C))) return rc;
-    if ((rc = dev_alloc(ctx, d_part, (size_t)nsl * rb_cap * n_split * PC * 64))) return rc;
-    if ((rc = dev_alloc(ctx, d_mean, 2 * PC * E))) return rc;
-    if ((rc = dev_alloc(ctx, d_abs, (size_t)n_sets * PC))) return rc;
-    if (out_phi && (rc = dev_alloc(ctx, d_phi, (size_t)n_sets * PC * E))) return rc;
-    // route 2's scratch units: a walk launch's nsl x rb_cap x n_split waves, a direct launch's nsl x 4 x workgroups
-    const size_t scr_units = (size_t)nsl * std::max<size_t>((size_t)rb_cap * n_split, 4 * (size_t)std::max(bg_blocks, ex_blocks));
-    if (route == 2 && (rc = dev_alloc(ctx, d_scr, scr_units * scr_unit))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(d_w.get(), W_sets, (size_t)n_sets * wn * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_co.get(), co.data(), co.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = dev_alloc(ctx, d_xeT, (size_t)cut.n_xeT))) return rc;
+    if ((rc = dev_alloc(ctx, d_xbT, (size_t)cut.n_xbT))) return rc;
+    if ((rc = dev_alloc(ctx, d_z0b, (size_t)cut.n_z0b))) return rc;
+    if ((rc = dev_alloc(ctx, d_fx, (size_t)cut.n_fx))) return rc;
+    if ((rc = dev_alloc(ctx, d_fb, (size_t)cut.n_fb))) return rc;
+    if ((rc = dev_alloc(ctx, d_part, (size_t)cut.n_part))) return rc;
+    if ((rc = dev_alloc(ctx, d_mean, (size_t)cut.n_mean))) return rc;
+    if ((rc = dev_alloc(ctx, d_abs, (size_t)cut.n_abs))) return rc;
+    if (out_phi && (rc = dev_alloc(ctx, d_phi, (size_t)cut.n_phi))) return rc;
+    if (route == 2 && (rc = dev_alloc(ctx, d_scr, (size_t)cut.n_scr))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(d_ints.get(), ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_idx.get(), idx.data(), idx.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemsetAsync(d_mean.get(), 0, 2 * PC * E * sizeof(double), st));
-    HIP_TRY(ctx, hipMemsetAsync(d_abs.get(), 0, (size_t)n_sets * PC * sizeof(double), st));
-    hipLaunchKernelGGL(shap_gather_kernel, dim3((unsigned)(((size_t)Fp * b_cap + 255) / 256)), dim3(256), 0, st, (const float*)mb.X.get(), mb.Fp, F,
+    HIP_TRY(ctx, hipMemsetAsync(d_mean.get(), 0, (size_t)cut.n_mean * sizeof(double), st));
+    HIP_TRY(ctx, hipMemsetAsync(d_abs.get(), 0, (size_t)cut.n_abs * sizeof(double), st));
+    hipLaunchKernelGGL(shap_gather_kernel, dim3((unsigned)(((size_t)cut.n_xbT + 255) / 256)), dim3(256), 0, st, (const float*)mb.X.get(), mb.Fp, F,
                        (const long long*)d_idx.get() + n_explain, (int)n_bg, b_cap, Fp, d_xbT.get());
     HIP_TRY(ctx, hipGetLastError());
 
-    const size_t lds = ((size_t)Fp * H0P + (size_t)r1.q.tail_floats) * sizeof(float);
+    Route1Kernel<PdpParams, ShapWalk> walk;
+    Route1Kernel<PdpParams, ShapDirect> direct1;
     if (route == 1) {
-        const void* fn = H0P == 32 ? reinterpret_cast<const void*>(shap_walk_kernel<32>) : reinterpret_cast<const void*>(shap_walk_kernel<64>);
-        HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if ((rc = walk.pick(ctx, H0P, shap_walk_kernel<32>, shap_walk_kernel<64>, cut.lds_bytes))) return rc;
+        if ((rc = direct1.pick(ctx, H0P, shap_direct_kernel<32>, shap_direct_kernel<64>, 0))) return rc;
     }
     ShapWalk a{};
     a.xeT = d_xeT.get(); a.xbT = d_xbT.get(); a.z0b = d_z0b.get();
     a.perms = d_ints.get(); a.pstart = a.perms + (size_t)n_perm * P; a.pcols = a.pstart + P + 1; a.pskip = a.pcols + F;
-    a.part = d_part.get(); a.e_cap = e_cap; a.b_cap = b_cap; a.n_bg = n_bg; a.n_perm = n_perm; a.P = P; a.n_split = n_split; a.W = (int)W;
+    a.part = d_part.get(); a.e_cap = e_cap; a.b_cap = b_cap; a.n_bg = n_bg; a.n_perm = n_perm; a.P = P; a.n_split = n_split; a.W = cut.W;
     ShapFold q{};
     q.part = d_part.get(); q.mean = d_mean.get(); q.sq = d_mean.get() + PC * E; q.abs = d_abs.get(); q.phi = out_phi ? d_phi.get() : nullptr;
-    q.E = (long long)E; q.n_split = n_split; q.PC = (int)PC; q.inv_w = 1.0 / (double)W;
+    q.E = (long long)E; q.n_split = n_split; q.PC = (int)PC; q.inv_w = 1.0 / (double)cut.W;
 
     FiTimer tm;
     double walk_ns = 0.0;
     Route1Blocks blocks1;
     PdpParams p{};
-    ShapPlain k{};
+    PlainNet k{};
+    ShapPlain u{};
+    u.scr = d_scr.get();
     // one launch of a direct kernel: the sets s0 .. s0 + ns - 1 of the prepared group on the n rows of xT
     auto direct = [&](int s0, int ns, const ShapDirect& dk) {
         const dim3 grid((unsigned)((dk.n + 255) / 256), (unsigned)ns);
-        if (route == 1) {
-            p.set0 = s0;
-            if (H0P == 32) hipLaunchKernelGGL((shap_direct_kernel<32>), grid, dim3(256), 0, st, p, dk);
-            else hipLaunchKernelGGL((shap_direct_kernel<64>), grid, dim3(256), 0, st, p, dk);
-        } else {
-            k.set0 = s0;
-            hipLaunchKernelGGL(shap_direct_plain_kernel, grid, dim3(256), 0, st, k, dk);
-        }
+        p.set0 = u.set0 = s0;
+        if (route == 1) direct1.launch(grid, st, p, dk);
+        else hipLaunchKernelGGL(shap_direct_plain_kernel, grid, dim3(256), 0, st, k, u, dk);
     };
     // Groups of prepared sets outside, chunks of explained rows inside: a group is prepared once.  A row's sums over the sets still grow
     // in set order, a set's sum of |phi| in chunk order.  (A group's blocks go into the same buffers as the one before: its preparation
@@ -503,10 +442,7 @@ extern "C" int npbnn_predict_shapley(npbnn_ctx* ctx, const double* W_sets, const
         if ((rc = prepare_route1(ctx, r1, mx, d_w.get() + (size_t)g0 * wn, d_co.get(), act_prm_sets ? act_prm_sets + (size_t)g0 * n_act : nullptr, ng,
                                  apply_out_fn, &blocks1, &p)))
             return rc;
-        k.w0t = p.w0t; k.bias = p.bias; k.tail = p.tail; k.slopes = p.slopes; k.Fp = Fp; k.H0P = H0P; k.tail_floats = p.tail_floats;
-        k.n_layers = L; k.act_kind = p.act_kind; k.final_act = p.final_act; k.out_kind = p.out_kind; k.apply_out = p.apply_out; k.C = C;
-        k.max_w = max_w; k.scr = d_scr.get();
-        for (int l = 0; l < L; ++l) { k.width[l] = ctx->arch.out_dim[l]; k.t_inp[l] = p.t_inp[l]; k.t_off[l] = p.t_off[l]; }
+        k = plain_net(p, r1);
         // the background rows: z0(b) and f(b) of the group's sets
         for (int s0 = 0; s0 < ng; s0 += nsl) {
             ShapDirect dk{};
@@ -518,7 +454,7 @@ extern "C" int npbnn_predict_shapley(npbnn_ctx* ctx, const double* W_sets, const
         for (long long e0 = 0; e0 < n_explain; e0 += e_cap) {
             const int rows_c = (int)std::min<long long>(e_cap, n_explain - e0);
             if (g0 == 0 || e_cap < n_explain) {            // (one chunk: its rows stay gathered from the first group on)
-                hipLaunchKernelGGL(shap_gather_kernel, dim3((unsigned)(((size_t)Fp * e_cap + 255) / 256)), dim3(256), 0, st, (const float*)mx.X.get(), mx.Fp,
+                hipLaunchKernelGGL(shap_gather_kernel, dim3((unsigned)(((size_t)cut.n_xeT + 255) / 256)), dim3(256), 0, st, (const float*)mx.X.get(), mx.Fp,
                                    F, (const long long*)d_idx.get() + e0, rows_c, e_cap, Fp, d_xeT.get());
                 HIP_TRY(ctx, hipGetLastError());
             }
@@ -533,14 +469,8 @@ extern "C" int npbnn_predict_shapley(npbnn_ctx* ctx, const double* W_sets, const
                 HIP_TRY(ctx, hipGetLastError());
                 const dim3 grid((unsigned)((a.n_rb * n_split + 3) / 4), (unsigned)ns);
                 tm.mark(0, st);
-                if (route == 1) {
-                    p.set0 = s0;
-                    if (H0P == 32) hipLaunchKernelGGL((shap_walk_kernel<32>), grid, dim3(256), lds, st, p, a);
-                    else hipLaunchKernelGGL((shap_walk_kernel<64>), grid, dim3(256), lds, st, p, a);
-                } else {
-                    k.set0 = s0;
-                    hipLaunchKernelGGL(shap_walk_plain_kernel, grid, dim3(256), 0, st, k, a);
-                }
+                if (route == 1) walk.launch(grid, st, p, a);
+                else hipLaunchKernelGGL(shap_walk_plain_kernel, grid, dim3(256), 0, st, k, u, a);
                 HIP_TRY(ctx, hipGetLastError());
                 tm.mark(1, st);
                 q.n_set = ns; q.set0 = g0 + s0;
@@ -553,8 +483,8 @@ extern "C" int npbnn_predict_shapley(npbnn_ctx* ctx, const double* W_sets, const
             }
         }
     }
-    std::vector<double> h_mean(2 * PC * E), h_abs((size_t)n_sets * PC), h_phi(out_phi ? (size_t)n_sets * PC * E : 0);
-    std::vector<float> h_fx((size_t)n_sets * E * C), h_fb((size_t)n_sets * n_bg * C);
+    std::vector<double> h_mean((size_t)cut.n_mean), h_abs((size_t)cut.n_abs), h_phi((size_t)cut.n_phi);
+    std::vector<float> h_fx((size_t)cut.n_fx), h_fb((size_t)cut.n_fb);
     HIP_TRY(ctx, hipMemcpyAsync(h_mean.data(), d_mean.get(), h_mean.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(h_abs.data(), d_abs.get(), h_abs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(h_fx.data(), d_fx.get(), h_fx.size() * sizeof(float), hipMemcpyDeviceToHost, st));

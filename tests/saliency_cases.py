@@ -180,15 +180,19 @@ for _sets in (1, 2, 3, 7):
 # two overridden columns: their gradient must be exactly 0
 _case("override_two_columns", 1, override={5: 1.25, 17: -0.75}, pinned=True)
 _case("test_table", 1, which=1, test_rows=173)
-# Scratch in chunks.  A row of a chunk takes 3 x 32 x 4 bytes of later-layer factors and, for each of the 2 x 5 (set, output) pairs
-# of a launch, 32 x 4 bytes of D and 3 x 64 x 8 / 256 bytes of partials: 1724 bytes, 441 344 for the 256 rows a chunk has at
-# least.  900 000 bytes hold 522 rows: chunks of 512, five of them for 2111 rows.
+# Scratch in chunks: chunks of 512 rows, five of them (tests/test_host_attrib_plan.py asserts the cut these bytes give).
 _case("scratch_in_chunks", 1, rows=2111, env=(("NPBNN_SALIENCY_SCRATCH_BYTES", "900000"),))
 # route 2 on real shapes: a wide first layer, and the reference's default network where the library streams its weights by itself
 _case("wide_130x40", 2, nodes=(130, 40))
 _case("streamed_257x700", 2, rows=257, features=700, nodes=(50, 5))
 # config 2's network
 _case("config2_network", 1, rows=3000, features=256, nodes=(32, 8), n_out=10)
+# The turns of the plan's cut that nothing above takes; tests/test_host_attrib_plan.py asserts what each budget gives.  Route 2 with
+# its outputs in launches of 2, 2 and 1 (the later launches read the activations the first left in the scratch) over chunks of 256
+# and 44 rows; and the sets_7 cases with three sets' blocks prepared at a time: groups of 3, 3 and 1 sets.
+_case("route2_outputs_in_chunks", 2, nodes=(65, 6), env=(("NPBNN_SALIENCY_SCRATCH_BYTES", "520000"),))
+_case("sets_7_two_a_launch_in_groups", 1, sets=7, env=(("NPBNN_SALIENCY_PREP_BYTES", str(3 * 7104)),))
+_case("sets_7_one_a_launch_in_groups", 1, sets=7, nodes=(40, 6), env=(("NPBNN_SALIENCY_PREP_BYTES", str(3 * 13760)),))
 
 
 def inputs(case):

@@ -240,8 +240,8 @@ _case("override_grouped", 1, override={5: 1.25, 17: -0.75}, pinned=True, n_group
 # explained rows from the test table against backgrounds from the training table, and both from the test table
 _case("two_tables", 1, which=1, test_rows=173, bg_table=0)
 _case("test_table_alone", 1, which=1, test_rows=173)
-# Scratch in chunks.  A wave's partials take 40 x 5 x 64 x 8 = 102 400 bytes; 250 000 bytes hold two, which go to the splits of the
-# walks: a chunk is one block of 64 rows, five of them for 257 rows, one set a launch.
+# Scratch in chunks: two splits of the walks, chunks of one block of 64 rows, one set a launch (tests/test_host_attrib_plan.py asserts
+# the cut these bytes give).
 _case("scratch_in_chunks", 1, n_explain=257, env=(("NPBNN_SHAPLEY_SCRATCH_BYTES", "250000"),))
 # route 2 on real shapes: a wide first layer, and the reference's default network where the library streams its weights by itself
 _case("wide_130x40", 2, nodes=(130, 40))
@@ -250,6 +250,12 @@ _case("streamed_20x700", 2, rows=60, features=700, nodes=(50, 5), n_explain=20, 
 _case("config2_network", 1, features=256, nodes=(32, 8), n_out=10, n_explain=300, n_bg=4, n_perm=4)
 # all 24 permutations of 4 players: the exact Shapley value
 _case("exact_4_players", 1, n_groups=4, all_perms=True)
+# The turns of the plan's cut that nothing above takes; tests/test_host_attrib_plan.py asserts what each budget gives.  Route 2 with
+# room for two units of partials and scratch: two splits, two chunks, one set a launch; and the sets_7 cases with three sets' blocks
+# prepared at a time: groups of 3, 3 and 1 sets.
+_case("route2_scratch_in_chunks", 2, nodes=(130, 40), env=(("NPBNN_SHAPLEY_SCRATCH_BYTES", "450000"),))
+_case("sets_7_two_a_launch_in_groups", 1, sets=7, env=(("NPBNN_SHAPLEY_PREP_BYTES", str(3 * 7104)),))
+_case("sets_7_one_a_launch_in_groups", 1, sets=7, nodes=(40, 6), env=(("NPBNN_SHAPLEY_PREP_BYTES", str(3 * 13760)),))
 
 
 def inputs(case):

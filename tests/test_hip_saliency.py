@@ -98,6 +98,22 @@ def test_same_bits_every_call(name, env, monkeypatch):
         assert np.abs(x).max() > 0
 
 
+@pytest.mark.parametrize("plain", [False, True])
+@pytest.mark.parametrize("name", ["sets_7_two_a_launch", "sets_7_one_a_launch"])
+def test_same_bits_prepared_group_after_group(name, plain, monkeypatch):
+    """three sets' blocks prepared at a time (the budget of the case's ``_in_groups`` twin): set order and row order are unchanged"""
+    case, inp, _ = _case_data(name)
+    if plain:
+        monkeypatch.setenv("NPBNN_SALIENCY_PLAIN", "1")
+    (whole,), _ = _device(case, inp)
+    for k, v in sc.CASES[name + "_in_groups"]["env"]:
+        monkeypatch.setenv(k, v)
+    (grouped,), route = _device(case, inp)
+    assert route == (2 if plain else 1)
+    for x, y in zip(whole, grouped):
+        assert np.array_equal(x, y) and np.abs(x).max() > 0
+
+
 def test_refusals_leave_route_0():
     case, inp, _ = _case_data("sets_3_two_a_launch")
     ctx = _context(case, inp)

@@ -124,6 +124,22 @@ def test_chunks_give_the_values_of_one_chunk(monkeypatch):
         assert sh.relative_error(chunked[k], whole[k]) <= sh.TOL, k
 
 
+@pytest.mark.parametrize("plain", [False, True])
+@pytest.mark.parametrize("name", ["sets_7_two_a_launch", "sets_7_one_a_launch"])
+def test_same_bits_prepared_group_after_group(name, plain, monkeypatch):
+    """three sets' blocks prepared at a time (the budget of the case's ``_in_groups`` twin): set order and row order are unchanged"""
+    case, inp, _ = _case_data(name)
+    if plain:
+        monkeypatch.setenv("NPBNN_SHAPLEY_PLAIN", "1")
+    (whole,), _ = _device(case, inp)
+    for k, v in sh.CASES[name + "_in_groups"]["env"]:
+        monkeypatch.setenv(k, v)
+    (grouped,), route = _device(case, inp)
+    assert route == (2 if plain else 1)
+    for k in sh.NAMES:
+        assert np.array_equal(whole[k], grouped[k]) and np.abs(whole[k]).max() > 0, k
+
+
 def test_without_phi_the_summaries_are_the_same_bits():
     case, inp, _ = _case_data("sets_3_two_a_launch")
     ctx = _context(case, inp)
