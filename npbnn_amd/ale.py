@@ -15,11 +15,9 @@ pre-activation by a multiple of ``W0[:, j]``.  The sums along the feature, the c
 taken here in float64: one curve per sample, so the band is a credible band of the effect itself."""
 import numpy as np
 
-from . import _capi as capi
 from .files import load_obj
-from .layers import output_kind
-from .model import data_transform_obj
 from .pdp import get_feature_summary
+from .stored import Network, check_level, checkpoint_samples, quantile_summary
 
 
 def _focal_column(focal_feature, who):
@@ -61,31 +59,20 @@ def accumulate_and_centre(counts, effects):
 
 def _ale_local_effects(data, focal, edges, weights, alphas, actFun, output_act_fun, data_transform):
     """(counts [K], local effects [S, K, n_out]) on the table as the device holds it (the device seam)."""
-    from .backend import HipContext, pack_weights
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    n_features = data.shape[1]
-    kind = output_kind(output_act_fun)
-    slopes = None
-    if actFun._function == "genReLU":
-        n_hidden = len(weights[0]) - 1
-        slopes = [np.asarray(a, dtype=float).ravel()[:n_hidden] for a in alphas]
-    override = np.full(n_features, np.nan) if data_transform is None else np.asarray(data_transform.column_override(), dtype=float)
-    ctx = HipContext()
-    try:
-        ctx.set_data(data)
-        ctx.set_arch_from_weights(weights[0], n_features, actFun.device_kind(),
-                                  capi.OUT_IDENTITY if kind is None else kind, capi.LIK_NONE)
-        if kind is None and output_act_fun is not None:
+    net = Network(weights, alphas, actFun, output_act_fun, data_transform)
+    with net.on(data) as ctx:
+        if net.custom_output:
             # a custom output callable has no device kind: one pass per (edge, sample), the callable and the bins on the host
+            data = np.asarray(data, dtype=np.float64)
             col = data[:, focal].astype(np.float32)
             k_of_row = np.minimum(np.searchsorted(edges.astype(np.float32)[1:], col, side="left"), len(edges) - 2)
             counts = np.bincount(k_of_row, minlength=len(edges) - 1).astype(np.int64)
             effects = np.zeros((len(weights), len(edges) - 1, ctx.n_out))
             for i, w in enumerate(weights):
-                prm = None if slopes is None else slopes[i]
+                prm = None if net.slopes is None else net.slopes[i]
                 lower = None
                 for k, z in enumerate(edges):
-                    co = override.copy()
+                    co = np.full(data.shape[1], np.nan) if net.override is None else net.override.copy()
                     if np.isnan(co[focal]):
                         co[focal] = z
                     upper = output_act_fun(ctx.predict(w, act_prm=prm, col_override=co, apply_out_fn=False))
@@ -94,10 +81,8 @@ def _ale_local_effects(data, focal, edges, weights, alphas, actFun, output_act_f
                         effects[i, k - 1] = (upper[rows] - lower[rows]).mean(axis=0)
                     lower = upper
             return counts, effects
-        return ctx.predict_ale([pack_weights(w) for w in weights], focal, edges, act_prm_sets=slopes, col_override=override,
-                               apply_out_fn=kind is not None)
-    finally:
-        ctx.close()
+        packed, kw = net.sets()
+        return ctx.predict_ale(packed, focal, edges, **kw)
 
 
 def get_ale(data, focal_feature, estimation_mode, size_output, actFun, output_act_fun, weights, alphas, data_transform,
@@ -117,8 +102,7 @@ def get_ale(data, focal_feature, estimation_mode, size_output, actFun, output_ac
     set, as in ``get_pdp``: a focal column it switches off gives a flat zero curve.  ``ValueError`` for more than one focal
     column."""
     focal = _focal_column(focal_feature, "get_ale")
-    if not 0.0 < level < 1.0:
-        raise ValueError("get_ale: level must lie in (0, 1)")
+    check_level(level, "get_ale")
     if len(weights) == 0:
         raise ValueError("get_ale: no stored samples")
     edges = make_ale_edges(data, focal, n_bins)
@@ -127,23 +111,14 @@ def get_ale(data, focal_feature, estimation_mode, size_output, actFun, output_ac
     samples = accumulate_and_centre(counts, effects)
     if samples.shape[2] != size_output:
         raise ValueError("get_ale: the network has %d outputs, size_output is %d" % (samples.shape[2], size_output))
-    tail = 0.5 * (1.0 - level)
-    result = np.empty((len(edges), size_output, 3))
-    result[:, :, 0] = samples.mean(axis=0)
-    result[:, :, 1:] = np.moveaxis(np.quantile(samples, (tail, 1.0 - tail), axis=0), 0, -1)
-    return {'feature': edges, 'counts': np.asarray(counts), 'ale': result, 'ale_samples': samples, 'local_effects': np.asarray(effects)}
+    return {'feature': edges, 'counts': np.asarray(counts), 'ale': quantile_summary(samples, level), 'ale_samples': samples,
+            'local_effects': np.asarray(effects)}
 
 
 def ale(pickle_file, ale_features, n_bins=40):
     """Accumulated local effects from a checkpoint ``[bnn, mcmc, logger]`` on the model's training matrix: one ``get_ale`` dict
     per focal column in ``ale_features`` (a column index, or a list holding one)."""
-    model, _, logger = load_obj(pickle_file)
-    samples = logger._post_weight_samples
-    weights = [s['weights'] for s in samples]
-    alphas = [s['alphas'] for s in samples]
-    transform = None
-    if model._feature_indicators is not None:
-        transform = data_transform_obj(model._feature_indicators, model._feature_means)
+    model, weights, alphas, transform = checkpoint_samples(load_obj(pickle_file))
     data = np.asarray(model._data, dtype=np.float64)
     return [get_ale(data, focal, model._estimation_mode, model._size_output, model._act_fun, model._output_act_fun,
                     weights, alphas, transform, n_bins=n_bins) for focal in ale_features]

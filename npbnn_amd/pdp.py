@@ -10,10 +10,8 @@ grid values folded into layer 0's bias.  The cumulative sum over the classes, th
 host in float64."""
 import numpy as np
 
-from . import _capi as capi
 from .files import load_obj
-from .layers import output_kind
-from .model import data_transform_obj
+from .stored import Network, checkpoint_samples
 
 
 def get_feature_summary(data, focal_features):
@@ -46,36 +44,22 @@ def make_pdp_features(data, focal_features, steps_continuous=100):
 
 def _pdp_row_means(data, focal_features, grid, weights, alphas, actFun, output_act_fun, data_transform):
     """[n_points, n_rows, n_out]: per grid point and row, the prediction averaged over the stored samples (the device seam)."""
-    from .backend import HipContext, pack_weights
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    n_features = data.shape[1]
-    kind = output_kind(output_act_fun)
-    slopes = None
-    if actFun._function == "genReLU":
-        n_hidden = len(weights[0]) - 1
-        slopes = [np.asarray(a, dtype=float).ravel()[:n_hidden] for a in alphas]
-    override = np.full(n_features, np.nan) if data_transform is None else np.asarray(data_transform.column_override(), dtype=float)
-    ctx = HipContext()
-    try:
-        ctx.set_data(data)
-        ctx.set_arch_from_weights(weights[0], n_features, actFun.device_kind(),
-                                  capi.OUT_IDENTITY if kind is None else kind, capi.LIK_NONE)
-        if kind is None and output_act_fun is not None:
+    net = Network(weights, alphas, actFun, output_act_fun, data_transform)
+    with net.on(data) as ctx:
+        if net.custom_output:
             # a custom output callable has no device kind: one pass per (grid point, sample), the callable on the host
-            out = np.zeros((len(grid), data.shape[0], ctx.n_out))
+            out = np.zeros((len(grid), np.shape(data)[0], ctx.n_out))
             for g, point in enumerate(grid):
-                co = override.copy()
+                co = np.full(np.shape(data)[1], np.nan) if net.override is None else net.override.copy()
                 cols = np.asarray(focal_features)
                 free = np.isnan(co[cols])
                 co[cols[free]] = np.asarray(point, dtype=float)[free]
                 for i, w in enumerate(weights):
-                    y = ctx.predict(w, act_prm=None if slopes is None else slopes[i], col_override=co, apply_out_fn=False)
+                    y = ctx.predict(w, act_prm=None if net.slopes is None else net.slopes[i], col_override=co, apply_out_fn=False)
                     out[g] += output_act_fun(y)
             return out / len(weights)
-        return ctx.predict_pdp([pack_weights(w) for w in weights], focal_features, grid, act_prm_sets=slopes,
-                               col_override=override, apply_out_fn=kind is not None)
-    finally:
-        ctx.close()
+        packed, kw = net.sets()
+        return ctx.predict_pdp(packed, focal_features, grid, **kw)
 
 
 def get_pdp(data, focal_features, estimation_mode, size_output, actFun, output_act_fun, weights, alphas, data_transform):
@@ -102,13 +86,7 @@ def get_pdp(data, focal_features, estimation_mode, size_output, actFun, output_a
 def pdp(pickle_file, pdp_features):
     """Partial dependence from a checkpoint ``[bnn, mcmc, logger]`` on the model's training matrix: one ``get_pdp`` dict per list
     of focal features in ``pdp_features``."""
-    model, _, logger = load_obj(pickle_file)
-    samples = logger._post_weight_samples
-    weights = [s['weights'] for s in samples]
-    alphas = [s['alphas'] for s in samples]
-    transform = None
-    if model._feature_indicators is not None:
-        transform = data_transform_obj(model._feature_indicators, model._feature_means)
+    model, weights, alphas, transform = checkpoint_samples(load_obj(pickle_file))
     data = np.asarray(model._data, dtype=np.float64)
     return [get_pdp(data, focal, model._estimation_mode, model._size_output, model._act_fun, model._output_act_fun,
                     weights, alphas, transform) for focal in pdp_features]

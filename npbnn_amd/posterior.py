@@ -17,9 +17,9 @@ import numpy as np
 
 from . import _capi as capi
 from .files import load_obj
-from .layers import ActFun, output_kind
+from .layers import ActFun
 from .likelihoods import CalcAccuracy
-from .stored import sigma_matrix
+from .stored import Network, sigma_matrix
 
 
 class _SamplePredictor:
@@ -30,14 +30,10 @@ class _SamplePredictor:
         from .backend import HipContext, pack_weights
         self._weights = [s["weights"] for s in post_samples]
         self._packed = np.stack([pack_weights(w) for w in self._weights])
-        self._kind = output_kind(output_act_fun)
+        self._net = Network(self._weights, [s["alphas"] for s in post_samples], actFun, output_act_fun)
         self._out_fn = output_act_fun
-        self._act = actFun
         self._n_features = n_features
-        self._slopes = None
-        if actFun._function == "genReLU":
-            n_hidden = len(self._weights[0]) - 1
-            self._slopes = [np.asarray(s["alphas"], dtype=float)[:n_hidden] for s in post_samples]
+        self._slopes, self._applied = self._net.slopes, self._net.apply_out_fn
         self._ctx = HipContext()
         self._arch_set = False
 
@@ -45,20 +41,19 @@ class _SamplePredictor:
         ctx = self._ctx
         ctx.set_data(features)
         if not self._arch_set:
-            ctx.set_arch_from_weights(self._weights[0], self._n_features, self._act.device_kind(),
-                                      capi.OUT_IDENTITY if self._kind is None else self._kind, capi.LIK_NONE)
+            self._net.describe_to(ctx, self._n_features)
             self._arch_set = True
         return ctx
 
     @property
     def custom_output(self):
         """A custom output callable: no device kind, applied on the host to every sample's stack."""
-        return self._kind is None and self._out_fn is not None
+        return self._net.custom_output
 
     def _out_kind_for(self, kind, who):
         """The OUT_* constant the driver's ``kind`` stands for; ``ValueError`` in ``who``'s name when the model's output function is another."""
         want = {"classification": capi.OUT_SOFTMAX, "regression": capi.OUT_IDENTITY, "regression-error": capi.OUT_SOFTPLUS_HALF}[kind]
-        if (capi.OUT_IDENTITY if self._kind is None else self._kind) != want:
+        if self._net.out_kind != want:
             raise ValueError("%s: kind %r does not go with the model's output function" % (who, kind))
         return want
 
@@ -69,7 +64,7 @@ class _SamplePredictor:
 
     def predict_loaded(self):
         """``predict`` on the matrix ``load`` uploaded, without a second upload."""
-        y = self._ctx.predict_sets(list(self._packed), act_prm_sets=self._slopes, apply_out_fn=self._kind is not None)
+        y = self._ctx.predict_sets(list(self._packed), act_prm_sets=self._slopes, apply_out_fn=self._applied)
         if self.custom_output:      # host side, sample by sample
             y = np.array([self._out_fn(yi) for yi in y])
         return y
@@ -84,7 +79,7 @@ class _SamplePredictor:
             lo, hi = posterior_hpd(y, level)
             return np.mean(y, axis=0), lo, hi
         ctx = self._load(features)
-        return ctx.predict_sets_hpd(list(self._packed), level, act_prm_sets=self._slopes, apply_out_fn=self._kind is not None)
+        return ctx.predict_sets_hpd(list(self._packed), level, act_prm_sets=self._slopes, apply_out_fn=self._applied)
 
     def load(self, features):
         """Upload ``features`` (and describe the network on the first call): what ``permute`` and ``summary`` work on."""
@@ -119,7 +114,7 @@ class _SamplePredictor:
         if self.custom_output:
             raise ValueError("a custom output callable has no device summary")
         return self._ctx.predict_sets_summary(self._packed, mode, labels=labels, act_prm_sets=self._slopes,
-                                              want_summary=want_summary, apply_out_fn=self._kind is not None)
+                                              want_summary=want_summary, apply_out_fn=self._applied)
 
     def support(self, mode, labels, thresholds, **kw):
         """Threshold cube (and Bayes-factor table, NaN-masked summary, keep mask: ``HipContext.predict_sets_support``'s keywords) of
@@ -127,7 +122,7 @@ class _SamplePredictor:
         if self.custom_output:
             raise ValueError("a custom output callable has no device summary")
         return self._ctx.predict_sets_support(self._packed, mode, labels, thresholds, act_prm_sets=self._slopes,
-                                              apply_out_fn=self._kind is not None, **kw)
+                                              apply_out_fn=self._applied, **kw)
 
     def lppd(self, features, labels, lik_kind, sigma_sets=None, pointwise=False):
         """``HipContext.predict_sets_lppd``'s dict for the stored samples on ``features`` against ``labels`` (class indices,
@@ -204,7 +199,7 @@ class _SamplePredictor:
             return res if pointwise else dict(res, rhat=None, ess=None)
         ctx = self._load(features)
         return ctx.predict_sets_convergence(self._packed, n_chains, rhat_threshold, act_prm_sets=self._slopes,
-                                            apply_out_fn=self._kind is not None, pointwise=pointwise)
+                                            apply_out_fn=self._applied, pointwise=pointwise)
 
     def close(self):
         self._ctx.close()

@@ -12,44 +12,20 @@ summary over the samples is taken here in float64: one value per sample, so the 
 itself."""
 import numpy as np
 
-from . import _capi as capi
 from .files import load_obj
 from .layers import output_kind
-from .model import data_transform_obj
+from .stored import Network, check_level, checkpoint_samples, quantile_summary
 
 
 def _saliency_means(data, weights, alphas, actFun, output_act_fun, data_transform):
     """(mean, abs, sq), each [S, n_out, F]: the row means of G, |G| and G^2 on the table as the device holds it (the device
     seam)."""
-    from .backend import HipContext, pack_weights
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    n_features = data.shape[1]
-    kind = output_kind(output_act_fun)
-    if kind is None and output_act_fun is not None:
+    net = Network(weights, alphas, actFun, output_act_fun, data_transform)
+    if net.custom_output:
         raise ValueError("get_saliency: a custom output callable has no device kind and cannot be differentiated")
-    slopes = None
-    if actFun._function == "genReLU":
-        n_hidden = len(weights[0]) - 1
-        slopes = [np.asarray(a, dtype=float).ravel()[:n_hidden] for a in alphas]
-    override = None if data_transform is None else np.asarray(data_transform.column_override(), dtype=float)
-    ctx = HipContext()
-    try:
-        ctx.set_data(data)
-        ctx.set_arch_from_weights(weights[0], n_features, actFun.device_kind(), capi.OUT_IDENTITY if kind is None else kind,
-                                  capi.LIK_NONE)
-        return ctx.predict_saliency([pack_weights(w) for w in weights], act_prm_sets=slopes, col_override=override,
-                                    apply_out_fn=kind is not None)
-    finally:
-        ctx.close()
-
-
-def _summary(samples, level):
-    """[F, n_out, 3] of samples [S, n_out, F]: the mean over the samples, then the equal-tailed quantiles"""
-    tail = 0.5 * (1.0 - level)
-    res = np.empty((samples.shape[2], samples.shape[1], 3))
-    res[:, :, 0] = samples.mean(axis=0).T
-    res[:, :, 1:] = np.moveaxis(np.quantile(samples, (tail, 1.0 - tail), axis=0), 0, -1).transpose(1, 0, 2)
-    return res
+    with net.on(data) as ctx:
+        packed, kw = net.sets()
+        return ctx.predict_saliency(packed, **kw)
 
 
 def get_saliency(data, size_output, actFun, output_act_fun, weights, alphas, data_transform, level=0.95):
@@ -69,8 +45,7 @@ def get_saliency(data, size_output, actFun, output_act_fun, weights, alphas, dat
     the last sample's stay installed on ``actFun``.  A column ``data_transform`` switches off has gradient 0.  ``ValueError``
     for no samples, a ``level`` outside (0, 1), a ``size_output`` that is not the network's, and a custom output callable
     (it has no device kind, so it cannot be differentiated)."""
-    if not 0.0 < level < 1.0:
-        raise ValueError("get_saliency: level must lie in (0, 1)")
+    check_level(level, "get_saliency")
     if len(weights) == 0:
         raise ValueError("get_saliency: no stored samples")
     if output_kind(output_act_fun) is None and output_act_fun is not None:
@@ -81,7 +56,8 @@ def get_saliency(data, size_output, actFun, output_act_fun, weights, alphas, dat
     if mean.shape[1] != size_output:
         raise ValueError("get_saliency: the network has %d outputs, size_output is %d" % (mean.shape[1], size_output))
     samples = {'mean_gradient': mean, 'saliency': absolute, 'rms_gradient': np.sqrt(sq)}
-    result = {k: _summary(v, level) for k, v in samples.items()}
+    # ([F, size_output, 3] of samples [S, size_output, F])
+    result = {k: np.ascontiguousarray(quantile_summary(v, level).transpose(1, 0, 2)) for k, v in samples.items()}
     result['samples'] = samples
     result['sign_probability'] = (mean > 0).mean(axis=0).T
     result['ranking'] = np.argsort(-result['saliency'][:, :, 0].sum(axis=1), kind="stable")
@@ -93,12 +69,6 @@ def saliency(pickle_file, which="train", level=0.95):
     test matrix (``"test"``)."""
     if which not in ("train", "test"):
         raise ValueError("saliency: which must be 'train' or 'test'")
-    model, _, logger = load_obj(pickle_file)
-    samples = logger._post_weight_samples
-    weights = [s['weights'] for s in samples]
-    alphas = [s['alphas'] for s in samples]
-    transform = None
-    if model._feature_indicators is not None:
-        transform = data_transform_obj(model._feature_indicators, model._feature_means)
+    model, weights, alphas, transform = checkpoint_samples(load_obj(pickle_file))
     data = np.asarray(model._data if which == "train" else model._test_data, dtype=np.float64)
     return get_saliency(data, model._size_output, model._act_fun, model._output_act_fun, weights, alphas, transform, level=level)

@@ -17,40 +17,22 @@ import numpy as np
 from . import _capi as capi
 from .files import load_obj
 from .layers import output_kind
-from .model import data_transform_obj
+from .stored import Network, check_level, checkpoint_samples, quantile_summary
 
 
 def _shapley_device(data, rows, background_data, bg_rows, player_of, perms, weights, alphas, actFun, output_act_fun, data_transform,
                     want_phi):
     """``HipContext.predict_shapley``'s dict for the rows ``rows`` of ``data`` against the rows ``bg_rows`` of
     ``background_data`` (None: of ``data``), the tables as the device holds them (the device seam)."""
-    from .backend import HipContext, pack_weights
-    data = np.ascontiguousarray(data, dtype=np.float64)
-    n_features = data.shape[1]
-    kind = output_kind(output_act_fun)
-    if kind is None and output_act_fun is not None:
+    net = Network(weights, alphas, actFun, output_act_fun, data_transform)
+    if net.custom_output:
         raise ValueError("get_shapley: a custom output callable has no device kind")
-    slopes = None
-    if actFun._function == "genReLU":
-        n_hidden = len(weights[0]) - 1
-        slopes = [np.asarray(a, dtype=float).ravel()[:n_hidden] for a in alphas]
-    override = None if data_transform is None else np.asarray(data_transform.column_override(), dtype=float)
-    ctx = HipContext()
-    try:
-        which = which_bg = capi.TRAIN
-        if background_data is None:
-            ctx.set_data(data)
-        else:
-            ctx.set_data(np.ascontiguousarray(background_data, dtype=np.float64))
-            ctx.set_data(data, capi.TEST)
-            which = capi.TEST
-        ctx.set_arch_from_weights(weights[0], n_features, actFun.device_kind(), capi.OUT_IDENTITY if kind is None else kind,
-                                  capi.LIK_NONE)
-        return ctx.predict_shapley([pack_weights(w) for w in weights], rows, bg_rows, perms, player_of=player_of, act_prm_sets=slopes,
-                                   col_override=override, which=which, which_bg=which_bg, apply_out_fn=kind is not None,
-                                   want_phi=want_phi)
-    finally:
-        ctx.close()
+    # (the backgrounds come from the training table: with a table of their own, the explained rows are the test table's)
+    tables, which = ((data, None), capi.TRAIN) if background_data is None else ((background_data, data), capi.TEST)
+    with net.on(*tables) as ctx:
+        packed, kw = net.sets()
+        return ctx.predict_shapley(packed, rows, bg_rows, perms, player_of=player_of, which=which, which_bg=capi.TRAIN,
+                                   want_phi=want_phi, **kw)
 
 
 def _players(n_features, feature_indx_list):
@@ -71,15 +53,6 @@ def _players(n_features, feature_indx_list):
         player_of[j] = len(groups)
         groups.append([int(j)])
     return groups, player_of
-
-
-def _quantile_summary(samples, level):
-    """[..., 3] of samples [S, ...]: the mean over the samples, then the equal-tailed quantiles"""
-    tail = 0.5 * (1.0 - level)
-    res = np.empty(samples.shape[1:] + (3,))
-    res[..., 0] = samples.mean(axis=0)
-    res[..., 1:] = np.moveaxis(np.quantile(samples, (tail, 1.0 - tail), axis=0), 0, -1)
-    return res
 
 
 def get_shapley(data, size_output, actFun, output_act_fun, weights, alphas, data_transform, rows=None, background=100,
@@ -111,8 +84,7 @@ def get_shapley(data, size_output, actFun, output_act_fun, weights, alphas, data
     ``alphas``; the last sample's stay installed on ``actFun``.  A player whose columns ``data_transform`` switches off is 0.
     ``ValueError`` for no samples, a ``level`` outside (0, 1), a ``size_output`` that is not the network's, a custom output
     callable, ``n_perm`` below 1 or odd with ``antithetic``, no rows, an empty background, and overlapping groups."""
-    if not 0.0 < level < 1.0:
-        raise ValueError("get_shapley: level must lie in (0, 1)")
+    check_level(level, "get_shapley")
     if len(weights) == 0:
         raise ValueError("get_shapley: no stored samples")
     if output_kind(output_act_fun) is None and output_act_fun is not None:
@@ -149,13 +121,13 @@ def get_shapley(data, size_output, actFun, output_act_fun, weights, alphas, data
                           bool(return_samples))
     mean, sq, absolute, fx, base = (np.asarray(dev[k], dtype=np.float64) for k in ("mean", "sq", "abs", "fx", "base"))
     if return_samples:
-        attributions = _quantile_summary(np.asarray(dev["phi"], dtype=np.float64), level)
+        attributions = quantile_summary(np.asarray(dev["phi"], dtype=np.float64), level)
     else:
         z = NormalDist().inv_cdf(1.0 - 0.5 * (1.0 - level))
         sd = np.sqrt(np.maximum(sq - mean * mean, 0.0))
         attributions = np.stack([mean, mean - z * sd, mean + z * sd], axis=-1)
     result = {'attributions': attributions, 'prediction': fx.mean(axis=0), 'base_value': base.mean(axis=0),
-              'importance': _quantile_summary(absolute, level), 'players': players, 'permutations': perms, 'background_rows': bg_rows}
+              'importance': quantile_summary(absolute, level), 'players': players, 'permutations': perms, 'background_rows': bg_rows}
     result['ranking'] = np.argsort(-result['importance'][:, :, 0].sum(axis=1), kind="stable")
     if return_samples:
         result['samples'] = {'attributions': np.asarray(dev["phi"], dtype=np.float64), 'prediction': fx, 'base_value': base,
@@ -169,13 +141,7 @@ def shapley(pickle_file, which="test", **kw):
     from ``rows`` on."""
     if which not in ("train", "test"):
         raise ValueError("shapley: which must be 'train' or 'test'")
-    model, _, logger = load_obj(pickle_file)
-    samples = logger._post_weight_samples
-    weights = [s['weights'] for s in samples]
-    alphas = [s['alphas'] for s in samples]
-    transform = None
-    if model._feature_indicators is not None:
-        transform = data_transform_obj(model._feature_indicators, model._feature_means)
+    model, weights, alphas, transform = checkpoint_samples(load_obj(pickle_file))
     train = np.asarray(model._data, dtype=np.float64)
     data = train if which == "train" else np.asarray(model._test_data, dtype=np.float64)
     kw.setdefault("background_data", None if which == "train" else train)

@@ -1,7 +1,86 @@
-"""What the stored-sample drivers (``get_posterior_lppd``, ``_uncertainty``, ``_calibration``, ``_convergence``, in part ``_hpd`` and
-``_threshold``) share on the host: reading a loaded checkpoint, choosing the table, validating labels, targets and per-sample sigmas, and
-opening the predictor.  A leaf module: nothing here needs the device, and every error carries the caller's name (``who``)."""
+"""What the stored-sample drivers share on the host.  The statistics (``get_posterior_lppd``, ``_uncertainty``, ``_calibration``,
+``_convergence``, in part ``_hpd`` and ``_threshold``): reading a loaded checkpoint, choosing the table, validating labels, targets and
+per-sample sigmas, and opening the predictor.  The attributions (``get_pdp``, ``get_ale``, ``get_saliency``, ``get_shapley``) and the
+predictor itself: one description of the samples' network as the device takes it (``Network``), with the context it opens on a table,
+the samples of a loaded checkpoint, and the summary over the samples.  A leaf module: the backend is imported inside functions only,
+and every error carries the caller's name (``who``)."""
+import contextlib
+
 import numpy as np
+
+from . import _capi as capi
+from .layers import output_kind
+
+
+class Network:
+    """The network of the stored samples ``weights`` (a per-layer list each) as the library is told of it: ``out_kind`` (OUT_*,
+    identity for no output function and for a custom callable), ``apply_out_fn``, ``custom_output`` (a callable without a device
+    kind: the device returns the last layer's values and the callable runs on the host), ``slopes`` (genReLU: every sample's
+    ``alphas`` cut to the hidden layers; else None) and ``override`` (``data_transform``'s columns, or None without one: to the
+    library a missing override and one of NaN alone are the same)."""
+
+    def __init__(self, weights, alphas, actFun, output_act_fun, data_transform=None):
+        kind = output_kind(output_act_fun)
+        self.weights, self.act_kind = weights, actFun.device_kind()
+        self.out_kind = capi.OUT_IDENTITY if kind is None else kind
+        self.apply_out_fn = kind is not None
+        self.custom_output = kind is None and output_act_fun is not None
+        self.slopes = None
+        if actFun._function == "genReLU":
+            n_hidden = len(weights[0]) - 1
+            self.slopes = [np.asarray(a, dtype=float).ravel()[:n_hidden] for a in alphas]
+        self.override = None if data_transform is None else np.asarray(data_transform.column_override(), dtype=float)
+
+    def sets(self):
+        """what every ``HipContext.predict_*`` entry of the attributions takes: the packed samples and their keywords"""
+        from .backend import pack_weights
+        return [pack_weights(w) for w in self.weights], dict(act_prm_sets=self.slopes, col_override=self.override,
+                                                             apply_out_fn=self.apply_out_fn)
+
+    def describe_to(self, ctx, n_features):
+        ctx.set_arch_from_weights(self.weights[0], n_features, self.act_kind, self.out_kind, capi.LIK_NONE)
+
+    @contextlib.contextmanager
+    def on(self, data, test_data=None):
+        """A ``HipContext`` that holds ``data`` as its training table (and ``test_data`` as its test table), both as contiguous
+        float64, and this network; closed on the way out."""
+        from .backend import HipContext
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        ctx = HipContext()
+        try:
+            ctx.set_data(data)
+            if test_data is not None:
+                ctx.set_data(np.ascontiguousarray(test_data, dtype=np.float64), capi.TEST)
+            self.describe_to(ctx, data.shape[1])
+            yield ctx
+        finally:
+            ctx.close()
+
+
+def checkpoint_samples(checkpoint):
+    """(model, the samples' weights, their alphas, the model's feature indicators as a ``data_transform_obj`` or None) of a loaded
+    checkpoint ``[bnn, mcmc, logger]`` (the driver loads it through its own ``load_obj``)."""
+    from .model import data_transform_obj
+    model, _, logger = checkpoint
+    samples = logger._post_weight_samples
+    transform = None
+    if model._feature_indicators is not None:
+        transform = data_transform_obj(model._feature_indicators, model._feature_means)
+    return model, [s['weights'] for s in samples], [s['alphas'] for s in samples], transform
+
+
+def check_level(level, who):
+    if not 0.0 < level < 1.0:
+        raise ValueError("%s: level must lie in (0, 1)" % who)
+
+
+def quantile_summary(samples, level):
+    """[..., 3] of samples [S, ...]: the mean over the samples, then the equal-tailed quantiles"""
+    tail = 0.5 * (1.0 - level)
+    res = np.empty(samples.shape[1:] + (3,))
+    res[..., 0] = samples.mean(axis=0)
+    res[..., 1:] = np.moveaxis(np.quantile(samples, (tail, 1.0 - tail), axis=0), 0, -1)
+    return res
 
 
 def class_labels(labels, n_rows, n_classes, who):

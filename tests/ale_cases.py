@@ -7,6 +7,7 @@ import numpy as np
 
 import oracle as orc
 import pdp_cases
+from attrib_common import _apply_override, seam_to_oracle
 
 OUT_FNS = pdp_cases.OUT_FNS
 
@@ -21,13 +22,6 @@ def bins_of(column, edges):
 def _predict(x, w, fun, slopes, trainable, out_fn):
     act = orc.Act(fun, prm=None if slopes is None else np.asarray(slopes, dtype=float), trainable=trainable)
     return out_fn(orc.forward_logits(x, w, act))
-
-
-def _apply_override(x, override):
-    if override is not None:
-        cols = ~np.isnan(override)
-        x[:, cols] = np.asarray(override)[cols]
-    return x
 
 
 def local_effects(x, focal, edges, weights, fun="tanh", out_fn=orc.out_softmax, slopes=None, override=None, trainable=False):
@@ -101,12 +95,8 @@ def curve(counts, effects):
 def oracle_seam(data, focal, edges, weights, alphas, actFun, output_act_fun, data_transform):
     """float64 stand-in for npbnn_amd.ale._ale_local_effects: every sample with its own slopes, the feature indicators after
     the edges."""
-    from npbnn_amd import _capi as capi
-    from npbnn_amd.layers import output_kind
-    out_fn = {capi.OUT_SOFTMAX: orc.out_softmax, capi.OUT_IDENTITY: orc.out_identity}[output_kind(output_act_fun)]
-    override = None if data_transform is None else np.asarray(data_transform.column_override(), dtype=float)
-    return local_effects(data, focal, edges, weights, fun=actFun._function, out_fn=out_fn,
-                         slopes=[np.asarray(a, dtype=float) for a in alphas], override=override)
+    fun, out, slopes, override = seam_to_oracle(alphas, actFun, output_act_fun, data_transform)
+    return local_effects(data, focal, edges, weights, fun=fun, out_fn=OUT_FNS[out], slopes=slopes, override=override)
 
 
 # ---- the cases of npbnn_predict_ale (tests/test_hip_ale.py on the GPU, tests/test_host_ale.py's guard) -----------------------------

@@ -6,6 +6,7 @@ import os
 import numpy as np
 
 import oracle as orc
+from attrib_common import _apply_override, seam_to_oracle
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pdp.npz")
 
@@ -36,18 +37,13 @@ def call_args(bn, case):
 def oracle_row_means(data, focal_features, grid, weights, alphas, actFun, output_act_fun, data_transform):
     """float64 stand-in for npbnn_amd.pdp._pdp_row_means: grid values, then the feature indicators, then every sample's forward pass
     with its own slopes."""
-    from npbnn_amd import _capi as capi
-    from npbnn_amd.layers import output_kind
-    kind = output_kind(output_act_fun)
-    out_fn = {capi.OUT_SOFTMAX: orc.out_softmax, capi.OUT_IDENTITY: orc.out_identity}[kind]
+    fun, out, slopes, override = seam_to_oracle(alphas, actFun, output_act_fun, data_transform)
     res = []
     for point in grid:
         x = np.array(data, dtype=np.float64, copy=True)
         x[:, focal_features] = point
-        if data_transform is not None:
-            x = data_transform.transform(x)
-        preds = [out_fn(orc.forward_logits(x, w, orc.Act(actFun._function, prm=np.asarray(a, dtype=float))))
-                 for w, a in zip(weights, alphas)]
+        x = _apply_override(x, override)
+        preds = [OUT_FNS[out](orc.forward_logits(x, w, orc.Act(fun, prm=a))) for w, a in zip(weights, slopes)]
         res.append(np.mean(preds, axis=0))
     return np.array(res)
 

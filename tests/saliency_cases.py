@@ -10,14 +10,11 @@ import numpy as np
 
 import oracle as orc
 import pdp_cases
+from attrib_common import _act, _apply_override, seam_to_oracle
 
 MARGIN = 1e-4            # about 75 times the largest device - float64 difference measured on these draws (1.3e-6, NOTES 8)
 MAX_REDRAWN = 0.03       # share of a case's rows that may be redrawn
 PIECEWISE = ("ReLU", "genReLU")
-
-
-def _act(fun, slopes, trainable):
-    return orc.Act(fun, prm=None if slopes is None else np.asarray(slopes, dtype=float), trainable=trainable)
 
 
 def _matrix(w, n_in):
@@ -36,14 +33,6 @@ def _act_derivative(z, act, layer_n):
         return s * (1 + z * (1 - s))
     t = orc.activate(np.array(z, copy=True), act, layer_n)
     return 1.0 - t * t
-
-
-def _apply_override(x, override):
-    x = np.array(x, dtype=np.float64, copy=True)
-    if override is not None:
-        cols = ~np.isnan(override)
-        x[:, cols] = np.asarray(override)[cols]
-    return x
 
 
 def hidden_preactivations(x, w, act):
@@ -119,12 +108,8 @@ def reference(case, inp, wrong=None):
 def oracle_seam(data, weights, alphas, actFun, output_act_fun, data_transform):
     """float64 stand-in for npbnn_amd.saliency._saliency_means: every sample with its own slopes, the feature indicators as
     an override."""
-    from npbnn_amd import _capi as capi
-    from npbnn_amd.layers import output_kind
-    out = {capi.OUT_SOFTMAX: "softmax", capi.OUT_IDENTITY: "identity"}[output_kind(output_act_fun)]
-    override = None if data_transform is None else np.asarray(data_transform.column_override(), dtype=float)
-    return means(np.asarray(data, dtype=np.float64), weights, fun=actFun._function, out=out,
-                 slopes=[np.asarray(a, dtype=float) for a in alphas], override=override)
+    fun, out, slopes, override = seam_to_oracle(alphas, actFun, output_act_fun, data_transform)
+    return means(np.asarray(data, dtype=np.float64), weights, fun=fun, out=out, slopes=slopes, override=override)
 
 
 # ---- the cases of npbnn_predict_saliency (tests/test_hip_saliency.py on the GPU, tests/test_host_saliency.py's guards) ---------------

@@ -17,6 +17,7 @@ import numpy as np
 
 import oracle as orc
 import pdp_cases
+from attrib_common import _act, _apply_override, seam_to_oracle
 
 # The error of an output array is max|device - float64| / max|float64| over the case.  Largest values measured on an MI355X over the
 # 143 runs of tests/test_hip_shapley.py's cases on both routes (NOTES 8.14):
@@ -32,20 +33,8 @@ TOL = 5e-5
 TOL_EFFICIENCY = 2e-5
 
 
-def _act(fun, slopes, trainable):
-    return orc.Act(fun, prm=None if slopes is None else np.asarray(slopes, dtype=float), trainable=trainable)
-
-
 def _out_fn(out, apply_out):
     return pdp_cases.OUT_FNS[out] if apply_out else orc.out_identity
-
-
-def _apply_override(x, override):
-    x = np.array(x, dtype=np.float64, copy=True)
-    if override is not None:
-        cols = ~np.isnan(override)
-        x[:, cols] = np.asarray(override)[cols]
-    return x
 
 
 def _from_z0(z0, w, act, out_fn):
@@ -157,16 +146,13 @@ def efficiency_gap(res):
 def oracle_seam(data, rows, background_data, bg_rows, player_of, perms, weights, alphas, actFun, output_act_fun, data_transform, want_phi):
     """float64 stand-in for npbnn_amd.shapley._shapley_device: every sample with its own slopes, the feature indicators as an
     override."""
-    from npbnn_amd import _capi as capi
-    from npbnn_amd.layers import output_kind
-    out = {capi.OUT_SOFTMAX: "softmax", capi.OUT_IDENTITY: "identity"}[output_kind(output_act_fun)]
-    override = None if data_transform is None else np.asarray(data_transform.column_override(), dtype=float)
+    fun, out, slopes, override = seam_to_oracle(alphas, actFun, output_act_fun, data_transform)
     data = np.asarray(data, dtype=np.float64)
     bg = data if background_data is None else np.asarray(background_data, dtype=np.float64)
     n_players = int(np.max(player_of)) + 1
     players = [np.flatnonzero(np.asarray(player_of) == p).tolist() for p in range(n_players)]
-    res = outputs(*walks(data[np.asarray(rows)], bg[np.asarray(bg_rows)], weights, np.asarray(perms), players, fun=actFun._function, out=out,
-                         slopes=[np.asarray(a, dtype=float) for a in alphas], override=override))
+    res = outputs(*walks(data[np.asarray(rows)], bg[np.asarray(bg_rows)], weights, np.asarray(perms), players, fun=fun, out=out,
+                         slopes=slopes, override=override))
     if not want_phi:
         res["phi"] = None
     return res

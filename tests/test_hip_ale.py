@@ -12,6 +12,7 @@ import pytest
 
 import ale_cases
 import npbnn_amd as bn
+from attrib_common import softmax_np
 from npbnn_amd import _capi as capi
 from test_hip_pdp import TOL
 
@@ -166,6 +167,38 @@ def test_get_ale_curve(per_edge, monkeypatch):
     assert np.abs(res["ale"][:, :, 0] - curve_want.mean(axis=0)).max() <= 2 * bars[-1]
     tail = np.quantile(curve_want, (0.025, 0.975), axis=0)
     assert np.abs(res["ale"][:, :, 1] - tail[0]).max() <= 2 * bars[-1] and np.abs(res["ale"][:, :, 2] - tail[1]).max() <= 2 * bars[-1]
+
+
+def test_get_ale_with_a_custom_output_callable():
+    """A softmax the package does not know has no device kind: get_ale runs one pass per (edge, sample) for the last layer's values
+    and takes the callable, the bins and the means on the host.  The table, samples and quantile edges of ``bins_2`` - the smallest
+    case with more than one bin - cut to 257 rows (one past a block), 5 features, one hidden layer of 4 and 3 outputs, genReLU with
+    a slope per sample: against the float64 restatement on the table the device holds, and against the same call with bn.SoftMax,
+    whose softmax runs on the device."""
+    case = dict(ale_cases.CASES["bins_2"], rows=257, features=5, nodes=(4,), n_out=3, sets=2, fun="genReLU", slopes="per_set")
+    inp = ale_cases.inputs(case)
+    assert inp["x"].shape == (257, 5) and len(inp["edges"]) == 3 and not np.array_equal(*inp["slopes"])
+
+    def call(out_fn):
+        return bn.get_ale(inp["x"], [inp["column"]], "classification", 3, bn.ActFun(fun="genReLU"), out_fn, inp["weights"], inp["slopes"],
+                          None, n_bins=case["bins"])
+
+    res, same = call(softmax_np), call(bn.SoftMax)
+    assert np.array_equal(res["feature"], inp["edges"]) and np.array_equal(same["feature"], inp["edges"])
+    held = inp["x"].astype(np.float32).astype(np.float64)
+    counts, effects = ale_cases.local_effects(held, inp["column"], inp["edges"], inp["weights"], fun="genReLU", out_fn=softmax_np,
+                                              slopes=inp["slopes"])
+    curve = ale_cases.curve(counts, effects)
+    want = dict(local_effects=effects, ale_samples=curve,
+                ale=np.stack([curve.mean(axis=0)] + list(np.quantile(curve, (0.025, 0.975), axis=0)), axis=-1))
+    assert np.array_equal(res["counts"], counts) and np.array_equal(same["counts"], counts) and counts.min() > 0
+    assert np.abs(effects).max() > 100 * TOL
+    for key in ("local_effects", "ale_samples", "ale"):
+        print("\nale custom callable, %-13s: max|host branch - float64| %.3e, max|host branch - device softmax| %.3e (bar %.1e)"
+              % (key, np.abs(res[key] - want[key]).max(), np.abs(res[key] - same[key]).max(), TOL))
+    for key in ("local_effects", "ale_samples", "ale"):
+        assert res[key].shape == want[key].shape
+        assert np.abs(res[key] - want[key]).max() <= TOL and np.abs(res[key] - same[key]).max() <= TOL, key
 
 
 def test_ale_of_a_checkpoint(tmp_path):

@@ -9,6 +9,7 @@ import pytest
 import npbnn_amd as bn
 import oracle as orc
 import pdp_cases
+from attrib_common import softmax_np
 from npbnn_amd import _capi as capi
 
 pytestmark = pytest.mark.gpu
@@ -127,6 +128,30 @@ def test_more_sets_than_a_pass_with_their_own_slopes(per_grid, n_nodes, monkeypa
     y, route = device_means(x, weights, [5], grid, fun="genReLU", slopes=slopes)
     assert route == (2 if per_grid else 1)
     np.testing.assert_allclose(y, oracle_means(x, weights, [5], grid, fun="genReLU", slopes=slopes), rtol=0, atol=TOL)
+
+
+def test_get_pdp_with_a_custom_output_callable():
+    """A softmax the package does not know has no device kind: get_pdp runs one pass per (grid point, sample) for the last layer's
+    values and applies the callable on the host.  257 rows (one past a block), genReLU with a slope per sample, an ordinal focal
+    column of three levels: against the float64 restatement on the table the device holds, and against the same call with
+    bn.SoftMax, whose softmax runs on the device."""
+    x, weights = _drawn(257, 5, (4,), 3, 2, seed=21)
+    x[:, 1] = np.random.default_rng(22).integers(0, 3, 257)
+    slopes = [np.array([0.1]), np.array([0.35])]
+
+    def call(out_fn):
+        return bn.get_pdp(x, [1], "classification", 3, bn.ActFun(fun="genReLU"), out_fn, weights, slopes, None)
+
+    res, same = call(softmax_np), call(bn.SoftMax)
+    assert res["feature"].shape == (3, 1) and np.array_equal(res["feature"], same["feature"]) and res["pdp"].shape == (3, 3, 3)
+    held = x.astype(np.float32).astype(np.float64)
+    means = np.cumsum(oracle_means(held, weights, [1], res["feature"], fun="genReLU", out_fn=softmax_np, slopes=slopes), axis=2)
+    want = np.stack([means.mean(axis=1)] + list(np.quantile(means, (0.025, 0.975), axis=1)), axis=-1)
+    print("\npdp custom callable: max|host branch - float64| %.3e, max|host branch - device softmax| %.3e (bar %.1e)"
+          % (np.abs(res["pdp"] - want).max(), np.abs(res["pdp"] - same["pdp"]).max(), TOL))
+    assert np.ptp(want[:, :, 0], axis=0).max() > 100 * TOL
+    np.testing.assert_allclose(res["pdp"], want, rtol=0, atol=TOL)
+    np.testing.assert_allclose(res["pdp"], same["pdp"], rtol=0, atol=TOL)
 
 
 def test_pdp_of_a_checkpoint(tmp_path):

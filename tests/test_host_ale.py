@@ -13,6 +13,7 @@ import ale_cases
 import npbnn_amd as bn
 import oracle as orc
 import pdp_cases
+from attrib_common import fake_checkpoint
 from npbnn_amd import _capi as capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -196,20 +197,14 @@ def test_get_ale_refuses_two_columns_and_bad_levels(oracle_seam):
         bn.get_ale(*args, level=1.0)
 
 
-class _Holder:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
 def test_ale_reads_checkpoint(oracle_seam, monkeypatch):
     """ale(pickle_file, columns): the model's training matrix, activation and output function, the logger's samples and the model's
     feature indicators go into get_ale, one result per column."""
     c = FIXTURE["indicators"]
-    x, focal, mode, n_out, act, out_fn, weights, alphas, transform = pdp_cases.call_args(bn, c)
-    model = _Holder(_data=x, _estimation_mode=mode, _size_output=n_out, _act_fun=act, _output_act_fun=out_fn,
-                    _feature_indicators=c["indicators"], _feature_means=c["means"])
-    logger = _Holder(_post_weight_samples=[{"weights": w, "alphas": a} for w, a in zip(weights, alphas)])
-    monkeypatch.setattr(ALE_MOD, "load_obj", lambda path: [model, None, logger])
+    args = pdp_cases.call_args(bn, c)
+    x, focal, mode, n_out, act, out_fn, weights, alphas, transform = args
+    checkpoint = fake_checkpoint(args, c)
+    monkeypatch.setattr(ALE_MOD, "load_obj", lambda path: checkpoint)
     on = int(np.flatnonzero(np.asarray(c["indicators"]) != 0)[0])
     res = bn.ale("checkpoint.pkl", [[focal[0]], on], n_bins=9)
     assert len(res) == 2

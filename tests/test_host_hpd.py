@@ -11,6 +11,7 @@ import pytest
 import hpd_cases
 import npbnn_amd as bn
 import oracle as orc
+from attrib_common import _Holder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = hpd_cases.load()
@@ -86,11 +87,6 @@ def test_public_names_and_header():
 
 
 # ---- get_posterior_hpd on a checkpoint, the device seam replaced
-
-class _Holder:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
 
 def _checkpoint(fun="tanh", n_samples=9, n_out=3, classification=True, seed=0, n_rows=37, n_test=11):
     rs = np.random.default_rng(seed)

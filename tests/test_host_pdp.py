@@ -7,6 +7,7 @@ import pytest
 
 import npbnn_amd as bn
 import pdp_cases
+from attrib_common import fake_checkpoint
 
 CASES = pdp_cases.load()
 
@@ -48,21 +49,15 @@ def test_switched_off_focal_column_is_flat(oracle_seam):
     assert np.ptp(res["pdp"][:, :, 0], axis=0).max() < 1e-12
 
 
-class _Holder:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
 def test_pdp_reads_checkpoint(oracle_seam, monkeypatch):
     """pdp(pickle_file, lists): the model's training matrix, mode, outputs, activation and output function, the logger's samples and
     the model's feature indicators go into get_pdp, one result per list."""
     pdp_mod = importlib.import_module("npbnn_amd.pdp")
     c = CASES["indicators"]
-    x, focal, mode, n_out, act, out_fn, weights, alphas, _ = pdp_cases.call_args(bn, c)
-    model = _Holder(_data=x, _estimation_mode=mode, _size_output=n_out, _act_fun=act, _output_act_fun=out_fn,
-                    _feature_indicators=c["indicators"], _feature_means=c["means"])
-    logger = _Holder(_post_weight_samples=[{"weights": w, "alphas": a} for w, a in zip(weights, alphas)])
-    monkeypatch.setattr(pdp_mod, "load_obj", lambda path: [model, None, logger])
+    args = pdp_cases.call_args(bn, c)
+    focal, n_out = args[1], args[3]
+    checkpoint = fake_checkpoint(args, c)
+    monkeypatch.setattr(pdp_mod, "load_obj", lambda path: checkpoint)
     other = CASES["onehot"]
     res = bn.pdp("checkpoint.pkl", [focal, [4, 5, 6]])
     assert len(res) == 2

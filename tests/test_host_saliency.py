@@ -13,6 +13,7 @@ import npbnn_amd as bn
 import oracle as orc
 import pdp_cases
 import saliency_cases as sc
+from attrib_common import fake_checkpoint
 from npbnn_amd import _capi as capi
 from test_hip_pdp import TOL
 
@@ -169,21 +170,15 @@ def test_get_saliency_refusals(oracle_seam):
         bn.get_saliency(args[0], args[1], args[2], lambda z: z * z, *args[4:])
 
 
-class _Holder:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
 def test_saliency_reads_checkpoint(oracle_seam, monkeypatch):
     """saliency(pickle_file): the model's matrices, activation and output function, the logger's samples and the model's feature
     indicators go into get_saliency."""
     c = FIXTURE["indicators"]
-    x, _, mode, n_out, act, out_fn, weights, alphas, transform = pdp_cases.call_args(bn, c)
+    args = pdp_cases.call_args(bn, c)
+    x, _, mode, n_out, act, out_fn, weights, alphas, transform = args
     x_test = x[::3] + 0.25
-    model = _Holder(_data=x, _test_data=x_test, _estimation_mode=mode, _size_output=n_out, _act_fun=act, _output_act_fun=out_fn,
-                    _feature_indicators=c["indicators"], _feature_means=c["means"])
-    logger = _Holder(_post_weight_samples=[{"weights": w, "alphas": a} for w, a in zip(weights, alphas)])
-    monkeypatch.setattr(SAL_MOD, "load_obj", lambda path: [model, None, logger])
+    checkpoint = fake_checkpoint(args, c, _test_data=x_test)
+    monkeypatch.setattr(SAL_MOD, "load_obj", lambda path: checkpoint)
     off = np.asarray(c["indicators"]) == 0
     assert off.any() and not off.all()
     res = bn.saliency("checkpoint.pkl")

@@ -1,4 +1,4 @@
-"""The shared preparation behind the stored-sample entries and the grouped chain calls, on the host (no GPU): every one of the nine
+"""The shared preparation behind the stored-sample entries and the grouped chain calls, on the host (no GPU): every one of the twelve
 ``HipContext`` entries that take ``weight_sets`` refuses a wrong number of slope vectors and an empty list of sets before the library
 is touched, the three input forms pack to the same bytes, the one ``ChainJob`` builder fills the struct both grouped calls hand over,
 and ``sigma_matrix`` has its two levels of strictness.  (The bare context is the pattern of test_host_lppd._bare_context.)"""
@@ -49,6 +49,9 @@ ENTRIES = {
     "predict_sets_calibration": lambda ctx, sets, ap: ctx.predict_sets_calibration(sets, act_prm_sets=ap),
     "predict_sets_convergence": lambda ctx, sets, ap: ctx.predict_sets_convergence(sets, 2, act_prm_sets=ap),
     "predict_pdp": lambda ctx, sets, ap: ctx.predict_pdp(sets, [0], [[0.0]], act_prm_sets=ap),
+    "predict_ale": lambda ctx, sets, ap: ctx.predict_ale(sets, 0, [0.0, 1.0], act_prm_sets=ap),
+    "predict_saliency": lambda ctx, sets, ap: ctx.predict_saliency(sets, act_prm_sets=ap),
+    "predict_shapley": lambda ctx, sets, ap: ctx.predict_shapley(sets, [0], [1], [[0, 1]], act_prm_sets=ap),
 }
 
 
@@ -65,7 +68,7 @@ def test_slope_vectors_must_match_the_sets(entry, n_slopes):
 
 @pytest.mark.parametrize("entry", ENTRIES)
 def test_no_weight_sets(entry):
-    """All nine entries: no test expects the library's answer to an empty list through one of them, so none is left out."""
+    """All twelve entries: no test expects the library's answer to an empty list through one of them, so none is left out."""
     _NoDevice.touched = []
     for sets in ([], np.zeros((0, N_W))):
         with pytest.raises(ValueError, match="%s: no weight sets" % entry):

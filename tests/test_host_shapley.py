@@ -14,6 +14,7 @@ import pytest
 import npbnn_amd as bn
 import pdp_cases
 import shapley_cases as sh
+from attrib_common import fake_checkpoint
 from npbnn_amd import _capi as capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -220,21 +221,15 @@ def test_get_shapley_refusals(oracle_seam):
         bn.get_shapley(*args, rows=[0], background=[args[0].shape[0]], n_perm=2)
 
 
-class _Holder:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
 def test_shapley_reads_checkpoint(oracle_seam, monkeypatch):
     """shapley(pickle_file): the model's matrices, activation and output function, the logger's samples and the model's feature
     indicators go into get_shapley; the test matrix is explained against the training matrix."""
     c = FIXTURE["indicators"]
-    x, _, mode, n_out, act, out_fn, weights, alphas, transform = pdp_cases.call_args(bn, c)
+    args = pdp_cases.call_args(bn, c)
+    x, _, mode, n_out, act, out_fn, weights, alphas, transform = args
     x_test = x[::3] + 0.25
-    model = _Holder(_data=x, _test_data=x_test, _estimation_mode=mode, _size_output=n_out, _act_fun=act, _output_act_fun=out_fn,
-                    _feature_indicators=c["indicators"], _feature_means=c["means"])
-    logger = _Holder(_post_weight_samples=[{"weights": w, "alphas": a} for w, a in zip(weights, alphas)])
-    monkeypatch.setattr(SHAP_MOD, "load_obj", lambda path: [model, None, logger])
+    checkpoint = fake_checkpoint(args, c, _test_data=x_test)
+    monkeypatch.setattr(SHAP_MOD, "load_obj", lambda path: checkpoint)
     off = np.asarray(c["indicators"]) == 0
     assert off.any() and not off.all()
     kw = dict(rows=[0, 1, 2, 5], background=6, n_perm=4)
