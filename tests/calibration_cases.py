@@ -44,6 +44,19 @@ PARAMS = {
 }
 CASES = uc.CASES
 assert sorted(PARAMS) == sorted(CASES)
+# name -> dict(kind, n_bins, levels): the cases of another table (fold_envelope_cases) that go through this module's helpers
+EXTRA = {}
+
+
+def register(name, kind, n_bins, levels):
+    """A case of another table under the helpers here that take a case by name (``params``, ``edges_of``, ``rows_near_an_edge``,
+    ``point_fields_of``, ``score_fields_of``): its kind in CASES' letters, its bins and its coverage levels."""
+    assert name not in CASES and name not in EXTRA, name
+    EXTRA[name] = dict(kind=kind, n_bins=n_bins, levels=tuple(levels))
+
+
+def _kind(name):
+    return (CASES[name] if name in CASES else EXTRA[name])["kind"]
 
 
 def key(name, field):
@@ -65,38 +78,40 @@ def fields_of(name):
 
 
 def point_fields_of(name):
-    return CLASS_POINT if CASES[name]["kind"] == "cat" else REGRESSION_POINT
+    return CLASS_POINT if _kind(name) == "cat" else REGRESSION_POINT
 
 
 def score_fields_of(name):
-    return CLASS_SCORES if CASES[name]["kind"] == "cat" else REGRESSION_SCORES
+    return CLASS_SCORES if _kind(name) == "cat" else REGRESSION_SCORES
 
 
 def params(name):
-    p = PARAMS[name]
+    p = PARAMS[name] if name in PARAMS else EXTRA[name]
     return p["n_bins"], tuple(p["levels"])
 
 
-def _error_targets(name, inp):
+def _error_targets(name, inp, spec=None, seed=None):
     """Targets of a ``"regression-error"`` case: the teacher of ``uncertainty_cases.inputs`` (its generator replayed to the same
-    draws), its mean plus its softplus sigma times seeded normal noise, as a float32 holds them."""
+    draws), its mean plus its softplus sigma times seeded normal noise, as a float32 holds them.  ``spec`` and ``seed``: as
+    ``uncertainty_cases.inputs`` takes them, for a case of another table; the noise is then seeded from ``seed + "/noise"``."""
     import oracle as orc
-    spec = uc.ERROR_CASES[name]
-    rs = np.random.default_rng(cases.hash_name("uncertainty/" + name) % (2 ** 31))
+    spec = uc.ERROR_CASES[name] if spec is None else spec
+    rs = np.random.default_rng(cases.hash_name("uncertainty/" + name if seed is None else seed) % (2 ** 31))
     x = rs.standard_normal((len(inp["x"]), N_FEATURES))
     assert np.array_equal(x, inp["x"])
     teacher = [rs.normal(0, 0.6, s) for s in cases.layer_shapes(N_FEATURES, list(spec["nodes"]), spec["n_out"], spec["bias"])]
     z = orc.forward_logits(x, teacher, orc.Act(spec["fun"], np.full(len(spec["nodes"]), 0.15)))
     t = spec["n_out"] // 2
-    noise = np.random.default_rng(cases.hash_name("calibration/" + name) % (2 ** 31)).standard_normal((len(x), t))
+    noise = np.random.default_rng(cases.hash_name("calibration/" + name if seed is None else seed + "/noise") % (2 ** 31)).standard_normal((len(x), t))
     return (z[:, :t] + np.logaddexp(0.0, z[:, t:]) * noise).astype(np.float32).astype(np.float64)
 
 
-def inputs(name, n_rows=N_ROWS):
-    """x, the stored samples, and labels (class indices) or targets [rows, T], with the case's description."""
-    inp = uc.inputs(name, n_rows)
-    if name in uc.ERROR_CASES:
-        inp = dict(inp, labels=_error_targets(name, inp))
+def inputs(name, n_rows=N_ROWS, spec=None, seed=None):
+    """x, the stored samples, and labels (class indices) or targets [rows, T], with the case's description.  ``spec`` and ``seed``:
+    as ``uncertainty_cases.inputs`` takes them, for a case of another table (fold_envelope_cases)."""
+    inp = uc.inputs(name, n_rows, spec, seed)
+    if inp["kind"] == "err":
+        inp = dict(inp, labels=_error_targets(name, inp, spec, seed))
     return inp
 
 
@@ -164,7 +179,7 @@ def edges_of(name):
     in the same bin), and for regression the coverage edges (1 +- level) / 2."""
     n_bins, levels = params(name)
     e = [j / n_bins for j in range(1, n_bins)]
-    if CASES[name]["kind"] != "cat":
+    if _kind(name) != "cat":
         e += [(1 - lv) / 2 for lv in levels] + [(1 + lv) / 2 for lv in levels]
     return np.array(e, dtype=np.float64)
 

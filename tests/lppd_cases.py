@@ -34,10 +34,12 @@ def key(name, field):
     return "%s/%s" % (name, field)
 
 
-def inputs(name, n_rows=N_ROWS):
-    """x, the stored samples (weights, alphas, and error_prm for regression), labels (class indices) or targets [rows, outputs]."""
-    spec = CASES[name]
-    rs = np.random.default_rng(cases.hash_name("lppd/" + name) % (2 ** 31))
+def inputs(name, n_rows=N_ROWS, spec=None, seed=None):
+    """x, the stored samples (weights, alphas, and error_prm for regression), labels (class indices) or targets [rows, outputs].
+    ``spec`` and ``seed``: a description in CASES' form and the string the generator is seeded from, for a case of another table
+    (fold_envelope_cases); a single class has no other class to flip a label to."""
+    spec = CASES[name] if spec is None else spec
+    rs = np.random.default_rng(cases.hash_name("lppd/" + name if seed is None else seed) % (2 ** 31))
     x = rs.standard_normal((n_rows, N_FEATURES))
     shapes = cases.layer_shapes(N_FEATURES, list(spec["nodes"]), spec["n_out"], spec["bias"])
     reg = spec["kind"] == "reg"
@@ -53,9 +55,10 @@ def inputs(name, n_rows=N_ROWS):
     import oracle as orc                                  # (the float64 oracle's forward pass: the teacher's output)
     z = orc.forward_logits(x, teacher, orc.Act(spec["fun"], np.full(len(spec["nodes"]), 0.15)))
     if spec["kind"] == "cat":
-        labels = np.argmax(z, axis=1)
-        flip = rs.random(n_rows) < 0.1
-        labels = np.where(flip, (labels + rs.integers(1, spec["n_out"], n_rows)) % spec["n_out"], labels).astype(np.int64)
+        labels = np.argmax(z, axis=1).astype(np.int64)
+        if spec["n_out"] > 1:
+            flip = rs.random(n_rows) < 0.1
+            labels = np.where(flip, (labels + rs.integers(1, spec["n_out"], n_rows)) % spec["n_out"], labels).astype(np.int64)
     else:
         # (targets a float32 holds exactly: the device keeps them in float32, and the cases are about the likelihood, not that rounding)
         labels = (z + 0.7 * rs.standard_normal(z.shape)).astype(np.float32).astype(np.float64)

@@ -42,12 +42,14 @@ def fields_of(name):
     return CLASS_FIELDS if CASES[name]["kind"] == "cat" else REGRESSION_FIELDS
 
 
-def inputs(name, n_rows=N_ROWS):
-    """x and the stored samples (weights, alphas, and error_prm for ``"regression"``), with the case's description."""
-    if name in lc.CASES:
-        return lc.inputs(name, n_rows)
-    spec = ERROR_CASES[name]
-    rs = np.random.default_rng(cases.hash_name("uncertainty/" + name) % (2 ** 31))
+def inputs(name, n_rows=N_ROWS, spec=None, seed=None):
+    """x and the stored samples (weights, alphas, and error_prm for ``"regression"``), with the case's description.  ``spec`` and
+    ``seed``: a description in ERROR_CASES' or lppd_cases.CASES' form and the string the generator is seeded from, for a case of
+    another table (fold_envelope_cases)."""
+    if (name in lc.CASES) if spec is None else (spec["kind"] != "err"):
+        return lc.inputs(name, n_rows, spec, seed)
+    spec = ERROR_CASES[name] if spec is None else spec
+    rs = np.random.default_rng(cases.hash_name("uncertainty/" + name if seed is None else seed) % (2 ** 31))
     x = rs.standard_normal((n_rows, N_FEATURES))
     shapes = cases.layer_shapes(N_FEATURES, list(spec["nodes"]), spec["n_out"], spec["bias"])
     teacher = [rs.normal(0, 0.6, s) for s in shapes]
