@@ -519,6 +519,39 @@ int npbnn_predict_sets_convergence(npbnn_ctx* ctx, const double* W_sets, const d
                                    int which, int apply_out_fn, double rhat_threshold, double* out_rhat, double* out_ess,
                                    double* out_summary);
 
+/* The posterior predictive distribution of the n_sets stored samples on the resident matrix `which`, per (row, target): its quantiles,
+ * its mean and its continuous ranked probability score against targets given in the call.  The reference has no such function: its
+ * summary code takes calcHPD of the predicted means (np_bnn/BNN_plot.py:73-75), an interval that leaves the noise term out.  The
+ * predictive distribution of a cell is the mixture (1/S) sum_s N(mu_s, sigma_s^2), S = n_sets; npbnn_op_mixture (below) has the
+ * definitions.  The kind follows the output function of ctx's architecture:
+ *   NPBNN_OUT_IDENTITY       T = out_dim, mu_s = the set's prediction, sigma_s = sigma_sets[s][t]; sigma_sets [n_sets][T] is required,
+ *                            every entry positive and finite (the per-sample sigma of the Gaussian likelihood)
+ *   NPBNN_OUT_SOFTPLUS_HALF  out_dim = 2 T, the sets replay with the output function applied: a row of a set's predictions holds T
+ *                            means followed by T sigmas (RegressTransformError, np_bnn/BNN_lib.py:177); sigma_sets must be NULL
+ * and every other kind is refused.  The sets replay as in npbnn_predict_sets_hpd into a float32 device stack [n_sets][n_rows][out_dim]
+ * that never leaves the device, under the same byte budget (1 GiB; NPBNN_HPD_STACK_BYTES in the environment overrides it;
+ * NPBNN_E_NOMEM names the largest row count that fits); the kernels read mu and sigma where they lie in it and widen them to float64:
+ * the results are the definitions' values on the float64 array npbnn_predict_sets returns.
+ *   probs [n_probs]      n_probs in 0..16, each with min(p, 1 - p) >= 1e-12, in any order
+ *   targets              [n_rows][T] float64, or NULL (out_crps and out_totals are then NULL too); passed here and not taken from
+ *                        npbnn_set_targets_f64, which keeps float32.  Given, at least one of out_crps and out_totals is.
+ *   out_quantile         [n_probs][n_rows][T]; NULL exactly when n_probs == 0
+ *   out_mean             [n_rows][T], or NULL
+ *   out_crps             [n_rows][T], or NULL
+ *   out_totals           [T], or NULL: the sum of crps over the rows per target, made of per-workgroup float64 partials added in a
+ *                        fixed order
+ * The bits of a cell's result depend on its S values alone, and the grids on n_rows and T: two calls return the same bits however the
+ * replay groups the sets.  The CRPS costs S (S - 1) / 2 pair terms per cell.  NPBNN_E_ARG before any launch: NULL W_sets, n_sets < 1 or
+ * above 16384, more than 16 probabilities or one out of range, probs / out_quantile that do not go together, nothing asked for,
+ * out_crps or out_totals without targets or targets without either, a target that is NaN or infinite, `which` not 0 or 1, an output
+ * kind other than the two, an odd out_dim under NPBNN_OUT_SOFTPLUS_HALF, sigma_sets missing, non-positive or non-finite under
+ * NPBNN_OUT_IDENTITY or given under NPBNN_OUT_SOFTPLUS_HALF; NPBNN_E_STATE without npbnn_set_arch or without data on `which`.
+ * NPBNN_E_ARG after the passes: a prediction that is NaN or infinite, or a predicted sigma that is not positive and finite - a
+ * softplus that underflowed to 0 in float32 is a refusal, not a division.  A refused call leaves the outputs untouched. */
+int npbnn_predict_sets_predictive(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which,
+                                  const double* sigma_sets, const double* probs, int32_t n_probs, const double* targets,
+                                  double* out_quantile, double* out_mean, double* out_crps, double* out_totals);
+
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events
  * around each launch) and of the whole evaluation, in milliseconds. */
@@ -718,6 +751,33 @@ int npbnn_op_hpd(int device, const void* values, int value_type, int64_t n_sampl
  * has rhat = ess = NaN; this is not an error.  NPBNN_E_ARG: the limits above, or a value that is NaN or infinite. */
 int npbnn_op_convergence(int device, const void* values, int value_type, int32_t n_chains, int32_t n_draws, int64_t n_cols,
                          int64_t col_stride, double* out_rhat, double* out_ess);
+
+/* npbnn_op_mixture: quantiles, mean and continuous ranked probability score of n_cols Gaussian mixtures.  Cell c has n_samples = S
+ * components, 1 <= S <= 16384, mu_s at mu[s * col_stride + c] (value_type NPBNN_VALUE_F64 or NPBNN_VALUE_F32) and sigma_s
+ *   sigma_cols == 0       at sigma[s * col_stride + c], sigma of mu's type and layout
+ *   sigma_cols == T >= 1  at sigma[s * T + c % T], sigma float64 [n_samples][T]: the per-sample sigma of the Gaussian likelihood
+ * every mu finite and every sigma positive and finite.  All arithmetic is float64:
+ *   F(x)       = (1/S) sum_s Phi((x - mu_s) / sigma_s),  Phi(u) = 0.5 erfc(-u / sqrt 2)
+ *   quantile_p = the x with F(x) = p (F is continuous and strictly increasing: x is unique)
+ *   mean       = K + (1/S) sum_s (mu_s - K), K = mu_1 (as npbnn_predict_sets_calibration forms it)
+ *   A(m, v)    = 2 sqrt(v) phi(m / sqrt v) + m erf(m / sqrt(2 v))      (= E|N(m, v)|; both terms are >= 0)
+ *   crps(y)    = (1/S) sum_s A(y - mu_s, sigma_s^2)
+ *                - (1/(2 S^2)) [sum_s 2 sigma_s / sqrt(pi) + 2 sum_{s<t} A(mu_s - mu_t, sigma_s^2 + sigma_t^2)]
+ * The quantile is a safeguarded Newton search (bisection whenever a Newton step leaves the bracket) from the bracket of the
+ * components' own p-quantiles, widened while an end is on the wrong side, run until the bracket cannot narrow or 200 passes over S are
+ * spent; for p > 0.5 on the upper tail, sum erfc(+u) against 1 - p.  The end of the last bracket with the smaller residual is returned: with
+ * delta = (S + 8) 2^-53, |F(q) - p| <= 4 delta max(p, 1 - p) or q lies within 4 ulp of the root (F may pass the first bound within
+ * one ulp of x).  The CRPS costs S (S - 1) / 2 pair terms per cell; with T1 and T2 / 2 its two non-negative parts,
+ * |crps - exact| <= (64 + ceil(S (S - 1) / 128)) 2^-53 (T1 + T2 / 2).  The bits of a cell's result depend on its values and on S alone.
+ *   probs [n_probs]   n_probs in 0..16, each with min(p, 1 - p) >= 1e-12, in any order
+ *   out_quantile      [n_probs][n_cols]; NULL exactly when n_probs == 0
+ *   out_mean          [n_cols], or NULL
+ *   y, out_crps       [n_cols] both, or both NULL; y finite
+ * NPBNN_E_ARG, before the device is touched: more than 16384 samples, more than 16 probabilities or one out of range, nothing asked
+ * for, y without out_crps or the reverse, a mu or y that is NaN or infinite, a sigma that is not positive and finite. */
+int npbnn_op_mixture(int device, const void* mu, const void* sigma, int value_type, int64_t n_samples, int64_t n_cols, int64_t col_stride,
+                     int32_t sigma_cols, const double* probs, int32_t n_probs, const double* y, double* out_quantile, double* out_mean,
+                     double* out_crps);
 
 /* ---- MC3 temperature-swap exchange over RCCL (xGMI inside a node): replaces the multiprocessing pool
  * round trip of whole pickled chains in MC3.run_mcmc (np_bnn/BNN_mc3.py:94-112), of which the swap

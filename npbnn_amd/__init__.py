@@ -41,6 +41,7 @@ from .lppd import get_posterior_lppd, posterior_lppd  # noqa: F401
 from .uncertainty import get_posterior_uncertainty, posterior_uncertainty  # noqa: F401
 from .calibration import get_posterior_calibration, posterior_calibration  # noqa: F401
 from .convergence import get_posterior_convergence, posterior_convergence  # noqa: F401
+from .predictive import get_posterior_predictive, posterior_predictive  # noqa: F401
 from . import comm  # noqa: F401
 
 BNN = npBNN                       # BASELINE.json's wording

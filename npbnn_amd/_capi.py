@@ -169,6 +169,7 @@ SIGNATURES = {
     "npbnn_predict_sets_calibration": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, _DP, C.c_int32, _DP, C.c_int32, _DP, _DP, _DP,
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), _DP, _DP]),
     "npbnn_predict_sets_convergence": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int32, C.c_int, C.c_int, C.c_double, _DP, _DP, _DP]),
+    "npbnn_predict_sets_predictive": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, _DP, _DP, C.c_int32, _DP, _DP, _DP, _DP, _DP]),
     "npbnn_time_eval": (C.c_int, [_P, _DP, C.c_int, _DP, _DP]),
     "npbnn_time_pass": (C.c_int, [_P, _DP, C.c_int, C.c_int, _DP, C.POINTER(C.c_int)]),
     "npbnn_time_wide": (C.c_int, [_P, _DP, C.c_int, _DP, _DP, C.POINTER(C.c_int)]),
@@ -192,6 +193,8 @@ SIGNATURES = {
     "npbnn_op_sse": (C.c_int, [C.c_int, _DP, _DP, C.c_int64, C.c_int32, C.c_int32, C.c_int, _DP]),
     "npbnn_op_hpd": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _DP, _DP]),
     "npbnn_op_convergence": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _DP, _DP]),
+    "npbnn_op_mixture": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _DP, C.c_int32, _DP, _DP,
+                                   _DP, _DP]),
     "npbnn_comm_unique_id": (C.c_int, [C.c_char * 128]),
     "npbnn_comm_init": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_char * 128, C.POINTER(_P)]),
     "npbnn_comm_allgather_f64": (C.c_int, [_P, _DP, C.c_int, _DP]),

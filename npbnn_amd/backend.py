@@ -554,6 +554,50 @@ class HipContext:
                                                            capi.dptr(summary)))
         return result_dict(rhat, ess, summary, n_rows, n_chains, n_draws)
 
+    def predict_sets_predictive(self, weight_sets, probs=(0.025, 0.5, 0.975), sigma_sets=None, targets=None, act_prm_sets=None, which=capi.TRAIN,
+                                want_mean=True, want_crps_i=True):
+        """The posterior predictive distribution of several weight sets on the resident matrix, per (row, target)
+        (npbnn_predict_sets_predictive); the kind follows the architecture's output function: OUT_IDENTITY (T = n_out targets, with
+        ``sigma_sets`` [n_sets, T] or [n_sets]) or OUT_SOFTPLUS_HALF (T = n_out / 2, the sigma predicted per row).  A dict with
+        ``quantiles`` [len(probs), n_rows, T] (None without probs), ``mean`` [n_rows, T] (None without ``want_mean``) and, with
+        ``targets`` [n_rows, T] (float64, sent with the call), ``crps_i`` [n_rows, T] (None without ``want_crps_i``) and
+        ``crps_total`` [T], its sum over the rows; both are None without targets.  ``npbnn_amd.predictive`` has the definitions.  The
+        sets replay as in ``predict_sets_hpd`` into a float32 stack that stays on the device; the results are the definitions' on
+        the float64 array ``predict_sets`` returns."""
+        from .predictive import MAX_SAMPLES, check_probs
+        who = "predict_sets_predictive"
+        pr = check_probs(probs, who)
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, who)
+        n_rows, n_out, kind = self.n_rows[which], self.n_out, self.arch.out_kind
+        if n_sets > MAX_SAMPLES:
+            raise ValueError("%s: %d samples, at most %d are supported" % (who, n_sets, MAX_SAMPLES))
+        if n_rows < 1:
+            raise ValueError("%s: the matrix has no rows" % who)
+        if kind not in (capi.OUT_IDENTITY, capi.OUT_SOFTPLUS_HALF):
+            raise ValueError("%s: the predictive distribution is that of a regression (OUT_IDENTITY or OUT_SOFTPLUS_HALF)" % who)
+        if kind == capi.OUT_SOFTPLUS_HALF and n_out % 2:
+            raise ValueError("%s: OUT_SOFTPLUS_HALF splits the outputs into means and sigmas, and %d is odd" % (who, n_out))
+        t = n_out // 2 if kind == capi.OUT_SOFTPLUS_HALF else n_out
+        sig = None
+        if kind == capi.OUT_IDENTITY:
+            sig = sigma_matrix(sigma_sets, n_sets, t, who)
+        elif sigma_sets is not None:
+            raise ValueError("%s: sigma_sets goes with OUT_IDENTITY only" % who)
+        tg = None
+        if targets is not None:
+            from .stored import target_matrix
+            tg = np.ascontiguousarray(target_matrix(targets, n_rows, t, who))
+        if not len(pr) and not want_mean and tg is None:
+            raise ValueError("%s: nothing asked for (no probs, no mean, no targets)" % who)
+        quant = np.empty((len(pr), n_rows, t)) if len(pr) else None
+        mean = np.empty((n_rows, t)) if want_mean else None
+        crps_i = np.empty((n_rows, t)) if tg is not None and want_crps_i else None
+        totals = np.zeros(t) if tg is not None else None
+        self._chk(self._lib.npbnn_predict_sets_predictive(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which, capi.dptr(sig),
+                                                          capi.dptr(pr) if len(pr) else None, len(pr), capi.dptr(tg), capi.dptr(quant),
+                                                          capi.dptr(mean), capi.dptr(crps_i), capi.dptr(totals)))
+        return dict(quantiles=quant, mean=mean, crps_i=crps_i, crps_total=totals)
+
     def predict_pdp(self, weight_sets, focal, grid, act_prm_sets=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         """Partial dependence on the resident matrix (npbnn_predict_pdp): [n_grid, n_rows, n_out], per grid point and row the
         prediction averaged over the weight sets, the columns ``focal`` set to the grid point's values ``grid`` [n_grid, n_focal]

@@ -191,6 +191,61 @@ def statistic(kind, y, lab):
     raise ValueError(kind)
 
 
+def mixture(mu, sigma, probs=(), y=None):
+    """npbnn_op_mixture on ``mu`` [S, ...]: quantiles, mean and CRPS of the Gaussian mixtures (1/S) sum_s N(mu_s, sigma_s^2), one per
+    trailing cell (npbnn_amd/predictive.py has the definitions).  ``sigma`` has ``mu``'s shape (a sigma per sample and cell), or is
+    [S, T] / [S] with T the last axis of ``mu`` (a sigma per sample and target, taken as float64; a flat [S, cells] ``mu`` takes any T, cell c
+    reading column c % T).  Returns
+    ``(quantiles [len(probs), ...] or None without probs, mean [...], crps [...] or None without y)``, float64, the trailing shape
+    kept.  float32 ``mu`` stays float32 on its way to the device (and a per-cell ``sigma`` with it), anything else is taken as
+    float64; the arithmetic is float64 either way."""
+    from .predictive import MAX_SAMPLES, check_probs
+    who = "mixture"
+    a = np.asarray(mu)
+    if a.ndim < 1 or a.shape[0] < 1:
+        raise ValueError("%s: mu must have a leading sample axis" % who)
+    if a.shape[0] > MAX_SAMPLES:
+        raise ValueError("%s: %d samples, at most %d are supported" % (who, a.shape[0], MAX_SAMPLES))
+    pr = check_probs(probs, who)
+    n_samples, shape = a.shape[0], a.shape[1:]
+    v = np.ascontiguousarray(a.reshape(n_samples, -1), dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    n_cols = v.shape[1]
+    sg = np.asarray(sigma)
+    if sg.shape == a.shape:
+        sg, sigma_cols = np.ascontiguousarray(sg.reshape(n_samples, -1), dtype=v.dtype), 0
+    else:
+        n_targets = shape[-1] if len(shape) else 1
+        if sg.ndim == 1:
+            sg = sg.reshape(-1, 1)
+        # (a flat [S, cells] mu takes any [S, T]: cell c reads column c % T, as the library does)
+        if sg.ndim != 2 or sg.shape[0] != n_samples or sg.shape[1] < 1 or (sg.shape[1] not in (1, n_targets) and a.ndim != 2):
+            raise ValueError("%s: sigma is %s, expected mu's shape %s or (%d, %d)" % (who, sg.shape, a.shape, n_samples, n_targets))
+        sg = np.ascontiguousarray(sg, dtype=np.float64)
+        sigma_cols = sg.shape[1]
+    if not np.all(np.isfinite(v)):
+        raise ValueError("%s: mu holds NaN or infinite values" % who)
+    if not (np.all(np.isfinite(sg)) and np.all(sg > 0)):
+        raise ValueError("%s: every sigma must be positive and finite" % who)
+    yy = None
+    if y is not None:
+        yy = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+        if np.shape(y) != shape:
+            raise ValueError("%s: y is %s, the cells are %s" % (who, np.shape(y), shape))
+        if not np.all(np.isfinite(yy)):
+            raise ValueError("%s: y holds NaN or infinite values" % who)
+    quant = np.empty((len(pr), n_cols)) if len(pr) else None
+    mean = np.empty(n_cols)
+    crps = np.empty(n_cols) if yy is not None else None
+    if n_cols:
+        lib, dev = _lib()
+        kind = capi.VALUE_F32 if v.dtype == np.float32 else capi.VALUE_F64
+        _chk(lib, lib.npbnn_op_mixture(dev, v.ctypes.data, sg.ctypes.data, kind, n_samples, n_cols, n_cols, sigma_cols,
+                                       capi.dptr(pr) if len(pr) else None, len(pr), capi.dptr(yy), capi.dptr(quant), capi.dptr(mean),
+                                       capi.dptr(crps)))
+    return (None if quant is None else quant.reshape((len(pr),) + shape), mean.reshape(shape),
+            None if crps is None else crps.reshape(shape))
+
+
 def convergence(values, n_chains=1):
     """npbnn_op_convergence on a [S, n_cols] array, ``n_chains`` chains of S / n_chains draws in chain-major order: (rhat, ess) as
     float64 [n_cols], NaN in a constant column (npbnn_amd/convergence.py has the definition).  float32 stays float32 on its way to

@@ -201,6 +201,34 @@ class _SamplePredictor:
         return ctx.predict_sets_convergence(self._packed, n_chains, rhat_threshold, act_prm_sets=self._slopes,
                                             apply_out_fn=self._applied, pointwise=pointwise)
 
+    def predictive(self, features, kind, probs=(0.025, 0.5, 0.975), sigma_sets=None, targets=None, block_rows=None, who="predictive"):
+        """Quantiles, mean and CRPS of the posterior predictive distribution of the stored samples on ``features``, ``kind``
+        ``"regression"`` (``sigma_sets`` per sample) or ``"regression-error"``: a dict with ``quantiles`` [len(probs), N, T], ``mean``
+        [N, T] and, with ``targets`` [N, T], ``crps_i`` [N, T]; the stack stays on the device (npbnn_predict_sets_predictive).
+        ``block_rows``: the most rows a device stack may hold.  A table of more rows is uploaded whole - the scales of the first
+        layer's half-precision split are the whole table's - and served block by block as the context's second table, so a row's
+        predictions do not depend on the blocks.  A custom output callable has no device kind: it is refused in ``who``'s name and no
+        host stack is built."""
+        from .predictive import KINDS
+        if kind not in KINDS:
+            raise ValueError("%s: kind %r; one of %s" % (who, kind, ", ".join(KINDS)))
+        if self.custom_output:
+            raise ValueError("%s: the model's output function is a custom callable, which has no device kind; build the stack "
+                             "and call posterior_predictive" % who)
+        self._out_kind_for(kind, who)
+        if kind == "regression" and sigma_sets is None:
+            raise ValueError("%s: kind \"regression\" needs sigma_sets (a sigma per sample and target)" % who)
+        ctx = self._load(features)
+        kw = dict(probs=probs, sigma_sets=sigma_sets, act_prm_sets=self._slopes)
+        if block_rows is None or block_rows >= len(features):
+            return ctx.predict_sets_predictive(self._packed, targets=targets, **kw)
+        parts = []
+        for r in range(0, len(features), block_rows):
+            ctx.set_data(features[r:r + block_rows], capi.TEST)
+            parts.append(ctx.predict_sets_predictive(self._packed, targets=None if targets is None else targets[r:r + block_rows], which=capi.TEST, **kw))
+        return {k: (None if parts[0][k] is None else np.concatenate([p[k] for p in parts], axis=1 if k == "quantiles" else 0))
+                for k in ("quantiles", "mean", "crps_i")}
+
     def close(self):
         self._ctx.close()
 
