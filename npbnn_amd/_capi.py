@@ -259,6 +259,12 @@ def dptr(a):
     return None if a is None else a.ctypes.data_as(_DP)
 
 
+def value_array(a):
+    """``a`` as the contiguous array an ``npbnn_op_*`` call reads and its VALUE_* code: float32 stays float32, anything else is float64."""
+    v = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    return v, VALUE_F32 if v.dtype == np.float32 else VALUE_F64
+
+
 def check(lib, ctx, rc):
     if rc != 0:
         msg = lib.npbnn_last_error(ctx)

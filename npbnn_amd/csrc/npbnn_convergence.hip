@@ -7,22 +7,21 @@
 // rho(2k + 1) (the header has the whole definition).  The reference has no counterpart: it leaves convergence to a trace viewer on
 // the logged weights.
 //
-// convergence_kernel follows hpd_kernel (npbnn_hpd.hip): a workgroup takes a tile of adjacent columns, reads it sample row by sample
-// row (one coalesced read per row of the tile) and keeps it in LDS in the input's type, column pitch S | 1 (odd, against bank
-// conflicts).  Each wave then takes one column at a time.  Pass 1: the split chains' means, one after the other, into the wave's
+// convergence_kernel is a stack column kernel (npbnn_stack.hip.h: the tile rule, the loader, the wave sum and the launch it shares
+// with hpd_kernel and the mixture kernels): a workgroup takes a tile of adjacent columns and keeps it in LDS in the input's type,
+// column pitch S | 1 (odd, against bank conflicts).  Each wave then takes one column at a time.  Pass 1: the split chains' means, one after the other, into the wave's
 // LDS slots; pass 2: the centred sums, d formed on the fly from the LDS copy - never sum x^2 - n mu^2.  A lag's sum over all split
 // chains is one scan: the lanes stride over the flat index (split chain, i) and a fixed xor butterfly leaves the same bits in every
 // lane, so the stop and monotone decisions are wave-uniform.  Lags are scanned in pairs as the sequence asks for them: a column whose
 // sequence stops early never pays for the later lags.  All arithmetic is float64, no product is fused into a sum (fp contract off),
 // no floating-point atomics, no scratch.  The grid depends on the column count alone.
 //
-// npbnn_predict_sets_convergence replays the stored sets through replay_sets (npbnn_sets.hip.h) into a float32 device stack
+// npbnn_predict_sets_convergence replays the stored sets through replay_into_stack (npbnn_stack.hip.h) into a float32 device stack
 // [S][rows][C], as npbnn_predict_sets_hpd does; one launch of convergence_kernel reads it once, and convergence_summary_kernel, one
 // workgroup per output, reduces rhat and ess over the rows in a fixed order.
-#include "npbnn_sets.hip.h"
+#include "npbnn_stack.hip.h"
 
 #include <cmath>
-#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -30,7 +29,6 @@ namespace npbnn_api {
 
 namespace {
 
-constexpr int kConvWaves = kStackThreads / 64;
 constexpr int kConvMaxChains = 64;
 constexpr int kConvMinDraws = 8;
 
@@ -42,12 +40,6 @@ struct ConvParams {
     double* ess;
     int* flag;                // bit 0: a value is not finite
 };
-
-// the sum of v over the wave, the same bits in every lane
-__device__ inline double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // where split chain k begins in a column
 __device__ inline int split_start(int k, int N, int n) { return (k >> 1) * N + ((k & 1) ? N - n : 0); }
@@ -72,23 +64,15 @@ __device__ inline double lag_sum(const T* col, const double* mu, int m, int N, i
 template <class T>
 __global__ __launch_bounds__(kStackThreads) void convergence_kernel(ConvParams p) {
     extern __shared__ __align__(16) unsigned char conv_lds[];
-    __shared__ double mu_lds[kConvWaves][2 * kConvMaxChains];
+    __shared__ double mu_lds[kStackWaves][2 * kConvMaxChains];
     T* sh = reinterpret_cast<T*>(conv_lds);
-    const T* values = static_cast<const T*>(p.values);
     const int pitch = p.S | 1;
     const long long c0 = (long long)blockIdx.x * p.tile;
     const int tc = (int)min((long long)p.tile, p.n_cols - c0);
 
-    // ---- the tile, sample row by sample row, into LDS columns
-    bool bad = false;
-    for (int i = threadIdx.x; i < (p.S << p.log2tile); i += kStackThreads) {
-        const int s = i >> p.log2tile, c = i & (p.tile - 1);
-        if (c < tc) {
-            const T v = values[(long long)s * p.col_stride + c0 + c];
-            if (!isfinite(v)) bad = true;
-            sh[c * pitch + s] = v;
-        }
-    }
+    // ---- the tile into LDS columns
+    const bool bad = load_stack_tile<1, false, true>(sh, static_cast<const T*>(p.values), (const T*)nullptr, p.col_stride, p.S, p.S, (T)0, p.tile,
+                                                     p.log2tile, tc, pitch, [c0](int c) { return c0 + c; });
     if (bad) atomicOr(p.flag, 1);
     // (a tile with a value that is not finite has no result: the call fails)
     if (__syncthreads_or(bad)) return;
@@ -97,7 +81,7 @@ __global__ __launch_bounds__(kStackThreads) void convergence_kernel(ConvParams p
     const int N = p.N, n = p.n, m = 2 * p.M;
     const double dn = (double)n, dm = (double)m;
     double* mu = mu_lds[wave];
-    for (int c = wave; c < tc; c += kConvWaves) {
+    for (int c = wave; c < tc; c += kStackWaves) {
         const T* col = sh + c * pitch;
         // pass 1: the split chains' means
         double mu_sum = 0.0;
@@ -202,7 +186,7 @@ int convergence_shape(npbnn_ctx* ctx, const char* who, long long M, long long N)
 // convergence_kernel over n_cols columns of the device array `values` (T = float or double); rhat / ess device arrays [n_cols].  The
 // kernel is enqueued on `stream` and `flag` (zeroed here) raised when a value is not finite; the caller synchronises and reads it.
 template <class T>
-int launch_convergence(npbnn_ctx* ctx, hipStream_t stream, const T* values, int M, int N, long long n_cols, long long col_stride, double* rhat,
+int launch_convergence(npbnn_ctx* ctx, hipStream_t stream, const void* values, int M, int N, long long n_cols, long long col_stride, double* rhat,
                        double* ess, int* flag) {
     ConvParams p{};
     p.values = values;
@@ -212,21 +196,11 @@ int launch_convergence(npbnn_ctx* ctx, hipStream_t stream, const T* values, int 
     p.N = N;
     p.S = M * N;
     p.n = N / 2;
-    const size_t col_bytes = (size_t)(p.S | 1) * sizeof(T);
-    p.tile = 1;
-    while (p.tile < kStackMaxTile && (size_t)(2 * p.tile) * col_bytes <= kStackTileLds && 2 * p.tile <= n_cols) p.tile *= 2;
-    p.log2tile = ilog2(p.tile);
     p.rhat = rhat;
     p.ess = ess;
     p.flag = flag;
     HIP_TRY(ctx, hipMemsetAsync(flag, 0, sizeof(int), stream));
-    const size_t lds = (size_t)p.tile * col_bytes;      // <= 16385 * 8 bytes for one column of 16384 float64 values
-    const void* fn = reinterpret_cast<const void*>(convergence_kernel<T>);
-    HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long long blocks = (n_cols + p.tile - 1) / p.tile;
-    hipLaunchKernelGGL((convergence_kernel<T>), dim3((unsigned)blocks), dim3(kStackThreads), lds, stream, p);
-    HIP_TRY(ctx, hipGetLastError());
-    return NPBNN_OK;
+    return launch_stack_kernel(ctx, stream, reinterpret_cast<const void*>(convergence_kernel<T>), nullptr, (size_t)(p.S | 1) * sizeof(T), p);
 }
 
 }  // namespace
@@ -237,28 +211,22 @@ using namespace npbnn_api;
 
 extern "C" int npbnn_op_convergence(int device, const void* values, int value_type, int32_t n_chains, int32_t n_draws, int64_t n_cols,
                                     int64_t col_stride, double* out_rhat, double* out_ess) {
-    if (!values || !out_rhat || !out_ess || n_cols < 0 || col_stride < n_cols || (value_type != NPBNN_VALUE_F64 && value_type != NPBNN_VALUE_F32))
+    StackInput in(value_type);
+    if (!values || !out_rhat || !out_ess || n_cols < 0 || col_stride < n_cols || !in.ok())
         return fail(nullptr, NPBNN_E_ARG, "op_convergence: bad arguments");
     int rc = convergence_shape(nullptr, "op_convergence", n_chains, n_draws);
     if (rc) return rc;
     if (n_cols == 0) return NPBNN_OK;
     HIP_TRY(nullptr, hipSetDevice(device));
-    const size_t S = (size_t)n_chains * n_draws;
-    const size_t esize = value_type == NPBNN_VALUE_F64 ? 8 : 4;
-    const size_t n_el = (S - 1) * (size_t)col_stride + (size_t)n_cols;
-    DevBuf<double> d_v, d_res;          // (d_v: n_el values of esize bytes)
+    DevBuf<double> d_res;
     DevBuf<int> d_flag;
-    if ((rc = dev_alloc(nullptr, d_v, (n_el * esize + 7) / 8))) return rc;
+    if ((rc = in.upload(values, (int64_t)n_chains * n_draws, n_cols, col_stride))) return rc;
     if ((rc = dev_alloc(nullptr, d_res, 2 * (size_t)n_cols))) return rc;
     if ((rc = dev_alloc(nullptr, d_flag, 1))) return rc;
-    HIP_TRY(nullptr, hipMemcpy(d_v.get(), values, n_el * esize, hipMemcpyHostToDevice));
     double* rhat = d_res.get();
     double* ess = rhat + n_cols;
-    if (value_type == NPBNN_VALUE_F64)
-        rc = launch_convergence<double>(nullptr, nullptr, d_v.get(), n_chains, n_draws, n_cols, col_stride, rhat, ess, d_flag.get());
-    else
-        rc = launch_convergence<float>(nullptr, nullptr, reinterpret_cast<const float*>(d_v.get()), n_chains, n_draws, n_cols, col_stride, rhat, ess,
-                                       d_flag.get());
+    if (in.f32()) rc = launch_convergence<float>(nullptr, nullptr, in.buf.get(), n_chains, n_draws, n_cols, col_stride, rhat, ess, d_flag.get());
+    else rc = launch_convergence<double>(nullptr, nullptr, in.buf.get(), n_chains, n_draws, n_cols, col_stride, rhat, ess, d_flag.get());
     if (rc) return rc;
     int bad = 0;
     HIP_TRY(nullptr, hipMemcpy(&bad, d_flag.get(), sizeof(int), hipMemcpyDeviceToHost));
@@ -284,15 +252,13 @@ extern "C" int npbnn_predict_sets_convergence(npbnn_ctx* ctx, const double* W_se
     const int C = ctx->net.n_out;
     const long long n_rows = tb.n_rows;
     const size_t per_set = (size_t)n_rows * C;
-    if ((rc = check_stack_budget(ctx, "predict_sets_convergence", n_sets, n_rows, C))) return rc;
     hipStream_t st = tb.st;
     DevBuf<float> stack;
     DevBuf<double> d_res;
     DevBuf<int> d_flag;
-    if ((rc = dev_alloc(ctx, stack, (size_t)n_sets * per_set))) return rc;
+    if ((rc = replay_into_stack(ctx, "predict_sets_convergence", W_sets, act_prm_sets, n_sets, which, apply_out_fn, tb, &stack))) return rc;
     if ((rc = dev_alloc(ctx, d_res, 2 * per_set + 4 * (size_t)C))) return rc;
     if ((rc = dev_alloc(ctx, d_flag, 1))) return rc;
-    if ((rc = replay_sets(ctx, "predict_sets_convergence", W_sets, act_prm_sets, n_sets, which, apply_out_fn, stack.get(), SetSink()))) return rc;
     double* rhat = d_res.get();
     double* ess = rhat + per_set;
     double* summary = ess + per_set;

@@ -27,6 +27,7 @@
 #include "npbnn_attrib_plan.h"
 #include "npbnn_resident_plan.h"
 #include "npbnn_sched_plan.h"
+#include "npbnn_stack_plan.h"
 #include "npbnn_wide_plan.h"
 
 #define NPBNN_HOST_MAX_LAYERS 8
@@ -780,5 +781,13 @@ int npbnn_host_attrib_pdp_g_chunk(int n_grid, int64_t n_rows, int C, int64_t acc
 int npbnn_host_attrib_ale(const npbnn_attrib_route* r, int K, int C, int64_t n_rows, int64_t part_bytes, npbnn_attrib_ale* out) {
     if (!r || !out) return -1;
     npbnn_attrib_ale_of(r, K, C, n_rows, part_bytes, out);
+    return 0;
+}
+
+/* The tile rule of the column kernels over a sample stack (npbnn_stack_plan.h: what the HIP library sizes their LDS and grids by),
+ * exported for the CPU tests of that rule. */
+int npbnn_host_stack_tile(int64_t col_bytes, int64_t n_cols, int64_t max_col_bytes, npbnn_stack_tile* out) {
+    if (!out || col_bytes < 1 || n_cols < 0) return -1;
+    *out = npbnn_stack_tile_of(col_bytes, n_cols, max_col_bytes);
     return 0;
 }

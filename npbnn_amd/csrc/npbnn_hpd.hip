@@ -2,31 +2,22 @@
 //
 // calcHPD sorts one vector of S values, takes nIn = round(level * S) of them (round half to even: nearbyint under the default
 // rounding mode) and returns the first window d[k] .. d[k + nIn - 1] of smallest width (a later window replaces the best only when
-// strictly narrower).  hpd_kernel gives each workgroup a tile of TC adjacent columns: the tile is read sample row by sample row
-// (adjacent columns are contiguous, so a row of the tile is one coalesced read), transposed into LDS as TC columns of P = next
-// power of two >= S values (padded with +inf, column pitch P + 1 against bank conflicts) and sorted there by a bitonic network.
+// strictly narrower).  hpd_kernel gives each workgroup a tile of TC adjacent columns (the tile rule, the loader and the launch are
+// the stack column kernels' shared ones, npbnn_stack.hip.h): the tile goes into LDS as TC columns of P = next power of two >= S
+// values (padded with +inf, column pitch P + 1 against bank conflicts) and is sorted there by a bitonic network.
 // Each wave then scans the windows of its columns - widths in W, the input's type for npbnn_op_hpd and float64 for the float32
 // stack of npbnn_predict_sets_hpd - and a shuffle reduction picks the smallest width, the smallest k among equal ones.  The mean
 // (float64 sum in a fixed order) comes from the same LDS copy.  No atomics but the non-finite flag, no scratch.
 //
-// npbnn_predict_sets_hpd replays the stored sets through replay_sets (npbnn_sets.hip.h), each group writing its float32 predictions
-// straight into a device stack [S][rows][C]; one launch of hpd_kernel then reads the stack once.
-#include "npbnn_sets.hip.h"
+// npbnn_predict_sets_hpd replays the stored sets through replay_into_stack (npbnn_stack.hip.h), each group writing its float32
+// predictions straight into a device stack [S][rows][C]; one launch of hpd_kernel then reads the stack once.
+#include "npbnn_stack.hip.h"
 
-#include <climits>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 namespace npbnn_api {
 
 namespace {
-
-constexpr int kHpdThreads = kStackThreads;
-constexpr int kHpdMaxSamples = kStackMaxSamples;
-constexpr int kHpdMaxTile = kStackMaxTile;
-constexpr size_t kHpdTileLds = kStackTileLds;
 
 struct HpdParams {
     const void* values;       // values[s * col_stride + c]
@@ -39,26 +30,17 @@ struct HpdParams {
 };
 
 template <class T, class W>
-__global__ __launch_bounds__(kHpdThreads) void hpd_kernel(HpdParams p) {
+__global__ __launch_bounds__(kStackThreads) void hpd_kernel(HpdParams p) {
     extern __shared__ __align__(16) unsigned char hpd_lds[];
     T* sh = reinterpret_cast<T*>(hpd_lds);
-    const T* values = static_cast<const T*>(p.values);
     const int pitch = p.P + 1;
     const long long c0 = (long long)blockIdx.x * p.tile;
     const int tc = (int)min((long long)p.tile, p.n_cols - c0);
 
-    // ---- the tile, sample row by sample row, into LDS columns; +inf past S
-    bool bad = false;
-    for (int i = threadIdx.x; i < (p.P << p.log2tile); i += kHpdThreads) {
-        const int s = i >> p.log2tile, c = i & (p.tile - 1);
-        T v = (T)INFINITY;
-        if (s < p.S && c < tc) {
-            v = values[(long long)s * p.col_stride + c0 + c];
-            if (!isfinite(v)) bad = true;
-        }
-        sh[c * pitch + s] = v;
-    }
-    if (bad) atomicOr(p.flag, 1);
+    // ---- the tile into LDS columns; +inf past S
+    if (load_stack_tile<1, true, true>(sh, static_cast<const T*>(p.values), (const T*)nullptr, p.col_stride, p.S, p.P, (T)INFINITY, p.tile,
+                                       p.log2tile, tc, pitch, [c0](int c) { return c0 + c; }))
+        atomicOr(p.flag, 1);
 
     // ---- bitonic sort of every column, ascending
     const int log2half = p.log2P - 1;
@@ -66,7 +48,7 @@ __global__ __launch_bounds__(kHpdThreads) void hpd_kernel(HpdParams p) {
     for (int k = 2; k <= p.P; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
             __syncthreads();
-            for (int t = threadIdx.x; t < n_pairs; t += kHpdThreads) {
+            for (int t = threadIdx.x; t < n_pairs; t += kStackThreads) {
                 const int c = t >> log2half, q = t & ((1 << log2half) - 1);
                 const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1));
                 T* col = sh + c * pitch;
@@ -83,7 +65,7 @@ __global__ __launch_bounds__(kHpdThreads) void hpd_kernel(HpdParams p) {
     // ---- per column (one wave each): the first narrowest window, and the mean
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int m = p.S - p.n_in + 1;
-    for (int c = wave; c < tc; c += kHpdThreads / 64) {
+    for (int c = wave; c < tc; c += kStackWaves) {
         const T* col = sh + c * pitch;
         W best = (W)0;
         int bk = -1;
@@ -98,8 +80,8 @@ __global__ __launch_bounds__(kHpdThreads) void hpd_kernel(HpdParams p) {
             const W ob = __shfl_xor(best, off);
             const int ok = __shfl_xor(bk, off);
             if (ok >= 0 && (bk < 0 || ob < best || (ob == best && ok < bk))) { best = ob; bk = ok; }
-            sum += __shfl_xor(sum, off);
         }
+        sum = wave_sum(sum);
         if (lane == 0) {
             p.lo[c0 + c] = (double)col[bk];
             p.hi[c0 + c] = (double)col[bk + p.n_in - 1];
@@ -111,7 +93,7 @@ __global__ __launch_bounds__(kHpdThreads) void hpd_kernel(HpdParams p) {
 // nIn of calcHPD, or an error through fail(ctx, ...)
 int hpd_window(npbnn_ctx* ctx, const char* who, long long S, double level, int* n_in) {
     if (!(level > 0.0 && level < 1.0)) return fail(ctx, NPBNN_E_ARG, "%s: level %g outside (0, 1)", who, level);
-    if (S > kHpdMaxSamples) return fail(ctx, NPBNN_E_ARG, "%s: %lld samples, at most %d", who, S, kHpdMaxSamples);
+    if (S > kStackMaxSamples) return fail(ctx, NPBNN_E_ARG, "%s: %lld samples, at most %d", who, S, kStackMaxSamples);
     const double r = nearbyint(level * (double)S);
     if (r < 2.0) return fail(ctx, NPBNN_E_ARG, "%s: too little data to calculate marginal parameters (round(%g * %lld) < 2)", who, level, S);
     *n_in = (int)r;
@@ -119,41 +101,23 @@ int hpd_window(npbnn_ctx* ctx, const char* who, long long S, double level, int* 
 }
 
 // hpd_kernel over n_cols columns of the device array `values` (T = float or double, widths in W); lo / hi / mean device arrays
-// [n_cols].  Returns NPBNN_E_ARG when a value is not finite.
+// [n_cols].  The kernel is enqueued on `stream` and `flag` (zeroed here) raised when a value is not finite: the caller reads it.
 template <class T, class W>
-int launch_hpd(npbnn_ctx* ctx, hipStream_t stream, const char* who, const T* values, long long S, long long n_cols, long long col_stride,
-               int n_in, double* lo, double* hi, double* mean) {
+int launch_hpd(npbnn_ctx* ctx, hipStream_t stream, const void* values, long long S, long long n_cols, long long col_stride, int n_in, double* lo,
+               double* hi, double* mean, int* flag) {
     HpdParams p{};
     p.values = values;
     p.n_cols = n_cols;
     p.col_stride = col_stride;
     p.S = (int)S;
-    p.log2P = ilog2(S);
-    p.P = 1 << p.log2P;
+    for (p.P = 1; p.P < S; p.P *= 2) ++p.log2P;       // (the smallest power of two >= S)
     p.n_in = n_in;
-    const size_t col_bytes = (size_t)(p.P + 1) * sizeof(T);
-    p.tile = 1;
-    while (p.tile < kHpdMaxTile && (size_t)(2 * p.tile) * col_bytes <= kHpdTileLds && 2 * p.tile <= n_cols) p.tile *= 2;
-    p.log2tile = ilog2(p.tile);
     p.lo = lo;
     p.hi = hi;
     p.mean = mean;
-    DevBuf<int> flag;
-    int rc = dev_alloc(ctx, flag, 1);
-    if (rc) return rc;
-    p.flag = flag.get();
-    HIP_TRY(ctx, hipMemsetAsync(p.flag, 0, sizeof(int), stream));
-    const size_t lds = (size_t)p.tile * col_bytes;      // <= 16385 * 8 bytes for one column of 16384 float64 values
-    const void* fn = reinterpret_cast<const void*>(hpd_kernel<T, W>);
-    HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long long blocks = (n_cols + p.tile - 1) / p.tile;
-    hipLaunchKernelGGL((hpd_kernel<T, W>), dim3((unsigned)blocks), dim3(kHpdThreads), lds, stream, p);
-    HIP_TRY(ctx, hipGetLastError());
-    int bad = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&bad, p.flag, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (bad) return fail(ctx, NPBNN_E_ARG, "%s: a value is NaN or infinite", who);
-    return NPBNN_OK;
+    p.flag = flag;
+    HIP_TRY(ctx, hipMemsetAsync(flag, 0, sizeof(int), stream));
+    return launch_stack_kernel(ctx, stream, reinterpret_cast<const void*>(hpd_kernel<T, W>), nullptr, (size_t)(p.P + 1) * sizeof(T), p);
 }
 
 }  // namespace
@@ -164,29 +128,29 @@ using namespace npbnn_api;
 
 extern "C" int npbnn_op_hpd(int device, const void* values, int value_type, int64_t n_samples, int64_t n_cols, int64_t col_stride,
                             double level, double* out_lo, double* out_hi) {
-    if (!values || !out_lo || !out_hi || n_cols < 0 || col_stride < n_cols || n_samples < 1 ||
-        (value_type != NPBNN_VALUE_F64 && value_type != NPBNN_VALUE_F32))
+    StackInput in(value_type);
+    if (!values || !out_lo || !out_hi || n_cols < 0 || col_stride < n_cols || n_samples < 1 || !in.ok())
         return fail(nullptr, NPBNN_E_ARG, "op_hpd: bad arguments");
     int n_in = 0;
     int rc = hpd_window(nullptr, "op_hpd", n_samples, level, &n_in);
     if (rc) return rc;
     if (n_cols == 0) return NPBNN_OK;
     HIP_TRY(nullptr, hipSetDevice(device));
-    const size_t esize = value_type == NPBNN_VALUE_F64 ? 8 : 4;
-    const size_t n_el = (size_t)(n_samples - 1) * (size_t)col_stride + (size_t)n_cols;
-    DevBuf<double> d_v, d_lo, d_hi;          // (d_v: n_el values of esize bytes)
-    if ((rc = dev_alloc(nullptr, d_v, (n_el * esize + 7) / 8))) return rc;
-    if ((rc = dev_alloc(nullptr, d_lo, (size_t)n_cols))) return rc;
-    if ((rc = dev_alloc(nullptr, d_hi, (size_t)n_cols))) return rc;
-    HIP_TRY(nullptr, hipMemcpy(d_v.get(), values, n_el * esize, hipMemcpyHostToDevice));
-    if (value_type == NPBNN_VALUE_F64)
-        rc = launch_hpd<double, double>(nullptr, nullptr, "op_hpd", d_v.get(), n_samples, n_cols, col_stride, n_in, d_lo, d_hi, nullptr);
-    else
-        rc = launch_hpd<float, float>(nullptr, nullptr, "op_hpd", reinterpret_cast<const float*>(d_v.get()), n_samples, n_cols, col_stride,
-                                      n_in, d_lo, d_hi, nullptr);
+    DevBuf<double> d_res;
+    DevBuf<int> d_flag;
+    if ((rc = in.upload(values, n_samples, n_cols, col_stride))) return rc;
+    if ((rc = dev_alloc(nullptr, d_res, 2 * (size_t)n_cols))) return rc;
+    if ((rc = dev_alloc(nullptr, d_flag, 1))) return rc;
+    double* lo = d_res.get();
+    double* hi = lo + n_cols;
+    if (in.f32()) rc = launch_hpd<float, float>(nullptr, nullptr, in.buf.get(), n_samples, n_cols, col_stride, n_in, lo, hi, nullptr, d_flag.get());
+    else rc = launch_hpd<double, double>(nullptr, nullptr, in.buf.get(), n_samples, n_cols, col_stride, n_in, lo, hi, nullptr, d_flag.get());
     if (rc) return rc;
-    HIP_TRY(nullptr, hipMemcpy(out_lo, d_lo.get(), (size_t)n_cols * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(nullptr, hipMemcpy(out_hi, d_hi.get(), (size_t)n_cols * 8, hipMemcpyDeviceToHost));
+    int bad = 0;
+    HIP_TRY(nullptr, hipMemcpy(&bad, d_flag.get(), sizeof(int), hipMemcpyDeviceToHost));
+    if (bad) return fail(nullptr, NPBNN_E_ARG, "op_hpd: a value is NaN or infinite");
+    HIP_TRY(nullptr, hipMemcpy(out_lo, lo, (size_t)n_cols * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(nullptr, hipMemcpy(out_hi, hi, (size_t)n_cols * 8, hipMemcpyDeviceToHost));
     return NPBNN_OK;
 }
 
@@ -198,21 +162,23 @@ extern "C" int npbnn_predict_sets_hpd(npbnn_ctx* ctx, const double* W_sets, cons
     int n_in = 0;
     int rc = open_sets_table(ctx, "predict_sets_hpd", which, &tb);
     if (rc || (rc = hpd_window(ctx, "predict_sets_hpd", n_sets, level, &n_in))) return rc;
-    const int C = ctx->net.n_out;
-    const size_t per_set = (size_t)tb.n_rows * C;
-    if ((rc = check_stack_budget(ctx, "predict_sets_hpd", n_sets, tb.n_rows, C))) return rc;
+    const size_t per_set = (size_t)tb.n_rows * ctx->net.n_out;
     DevBuf<float> stack;
     DevBuf<double> d_res;
-    if ((rc = dev_alloc(ctx, stack, (size_t)n_sets * per_set))) return rc;
+    DevBuf<int> d_flag;
+    if ((rc = replay_into_stack(ctx, "predict_sets_hpd", W_sets, act_prm_sets, n_sets, which, apply_out_fn, tb, &stack))) return rc;
     if ((rc = dev_alloc(ctx, d_res, 3 * per_set))) return rc;
-    if ((rc = replay_sets(ctx, "predict_sets_hpd", W_sets, act_prm_sets, n_sets, which, apply_out_fn, stack.get(), SetSink()))) return rc;
+    if ((rc = dev_alloc(ctx, d_flag, 1))) return rc;
     // bounds from the float32 values with float64 widths: upstream's calcHPD on the float64 array npbnn_predict_sets returns
     double* lo = d_res.get();
     double* hi = lo + per_set;
     double* mean = hi + per_set;
-    rc = launch_hpd<float, double>(ctx, ctx->stream, "predict_sets_hpd", stack.get(), n_sets, (long long)per_set, (long long)per_set,
-                                   n_in, lo, hi, mean);
+    rc = launch_hpd<float, double>(ctx, ctx->stream, stack.get(), n_sets, (long long)per_set, (long long)per_set, n_in, lo, hi, mean, d_flag.get());
     if (rc) return rc;
+    int bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, d_flag.get(), sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (bad) return fail(ctx, NPBNN_E_ARG, "predict_sets_hpd: a value is NaN or infinite");
     HIP_TRY(ctx, hipMemcpyAsync(out_lo, lo, per_set * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_hi, hi, per_set * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out_mean, mean, per_set * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -8,7 +8,8 @@
 //   crps(y)    = (1/S) sum_s A(y - mu_s, sigma_s^2) - (1/(2 S^2)) [sum_s 2 sigma_s / sqrt(pi) + 2 sum_{s<t} A(mu_s - mu_t, sigma_s^2 + sigma_t^2)]
 // The reference has no counterpart: its summary code takes calcHPD of the means (np_bnn/BNN_plot.py:73-75), which leaves the noise out.
 //
-// Both kernels follow hpd_kernel (npbnn_hpd.hip): a workgroup of kStackThreads threads takes a tile of adjacent cells into LDS - mu in
+// Both kernels are stack column kernels (npbnn_stack.hip.h: the tile rule of npbnn_stack_plan.h, the loader, the wave reductions
+// and the launch they share with hpd_kernel and convergence_kernel): a workgroup takes a tile of adjacent cells into LDS - mu in
 // the input's type, and sigma beside it when it has mu's type and layout; a per-sample float64 sigma [S][T] is small, shared by every
 // cell of a target, and is read where it lies.  A single cell that does not fit the LDS (float64 mu and sigma at S = 16384) is not
 // staged: every pass reads it from global memory.  One wave works on one cell at a time, its 64 lanes stride over S (over the pairs
@@ -25,8 +26,8 @@
 //
 // Floating-point contraction (the rule of npbnn_fold.hip.h): this unit's definitions are float64 sums of products whose bits a test
 // compares against a restatement, so contraction is switched off for the whole unit after the includes; the headers above it hold no
-// product that feeds a sum (npbnn_sets.hip.h says so of itself) and are not touched by it.
-#include "npbnn_sets.hip.h"
+// product that feeds a sum (npbnn_stack.hip.h and npbnn_sets.hip.h say so of themselves) and are not touched by it.
+#include "npbnn_stack.hip.h"
 
 #include <cfloat>
 #include <cmath>
@@ -41,9 +42,7 @@ namespace {
 constexpr int kMixMaxProbs = 16;
 constexpr int kMixMaxSteps = 200;                  // passes of the root search (a CPU emulation of the scheme needed 77 at most)
 constexpr int kMixMaxWiden = 128;                  // doublings of an end that is on the wrong side
-constexpr size_t kMixMaxLds = 160 * 1024;          // a single staged cell may take the whole LDS
 constexpr double kMinTail = 1e-12;                 // min(p, 1 - p) at least
-constexpr int kMixWaves = kStackThreads / 64;
 constexpr int kFlagBadSigma = 8;                   // (beside kFlagNaN: a mu that is not finite)
 
 constexpr double kInvSqrt2 = 0.70710678118654752440;
@@ -70,24 +69,6 @@ __device__ inline long long cell_off(const MixParams& p, long long c) {
     return (c / p.cells_per_row) * p.row_pitch + c % p.cells_per_row;
 }
 
-// the sum / smallest / largest of v over the wave, the same bits in every lane
-__device__ inline double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ inline double wave_min(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ inline double wave_max(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ inline int wave_or(int v) {
-    for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off);
-    return v;
-}
-
 // One cell's components: mu and sigma of sample s, from the LDS copy or from where they lie.
 template <class V, bool SIG64>
 struct Cell {
@@ -100,20 +81,12 @@ struct Cell {
     __device__ double sd(int s) const { return SIG64 ? sg64[(long long)s * sg_stride] : (double)sg[s * stride]; }
 };
 
-// The workgroup's tile into LDS, sample row by sample row (adjacent cells are contiguous within a row of the table): mu [tile][pitch],
-// then sigma [tile][pitch] unless SIG64.  Every thread of the workgroup calls it.
+// The workgroup's tile into LDS (adjacent cells are contiguous within a row of the table): mu [tile][pitch], then sigma [tile][pitch]
+// unless SIG64.  Every thread of the workgroup calls it.
 template <class V, bool SIG64>
 __device__ inline void stage_tile(const MixParams& p, V* sh, long long c0, int tc, int pitch) {
-    const V* gmu = static_cast<const V*>(p.mu);
-    const V* gsg = static_cast<const V*>(p.sg);
-    V* sh_sg = sh + (long long)p.tile * pitch;
-    for (int i = threadIdx.x; i < (p.S << p.log2tile); i += kStackThreads) {
-        const int s = i >> p.log2tile, c = i & (p.tile - 1);
-        if (c >= tc) continue;
-        const long long at = (long long)s * p.col_stride + cell_off(p, c0 + c);
-        sh[c * pitch + s] = gmu[at];
-        if (!SIG64) sh_sg[c * pitch + s] = gsg[at];
-    }
+    load_stack_tile<SIG64 ? 1 : 2, false, false>(sh, static_cast<const V*>(p.mu), static_cast<const V*>(p.sg), p.col_stride, p.S, p.S, (V)0, p.tile,
+                                                 p.log2tile, tc, pitch, [&p, c0](int c) { return cell_off(p, c0 + c); });
     __syncthreads();
 }
 
@@ -226,7 +199,7 @@ __global__ __launch_bounds__(kStackThreads) void mixture_quantile_kernel(MixPara
     const int tc = (int)min((long long)p.tile, p.n_cols - c0);
     if (STAGED) stage_tile<V, SIG64>(p, reinterpret_cast<V*>(mix_lds), c0, tc, pitch);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = wave; c < tc; c += kMixWaves) {
+    for (int c = wave; c < tc; c += kStackWaves) {
         const Cell<V, SIG64> cell = cell_of<V, SIG64, STAGED>(p, sh, c0, c, pitch);
         const int f = cell_flags(cell, p.S, lane);
         if (f) {                                                   // (refused by the host: no search on such values)
@@ -261,7 +234,7 @@ __global__ __launch_bounds__(kStackThreads) void mixture_crps_kernel(MixParams p
     if (STAGED) stage_tile<V, SIG64>(p, reinterpret_cast<V*>(mix_lds), c0, tc, pitch);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int S = p.S;
-    for (int c = wave; c < tc; c += kMixWaves) {
+    for (int c = wave; c < tc; c += kStackWaves) {
         const Cell<V, SIG64> cell = cell_of<V, SIG64, STAGED>(p, sh, c0, c, pitch);
         const int f = cell_flags(cell, S, lane);
         if (f) {
@@ -337,39 +310,24 @@ int check_probs(npbnn_ctx* ctx, const char* who, const double* probs, int n_prob
     return NPBNN_OK;
 }
 
-template <class V, bool SIG64>
-int launch_kernel(npbnn_ctx* ctx, hipStream_t stream, const MixParams& p, bool staged, bool crps, size_t lds, unsigned blocks) {
-    const void* fn;
-    if (crps) fn = staged ? reinterpret_cast<const void*>(mixture_crps_kernel<V, SIG64, true>) : reinterpret_cast<const void*>(mixture_crps_kernel<V, SIG64, false>);
-    else fn = staged ? reinterpret_cast<const void*>(mixture_quantile_kernel<V, SIG64, true>) : reinterpret_cast<const void*>(mixture_quantile_kernel<V, SIG64, false>);
-    if (lds) HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    MixParams arg = p;
-    void* args[] = {&arg};
-    HIP_TRY(ctx, hipLaunchKernel(fn, dim3(blocks), dim3(kStackThreads), args, lds, stream));
-    return NPBNN_OK;
-}
-
 // The kernels over the n_cols cells p describes (mu, sg / sg64, strides, S, probabilities, outputs; all on the device): the
-// quantile kernel when quantiles or the mean are asked for, the CRPS kernel when p.crps is.  Chooses the tile, raises nothing
-// itself: the caller reads the flag word.  f32: mu (and a same-type sigma) are float32.
-int launch_mixture(npbnn_ctx* ctx, hipStream_t stream, MixParams p, bool f32) {
-    const bool sig64 = p.sigma_cols > 0;
-    const size_t cell_bytes = (size_t)(p.S | 1) * (f32 ? 4 : 8) * (sig64 ? 1 : 2);
-    p.tile = 1;
-    while (p.tile < kStackMaxTile && (size_t)(2 * p.tile) * cell_bytes <= kStackTileLds && 2 * p.tile <= p.n_cols) p.tile *= 2;
-    p.log2tile = ilog2(p.tile);
-    const bool staged = (size_t)p.tile * cell_bytes <= kMixMaxLds;       // (a tile of more than one cell always is)
-    const size_t lds = staged ? (size_t)p.tile * cell_bytes : 0;
-    const unsigned blocks = (unsigned)((p.n_cols + p.tile - 1) / p.tile);
-    for (int pass = 0; pass < 2; ++pass) {
-        const bool crps = pass == 1;
-        if (crps ? !p.crps : !(p.n_probs > 0 || p.mean)) continue;
-        int rc;
-        if (f32) rc = sig64 ? launch_kernel<float, true>(ctx, stream, p, staged, crps, lds, blocks) : launch_kernel<float, false>(ctx, stream, p, staged, crps, lds, blocks);
-        else rc = sig64 ? launch_kernel<double, true>(ctx, stream, p, staged, crps, lds, blocks) : launch_kernel<double, false>(ctx, stream, p, staged, crps, lds, blocks);
-        if (rc) return rc;
-    }
-    return NPBNN_OK;
+// quantile kernel when quantiles or the mean are asked for, the CRPS kernel when p.crps is.  The caller reads the flag word.
+template <class V, bool SIG64>
+int launch_mixture(npbnn_ctx* ctx, hipStream_t stream, const MixParams& p) {
+    const size_t cell_bytes = (size_t)(p.S | 1) * sizeof(V) * (SIG64 ? 1 : 2);
+    int rc = NPBNN_OK;
+    if (p.n_probs > 0 || p.mean)
+        rc = launch_stack_kernel(ctx, stream, reinterpret_cast<const void*>(mixture_quantile_kernel<V, SIG64, true>),
+                                 reinterpret_cast<const void*>(mixture_quantile_kernel<V, SIG64, false>), cell_bytes, p);
+    if (!rc && p.crps)
+        rc = launch_stack_kernel(ctx, stream, reinterpret_cast<const void*>(mixture_crps_kernel<V, SIG64, true>),
+                                 reinterpret_cast<const void*>(mixture_crps_kernel<V, SIG64, false>), cell_bytes, p);
+    return rc;
+}
+// f32: mu (and a same-type sigma) are float32
+int launch_mixture(npbnn_ctx* ctx, hipStream_t stream, const MixParams& p, bool f32) {
+    if (p.sigma_cols > 0) return f32 ? launch_mixture<float, true>(ctx, stream, p) : launch_mixture<double, true>(ctx, stream, p);
+    return f32 ? launch_mixture<float, false>(ctx, stream, p) : launch_mixture<double, false>(ctx, stream, p);
 }
 
 int refuse_flags(npbnn_ctx* ctx, const char* who, int flags, const char* what) {
@@ -389,8 +347,8 @@ extern "C" int npbnn_op_mixture(int device, const void* mu, const void* sigma, i
                                 int32_t sigma_cols, const double* probs, int32_t n_probs, const double* y, double* out_quantile, double* out_mean,
                                 double* out_crps) {
     const char* who = "op_mixture";
-    if (!mu || !sigma || n_cols < 0 || col_stride < n_cols || n_samples < 1 || sigma_cols < 0 ||
-        (value_type != NPBNN_VALUE_F64 && value_type != NPBNN_VALUE_F32))
+    StackInput d_mu(value_type), d_sg(sigma_cols > 0 ? NPBNN_VALUE_F64 : value_type);
+    if (!mu || !sigma || n_cols < 0 || col_stride < n_cols || n_samples < 1 || sigma_cols < 0 || !d_mu.ok())
         return fail(nullptr, NPBNN_E_ARG, "%s: bad arguments", who);
     if (n_samples > kStackMaxSamples) return fail(nullptr, NPBNN_E_ARG, "%s: %lld samples, at most %d", who, (long long)n_samples, kStackMaxSamples);
     MixParams p{};
@@ -398,7 +356,7 @@ extern "C" int npbnn_op_mixture(int device, const void* mu, const void* sigma, i
     if (rc) return rc;
     if ((y != nullptr) != (out_crps != nullptr)) return fail(nullptr, NPBNN_E_ARG, "%s: y and out_crps go together", who);
     if (!out_quantile && !out_mean && !out_crps) return fail(nullptr, NPBNN_E_ARG, "%s: nothing asked for", who);
-    const bool f32 = value_type == NPBNN_VALUE_F32;
+    const bool f32 = d_mu.f32();
     auto value_at = [f32](const void* a, size_t i) { return f32 ? (double)static_cast<const float*>(a)[i] : static_cast<const double*>(a)[i]; };
     for (int64_t s = 0; s < n_samples; ++s)
         for (int64_t c = 0; c < n_cols; ++c) {
@@ -412,25 +370,19 @@ extern "C" int npbnn_op_mixture(int device, const void* mu, const void* sigma, i
         if (!std::isfinite(y[c])) return fail(nullptr, NPBNN_E_ARG, "%s: a y is NaN or infinite", who);
     if (n_cols == 0) return NPBNN_OK;
     HIP_TRY(nullptr, hipSetDevice(device));
-    const size_t esize = f32 ? 4 : 8;
-    const size_t n_el = (size_t)(n_samples - 1) * (size_t)col_stride + (size_t)n_cols;
-    const size_t n_sig = sigma_cols > 0 ? (size_t)n_samples * sigma_cols : n_el;
-    const size_t sig_bytes = sigma_cols > 0 ? n_sig * 8 : n_sig * esize;
-    DevBuf<double> d_mu, d_sg, d_y, d_out;                       // (d_mu, d_sg: bytes rounded up to whole doubles)
+    DevBuf<double> d_y, d_out;
     DevBuf<int> d_flag;
     const size_t nq = (size_t)n_probs * n_cols;
-    if ((rc = dev_alloc(nullptr, d_mu, (n_el * esize + 7) / 8))) return rc;
-    if ((rc = dev_alloc(nullptr, d_sg, (sig_bytes + 7) / 8))) return rc;
+    if ((rc = d_mu.upload(mu, n_samples, n_cols, col_stride))) return rc;
+    if ((rc = sigma_cols > 0 ? d_sg.upload(sigma, n_samples, sigma_cols, sigma_cols) : d_sg.upload(sigma, n_samples, n_cols, col_stride))) return rc;
     if ((rc = dev_alloc(nullptr, d_y, y ? (size_t)n_cols : 0))) return rc;
     if ((rc = dev_alloc(nullptr, d_out, nq + 2 * (size_t)n_cols))) return rc;
     if ((rc = dev_alloc(nullptr, d_flag, 1))) return rc;
-    HIP_TRY(nullptr, hipMemcpy(d_mu.get(), mu, n_el * esize, hipMemcpyHostToDevice));
-    HIP_TRY(nullptr, hipMemcpy(d_sg.get(), sigma, sig_bytes, hipMemcpyHostToDevice));
     if (y) HIP_TRY(nullptr, hipMemcpy(d_y.get(), y, (size_t)n_cols * 8, hipMemcpyHostToDevice));
     HIP_TRY(nullptr, hipMemset(d_flag.get(), 0, sizeof(int)));
-    p.mu = d_mu.get();
-    p.sg = sigma_cols > 0 ? nullptr : d_sg.get();
-    p.sg64 = sigma_cols > 0 ? d_sg.get() : nullptr;
+    p.mu = d_mu.buf.get();
+    p.sg = sigma_cols > 0 ? nullptr : d_sg.buf.get();
+    p.sg64 = sigma_cols > 0 ? d_sg.buf.get() : nullptr;
     p.n_cols = n_cols;
     p.col_stride = col_stride;
     p.cells_per_row = 1;
@@ -481,7 +433,6 @@ extern "C" int npbnn_predict_sets_predictive(npbnn_ctx* ctx, const double* W_set
     const size_t n_cells = (size_t)n_rows * T;
     for (size_t i = 0; targets && i < n_cells; ++i)
         if (!std::isfinite(targets[i])) return fail(ctx, NPBNN_E_ARG, "%s: target %zu of row %zu is NaN or infinite", who, i % T, i / T);
-    if ((rc = check_stack_budget(ctx, who, n_sets, n_rows, C))) return rc;
     hipStream_t st = tb.st;
     const size_t per_set = (size_t)n_rows * C;
     const size_t nq = (size_t)n_probs * n_cells;
@@ -489,7 +440,8 @@ extern "C" int npbnn_predict_sets_predictive(npbnn_ctx* ctx, const double* W_set
     DevBuf<float> stack;
     DevBuf<double> d_sig, d_y, d_out, d_part;
     DevBuf<int> d_flag;
-    if ((rc = dev_alloc(ctx, stack, (size_t)n_sets * per_set))) return rc;
+    // (with the output function applied a row of the stack holds T means followed by T sigmas; the identity has none to apply)
+    if ((rc = replay_into_stack(ctx, who, W_sets, act_prm_sets, n_sets, which, sp ? 1 : 0, tb, &stack))) return rc;
     if ((rc = dev_alloc(ctx, d_sig, sp ? 0 : (size_t)n_sets * T))) return rc;
     if ((rc = dev_alloc(ctx, d_y, targets ? n_cells : 0))) return rc;
     if ((rc = dev_alloc(ctx, d_out, nq + 2 * n_cells))) return rc;
@@ -499,8 +451,6 @@ extern "C" int npbnn_predict_sets_predictive(npbnn_ctx* ctx, const double* W_set
     if (!sp) HIP_TRY(ctx, hipMemcpyAsync(d_sig.get(), sigma_sets, (size_t)n_sets * T * sizeof(double), hipMemcpyHostToDevice, st));
     if (targets) HIP_TRY(ctx, hipMemcpyAsync(d_y.get(), targets, n_cells * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));                          // (sigma_sets and targets are pageable memory of the caller's)
-    // (with the output function applied a row of the stack holds T means followed by T sigmas; the identity has none to apply)
-    if ((rc = replay_sets(ctx, who, W_sets, act_prm_sets, n_sets, which, sp ? 1 : 0, stack.get(), SetSink()))) return rc;
     p.mu = stack.get();
     p.sg = sp ? stack.get() + T : nullptr;
     p.sg64 = sp ? nullptr : d_sig.get();

@@ -5,7 +5,7 @@
 // is not: more than 64 nodes, a contraction cut into K-slices).  A group whose scaled layer-0 weights leave the fp16 range repeats on the
 // exact float32 path - on the weight-streamed path, where the packing reports per set, only the set that left it.  What an entry does
 // with a group's float32 predictions is its sink.  NPBNN_INFO_REPLAY_PASSES / _MAX_GROUP: what the last replay launched.
-#include "npbnn_sets.hip.h"
+#include "npbnn_stack.hip.h"
 
 #include <cmath>
 
@@ -26,8 +26,8 @@ void load_group_slopes(npbnn_ctx* ctx, const double* act_prm_sets, int n_act, in
         for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
 }
 
-int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_rows, int C) {
-    size_t budget = kStackBytes;
+static int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_rows, int C) {
+    size_t budget = 1ull << 30;        // default budget of a float32 device stack [n_sets][n_rows][out_dim]
     if (const char* e = getenv("NPBNN_HPD_STACK_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
     const size_t row_bytes = (size_t)n_sets * C * sizeof(float);
     if ((size_t)n_rows * row_bytes > budget)
@@ -35,6 +35,14 @@ int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_
                     "(NPBNN_HPD_STACK_BYTES); at most %zu rows fit", who, n_sets, n_rows, C, (size_t)n_rows * row_bytes, budget,
                     budget / row_bytes);
     return NPBNN_OK;
+}
+
+int replay_into_stack(npbnn_ctx* ctx, const char* who, const double* W_sets, const double* act_prm_sets, int n_sets, int which, int apply_out_fn,
+                      const SetsTable& t, DevBuf<float>* stack) {
+    const int C = ctx->net.n_out;
+    int rc = check_stack_budget(ctx, who, n_sets, t.n_rows, C);
+    if (rc || (rc = dev_alloc(ctx, *stack, (size_t)n_sets * t.n_rows * C))) return rc;
+    return replay_sets(ctx, who, W_sets, act_prm_sets, n_sets, which, apply_out_fn, stack->get(), SetSink());
 }
 
 EvalParams predict_params(npbnn_ctx* ctx, const Dataset& d, float* y_out, int apply_out_fn) {

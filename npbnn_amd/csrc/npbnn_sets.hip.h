@@ -1,13 +1,13 @@
-// What the entries that run stored weight sets over a resident table share (npbnn_capi.hip: npbnn_predict_sets; npbnn_hpd.hip;
-// npbnn_importance.hip: npbnn_predict_sets_summary; npbnn_support.hip; npbnn_lppd.hip; npbnn_uncertainty.hip; npbnn_calibration.hip; npbnn_convergence.hip;
-// npbnn_pdp.hip, route 2):
+// What the entries that run stored weight sets over a resident table share (npbnn_capi.hip: npbnn_predict_sets; npbnn_importance.hip:
+// npbnn_predict_sets_summary; npbnn_support.hip; npbnn_lppd.hip; npbnn_uncertainty.hip; npbnn_calibration.hip; npbnn_pdp.hip, route 2;
+// and through npbnn_stack.hip.h npbnn_hpd.hip, npbnn_convergence.hip, npbnn_predictive.hip):
 // the replay of the sets group after group (replay_sets, npbnn_sets.hip) and the host helpers it is built from, the flag word's bits,
 // the launch shape of the streaming kernels, the HIP-event timer behind NPBNN_FI_TIMING, the fixed-order workgroup sum and the host
 // tail that adds its partials, and the host scaffold of an entry: open_sets_table (the checks before the device is touched; every
 // entry but npbnn_predict_sets), finish_sets_entry (the tail of the five entries that end in a final kernel and a flag word),
 // check_sigma_sets and PointOuts (npbnn_lppd.hip, npbnn_uncertainty.hip, npbnn_calibration.hip).  The device code those three fold
-// with - the softmax fold, softplus, the label check - is in npbnn_fold.hip.h, which has a rule on contraction of its own.  Nothing
-// here belongs to a single entry.  Not part of the ABI.
+// with - the softmax fold, softplus, the label check - is in npbnn_fold.hip.h, which has a rule on contraction of its own; the kStack*
+// limits, the tile and the stack of the column kernels are in npbnn_stack.hip.h.  Nothing here belongs to a single entry.  Not part of the ABI.
 #pragma once
 #include "npbnn_ctx.hip.h"
 
@@ -26,14 +26,6 @@ constexpr int kFiMaxBlocks = 2048;                 // memory-bound kernels: grid
 constexpr int kFlagBadRow = 1;                     // permutation index outside [0, n_rows)
 constexpr int kFlagNaN = 2;                        // a prediction is NaN
 constexpr int kFlagBadLabel = 4;                   // a label outside [0, C)
-
-// The column kernels over a sample stack [S][n_cols] (npbnn_hpd.hip, npbnn_convergence.hip): a workgroup of kStackThreads threads takes
-// a tile of adjacent columns into LDS.
-constexpr int kStackThreads = 256;
-constexpr int kStackMaxSamples = 16384;
-constexpr int kStackMaxTile = 64;                      // columns of a workgroup at most
-constexpr size_t kStackTileLds = 80 * 1024;            // LDS a tile may take when it holds more than one column (two per CU)
-constexpr size_t kStackBytes = 1ull << 30;             // default budget of a float32 device stack [n_sets][n_rows][out_dim]
 
 inline unsigned grid_for(long long items) {
     long long b = (items + kFiThreads - 1) / kFiThreads;
@@ -115,17 +107,6 @@ template <class T>
 int dev_alloc(npbnn_ctx* ctx, DevBuf<T>& b, size_t n) {
     return b.reserve(ctx, n ? n : 16 / sizeof(T));
 }
-
-// the smallest r with 2^r >= v
-inline int ilog2(long long v) {
-    int r = 0;
-    while ((1ll << r) < v) ++r;
-    return r;
-}
-
-// NPBNN_E_NOMEM through fail(ctx, ...) when the float32 stack [n_sets][n_rows][C] of `who` is over its byte budget: kStackBytes, or
-// NPBNN_HPD_STACK_BYTES from the environment.  The message names the largest row count that fits.
-int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_rows, int C);
 
 // How many of the sets s0, s0 + 1, ... share set s0's activation slopes [n_sets][n_act] (all of them when there are none), cap at most:
 // they travel together in one streaming read of X.

@@ -208,7 +208,7 @@ def mixture(mu, sigma, probs=(), y=None):
         raise ValueError("%s: %d samples, at most %d are supported" % (who, a.shape[0], MAX_SAMPLES))
     pr = check_probs(probs, who)
     n_samples, shape = a.shape[0], a.shape[1:]
-    v = np.ascontiguousarray(a.reshape(n_samples, -1), dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    v, kind = capi.value_array(a.reshape(n_samples, -1))
     n_cols = v.shape[1]
     sg = np.asarray(sigma)
     if sg.shape == a.shape:
@@ -238,7 +238,6 @@ def mixture(mu, sigma, probs=(), y=None):
     crps = np.empty(n_cols) if yy is not None else None
     if n_cols:
         lib, dev = _lib()
-        kind = capi.VALUE_F32 if v.dtype == np.float32 else capi.VALUE_F64
         _chk(lib, lib.npbnn_op_mixture(dev, v.ctypes.data, sg.ctypes.data, kind, n_samples, n_cols, n_cols, sigma_cols,
                                        capi.dptr(pr) if len(pr) else None, len(pr), capi.dptr(yy), capi.dptr(quant), capi.dptr(mean),
                                        capi.dptr(crps)))
@@ -254,13 +253,12 @@ def convergence(values, n_chains=1):
     a = np.asarray(values)
     if a.ndim != 2:
         raise ValueError("convergence: values must be [samples, columns], got shape %s" % (a.shape,))
-    v = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    v, kind = capi.value_array(a)
     n_draws = check_shape("convergence", v.shape[0], n_chains)
     n_cols = v.shape[1]
     rhat, ess = np.empty(n_cols), np.empty(n_cols)
     if n_cols == 0:
         return rhat, ess
     lib, dev = _lib()
-    kind = capi.VALUE_F32 if v.dtype == np.float32 else capi.VALUE_F64
     _chk(lib, lib.npbnn_op_convergence(dev, v.ctypes.data, kind, int(n_chains), n_draws, n_cols, n_cols, capi.dptr(rhat), capi.dptr(ess)))
     return rhat, ess

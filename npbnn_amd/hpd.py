@@ -32,7 +32,7 @@ def _window(n_samples, level):
 
 def _values(a):
     """float32 stays float32 (widths in float32, as upstream on a float32 array); anything else is taken as float64."""
-    v = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    v = capi.value_array(a)[0]
     if not np.all(np.isfinite(v)):
         raise ValueError("calcHPD: the data hold NaN or infinite values")
     return v
@@ -46,7 +46,7 @@ def _op_hpd(values, level):
     if n_cols == 0:
         return lo, hi
     lib, dev = _lib()
-    kind = capi.VALUE_F32 if values.dtype == np.float32 else capi.VALUE_F64
+    values, kind = capi.value_array(values)
     capi.check(lib, None, lib.npbnn_op_hpd(dev, values.ctypes.data, kind, n_samples, n_cols, n_cols, float(level),
                                            capi.dptr(lo), capi.dptr(hi)))
     return lo, hi
@@ -85,6 +85,11 @@ def stack_budget():
     return v if v > 0 else STACK_BYTES
 
 
+def stack_rows(n_samples, n_out):
+    """Rows of a table whose float32 device stack [samples, rows, outputs] fits ``stack_budget``."""
+    return max(1, stack_budget() // (n_samples * n_out * 4))
+
+
 def _hpd_row_blocks(blocks, post_samples, actFun, output_act_fun, level):
     """[(mean, lower, upper)] for each block of rows of a feature matrix, every stored sample replayed on it (the device seam).
     One device context serves every block: its matrix is replaced, the packed samples stay."""
@@ -99,7 +104,7 @@ def _rows_hpd(matrix, samples, act, output_act_fun, level, n_out):
     if len(matrix) == 0:
         return np.zeros((0, n_out)), np.zeros((0, n_out)), np.zeros((0, n_out))
     x = np.asarray(matrix, dtype=np.float64)
-    rows = max(1, stack_budget() // (len(samples) * n_out * 4))
+    rows = stack_rows(len(samples), n_out)
     blocks = [x[r:r + rows] for r in range(0, len(x), rows)]
     parts = _hpd_row_blocks(blocks, samples, act, output_act_fun, level)
     return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))

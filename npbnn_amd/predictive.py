@@ -27,6 +27,7 @@ mean and the scores come back."""
 import numpy as np
 
 from .files import load_obj
+from .hpd import stack_rows
 from .layers import output_kind
 from .stored import choose_table, open_checkpoint, open_predictor, sample_sigmas, sigma_matrix, target_matrix
 
@@ -146,12 +147,6 @@ def posterior_predictive(stack, kind="regression", sigma_sets=None, probs=DEFAUL
         res["crps_i"] = _crps(mu2, sig2, t.reshape(-1)).reshape(n_rows, n_targets)
         res["crps"] = np.sum(res["crps_i"], axis=0) / n_rows
     return res
-
-
-def stack_rows(n_samples, n_out):
-    """Rows of a table whose float32 device stack [samples, rows, outputs] fits the budget of ``get_posterior_hpd``."""
-    from .hpd import stack_budget
-    return max(1, stack_budget() // (n_samples * n_out * 4))
 
 
 def get_posterior_predictive(pkl_file, features=None, labels=None, probs=DEFAULT_PROBS, crps=True):

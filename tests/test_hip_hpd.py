@@ -9,7 +9,7 @@ import pytest
 import cases
 import hpd_cases
 import npbnn_amd as bn
-from npbnn_amd import _capi as capi
+from npbnn_amd import _capi as capi, device_ops
 
 pytestmark = pytest.mark.gpu
 
@@ -57,6 +57,31 @@ def test_posterior_hpd_keeps_trailing_shape():
     lo, hi = bn.posterior_hpd(x, 0.9)
     want = hpd_cases.hpd_columns(x, 0.9)
     assert lo.shape == (4, 3) and np.array_equal(lo, want[0]) and np.array_equal(hi, want[1])
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("S,n_cols", [(17, 1), (17, 65), (257, 130)])
+def test_op_hpd_strided_equals_packed_and_a_column_does_not_depend_on_its_tile(S, n_cols, dtype):
+    """The columns sit in a wider array (col_stride = n_cols + 3): bounds byte for byte those of the packed call.  The columns are five
+    distinct ones over and over, ties included, so a copy lands in another tile and at another place in it (65 columns of 17: a
+    tile of 64 and one of 1; 130 of 257: tiles of 32 in float32 and of 16 in float64, the last of 2) and gives the bytes of the first."""
+    rs = np.random.default_rng(1000 * S + n_cols)
+    base = rs.standard_normal((S, 5)).astype(dtype)
+    base[:, 3] = np.round(base[:, 3] * 4)
+    idx = np.arange(n_cols) % 5
+    v = np.ascontiguousarray(base[:, idx])
+    lo, hi = bn.posterior_hpd(v, 0.9)
+    want = hpd_cases.hpd_columns(v, 0.9)
+    assert np.array_equal(lo, want[0]) and np.array_equal(hi, want[1])
+    for j in range(n_cols):
+        assert lo[j].tobytes() == lo[idx[j]].tobytes() and hi[j].tobytes() == hi[idx[j]].tobytes(), j
+    lib, dev = device_ops._lib()
+    wide = np.full((S, n_cols + 3), 7.0, dtype=dtype)
+    wide[:, :n_cols] = v
+    lo2, hi2 = np.empty(n_cols), np.empty(n_cols)
+    rc = lib.npbnn_op_hpd(dev, wide.ctypes.data, capi.VALUE_F32 if dtype == "float32" else capi.VALUE_F64, S, n_cols, n_cols + 3, 0.9,
+                          capi.dptr(lo2), capi.dptr(hi2))
+    assert rc == 0 and lo2.tobytes() == lo.astype(np.float64).tobytes() and hi2.tobytes() == hi.astype(np.float64).tobytes()
 
 
 # ---- the fused entry: replay into a device stack, one HPD launch

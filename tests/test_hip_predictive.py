@@ -87,6 +87,37 @@ def test_mixture_global_memory_route():
     assert np.array_equal(mean, pc.mean_of(mu))
 
 
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("sigma_cols", [0, 3], ids=["per_cell", "per_sample"])
+@pytest.mark.parametrize("S,n_cols", [(S, n) for S in (2, 65) for n in (1, 65)])
+def test_mixture_strided_equals_packed_and_a_cell_does_not_depend_on_its_tile(S, n_cols, sigma_cols, dtype):
+    """mu (and a per-cell sigma beside it) sit in wider arrays (col_stride = n_cols + 3): quantiles, mean and CRPS byte for byte
+    those of the packed call.  The cells are six distinct ones over and over (cell c of a [S, 3] sigma reads column c % 3, which
+    c % 6 fixes), so of 65 cells - a tile of 64 and one of 1 - a copy lands in the other tile and at other places, and gives the
+    bytes of the first."""
+    mu6, sg6, y6 = pc.make("random", S, 6, sigma_cols)
+    idx = np.arange(n_cols) % 6
+    mu = np.ascontiguousarray(mu6[:, idx]).astype(dtype)
+    sg = sg6 if sigma_cols else np.ascontiguousarray(sg6[:, idx]).astype(dtype)
+    y = np.ascontiguousarray(y6[idx])
+    q, mean, crps = device_ops.mixture(mu, sg, pc.PROBS, y)
+    for j in range(n_cols):
+        for a in (q.T, mean, crps):
+            assert a[j].tobytes() == a[idx[j]].tobytes(), j
+    lib, dev = device_ops._lib()
+    wide = np.full((S, n_cols + 3), 7.0, dtype=dtype)
+    wide[:, :n_cols] = mu
+    wide_sg = sg
+    if not sigma_cols:
+        wide_sg = np.full((S, n_cols + 3), 7.0, dtype=dtype)
+        wide_sg[:, :n_cols] = sg
+    pr = np.asarray(pc.PROBS, dtype=np.float64)
+    q2, mean2, crps2 = np.empty((len(pr), n_cols)), np.empty(n_cols), np.empty(n_cols)
+    rc = lib.npbnn_op_mixture(dev, wide.ctypes.data, wide_sg.ctypes.data, capi.VALUE_F32 if dtype == "float32" else capi.VALUE_F64, S, n_cols,
+                              n_cols + 3, sigma_cols, capi.dptr(pr), len(pr), capi.dptr(y), capi.dptr(q2), capi.dptr(mean2), capi.dptr(crps2))
+    assert rc == 0 and q2.tobytes() == q.tobytes() and mean2.tobytes() == mean.tobytes() and crps2.tobytes() == crps.tobytes()
+
+
 def test_mixture_keeps_the_trailing_shape_and_refuses():
     mu, sg, y = pc.make("random", 7, 6)
     flat = device_ops.mixture(mu, sg, (0.1, 0.9), y)
