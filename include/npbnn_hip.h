@@ -209,7 +209,10 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
        NPBNN_INFO_SALIENCY_ROUTE = 27, NPBNN_INFO_SALIENCY_FOLD_NS = 28,
        /* the route that served the last npbnn_predict_shapley (1 or 2; 0 before any call, and after one that was refused), and with
         * NPBNN_FI_TIMING=1 the device time in nanoseconds of its walk kernels (0 otherwise) */
-       NPBNN_INFO_SHAPLEY_ROUTE = 29, NPBNN_INFO_SHAPLEY_WALK_NS = 30 };
+       NPBNN_INFO_SHAPLEY_ROUTE = 29, NPBNN_INFO_SHAPLEY_WALK_NS = 30,
+       /* with NPBNN_FI_TIMING=1 the device time in nanoseconds of the last npbnn_predict_sets_loo's final kernel (0 otherwise, and
+        * after a call refused before any launch); its passes and its log-likelihood launches are in NPBNN_INFO_SUMMARY_PASS_NS / _ACC_NS */
+       NPBNN_INFO_LOO_FINAL_NS = 31 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -552,6 +555,28 @@ int npbnn_predict_sets_predictive(npbnn_ctx* ctx, const double* W_sets, const do
                                   const double* sigma_sets, const double* probs, int32_t n_probs, const double* targets,
                                   double* out_quantile, double* out_mean, double* out_crps, double* out_totals);
 
+/* Pareto-smoothed importance-sampling leave-one-out cross-validation (PSIS-LOO; Vehtari, Gelman, Gabry 2017; Vehtari et al. 2024) of
+ * the n_sets stored samples on the resident matrix `which`, against the labels (NPBNN_LIK_CATEGORICAL) or targets (NPBNN_LIK_GAUSS,
+ * sigma_sets [n_sets][out_dim]) set on it; lik_kind, sigma_sets and the per-row terms ll[s][i] as in npbnn_predict_sets_lppd, every
+ * other kind refused in the same words.  The sets replay as there (pre-output float32 values, grouping without effect on a bit); each
+ * group's ll goes into a float64 device matrix [n_sets][n_rows], and one launch of the kernel of npbnn_op_psis (below, which has the
+ * definition) reads it once.  2 <= n_sets <= 16384.  The matrix is budgeted like the stack of npbnn_predict_sets_hpd: n_sets * n_rows * 8
+ * bytes against 1 GiB (NPBNN_HPD_STACK_BYTES in the environment overrides it); NPBNN_E_NOMEM before any allocation names the rows that
+ * fit, and the caller goes block by block of rows (a row's results depend on its own column alone).
+ *   out_elpd, out_lppd, out_k   [n_rows] each: elpd_loo_i, lppd_i and the Pareto shape k of the row (+inf where the tail holds four
+ *                               values or fewer: plain importance sampling)
+ *   out_log_lik_sample          [n_sets], or NULL: sum_i ll[s][i], from per-workgroup float64 partials added in a fixed order
+ *   out_log_lik                 [n_sets][n_rows], or NULL: the matrix itself
+ * Every summation order is fixed: two calls return the same bytes.  NPBNN_E_ARG before the device is touched: NULL W_sets or outputs,
+ * n_sets < 2 or above 16384, a lik_kind that is not served, sigma_sets that does not go with it or is not positive and finite, an
+ * output function that does not go with the likelihood, targets of another width; NPBNN_E_STATE without npbnn_set_arch, data, labels
+ * or targets.  NPBNN_E_ARG before any evaluation: a label outside [0, out_dim); after the passes: a prediction that is NaN or a
+ * log-likelihood that is not finite.  A call refused before any evaluation leaves 0 in NPBNN_INFO_SUMMARY_PASS_NS, _ACC_NS and
+ * NPBNN_INFO_LOO_FINAL_NS. */
+int npbnn_predict_sets_loo(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, int which, int lik_kind,
+                           const double* sigma_sets, double* out_elpd, double* out_lppd, double* out_k, double* out_log_lik_sample,
+                           double* out_log_lik);
+
 /* ---- timing hook for bench.py: launches the evaluation kernels `iters` times on the ctx stream
  * with weights already resident and returns the mean duration of the dominant kernel (HIP events
  * around each launch) and of the whole evaluation, in milliseconds. */
@@ -734,6 +759,28 @@ int npbnn_op_sse(int device, const double* pred, const double* targets, int64_t 
 #define NPBNN_VALUE_F32 1
 int npbnn_op_hpd(int device, const void* values, int value_type, int64_t n_samples, int64_t n_cols, int64_t col_stride, double level,
                  double* out_lo, double* out_hi);
+
+/* npbnn_op_psis: PSIS-LOO of each of n_cols columns of log-likelihoods, column i's n_samples = S values ll_s at
+ * values[s * col_stride + i] (value_type NPBNN_VALUE_F64 or NPBNN_VALUE_F32), 2 <= S <= 16384, every value finite.  All arithmetic
+ * is float64.  Per column:
+ *   x_s   = -ll_s - max_t(-ll_t)                              (log importance ratios, the largest 0)
+ *   M     = ceil(min(S / 5, 3 sqrt(S)));   cut = max((M + 1)-th largest x, log(DBL_MIN));   ecut = exp(cut)
+ *   tail  = the x_s > cut (strictly), ascending x_(1) <= ... <= x_(n); n may be below M under ties, or 0
+ *   n <= 4:  k = +inf and every log weight lw_s = x_s (plain importance sampling)
+ *   n >  4:  t_j = exp(x_(j)) - ecut; (k, sigma) = gpdfit(t); the j-th smallest tail value gets
+ *            lw = min(log(sigma * expm1(-k * log1p(-p_j)) / k + ecut), 0), p_j = (j - 0.5) / n (k == 0: -sigma * log1p(-p_j) for the
+ *            quotient); lw_s = x_s outside the tail
+ *   elpd_loo_i = logsumexp_s(lw_s + ll_s) - logsumexp_s(lw_s)  (each with its maximum taken out first)
+ *   lppd_i     = logsumexp_s(ll_s) - log S
+ * gpdfit is Zhang and Stephens (2009) with the weakly informative prior of loo / ArviZ, on t ascending of length n:
+ *   m = 30 + floor(sqrt(n));  b_q = (1 - sqrt(m / (q - 0.5))) / (3 t[floor(n / 4 + 0.5) - 1]) + 1 / t[n - 1], q = 1..m
+ *   k_q = mean_j log1p(-b_q t_j);  L_q = n (log(-b_q / k_q) - k_q - 1);  w_q = 1 / sum_r exp(L_r - L_q)
+ *   the q with w_q >= 10 * 2^-52 are kept and renormalised;  b = sum_q b_q w_q;  k' = mean_j log1p(-b t_j)
+ *   sigma = -k' / b;  k = (n k' + 5) / (n + 10)
+ * out_elpd, out_lppd, out_k [n_cols].  The bits of a column's results depend on its values alone.  NPBNN_E_ARG: S outside the
+ * limits, or a value that is NaN or infinite.  n_cols == 0 returns at once. */
+int npbnn_op_psis(int device, const void* values, int value_type, int64_t n_samples, int64_t n_cols, int64_t col_stride, double* out_elpd,
+                  double* out_lppd, double* out_k);
 
 /* npbnn_op_convergence: split R-hat and effective sample size of each of n_cols columns, column c's values at
  * values[s * col_stride + c] (value_type NPBNN_VALUE_F64 or NPBNN_VALUE_F32).  All arithmetic is float64.  A column is M = n_chains

@@ -38,6 +38,7 @@ from .saliency import get_saliency, saliency  # noqa: F401
 from .shapley import get_shapley, shapley  # noqa: F401
 from .hpd import calcHPD, get_posterior_hpd, posterior_hpd  # noqa: F401
 from .lppd import get_posterior_lppd, posterior_lppd  # noqa: F401
+from .loo import get_posterior_loo, loo_compare, posterior_loo  # noqa: F401
 from .uncertainty import get_posterior_uncertainty, posterior_uncertainty  # noqa: F401
 from .calibration import get_posterior_calibration, posterior_calibration  # noqa: F401
 from .convergence import get_posterior_convergence, posterior_convergence  # noqa: F401

@@ -44,6 +44,7 @@ INFO_SALIENCY_ROUTE = 27
 INFO_SALIENCY_FOLD_NS = 28
 INFO_SHAPLEY_ROUTE = 29
 INFO_SHAPLEY_WALK_NS = 30
+INFO_LOO_FINAL_NS = 31
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
 E_STATE = -2
@@ -165,6 +166,7 @@ SIGNATURES = {
                                              _DP, C.c_int32, _DP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _DP,
                                              C.POINTER(C.c_uint8)]),
     "npbnn_predict_sets_lppd": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "npbnn_predict_sets_loo": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, C.c_int, _DP, _DP, _DP, _DP, _DP, _DP]),
     "npbnn_predict_sets_uncertainty": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, _DP, _DP, _DP, _DP, _DP]),
     "npbnn_predict_sets_calibration": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int, _DP, C.c_int32, _DP, C.c_int32, _DP, _DP, _DP,
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), _DP, _DP]),
@@ -192,6 +194,7 @@ SIGNATURES = {
                                      C.POINTER(C.c_int64)]),
     "npbnn_op_sse": (C.c_int, [C.c_int, _DP, _DP, C.c_int64, C.c_int32, C.c_int32, C.c_int, _DP]),
     "npbnn_op_hpd": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, _DP, _DP]),
+    "npbnn_op_psis": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, _DP, _DP, _DP]),
     "npbnn_op_convergence": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _DP, _DP]),
     "npbnn_op_mixture": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _DP, C.c_int32, _DP, _DP,
                                    _DP, _DP]),

@@ -444,6 +444,37 @@ class HipContext:
         return dict(lppd=float(totals[0]), mean_log_lik=float(totals[1]), p_waic=float(totals[2]), log_lik_sample=trace,
                     lppd_i=point[0], mean_log_lik_i=point[1], p_waic_i=point[2])
 
+    def predict_sets_loo(self, weight_sets, lik_kind, sigma_sets=None, act_prm_sets=None, which=capi.TRAIN, log_lik=False):
+        """PSIS leave-one-out cross-validation of several weight sets on the resident matrix, against the labels (``lik_kind``
+        LIK_CATEGORICAL) or targets (LIK_GAUSS, ``sigma_sets`` [n_sets, n_targets] or [n_sets]) set on it
+        (npbnn_predict_sets_loo; ``npbnn_amd.loo`` has the definition).  A dict with the pointwise ``elpd_loo_i``, ``lppd_i`` and
+        ``pareto_k`` [n_rows], ``log_lik_sample`` [n_sets] and, with ``log_lik``, the float64 matrix ``log_lik`` [n_sets, n_rows]
+        (None otherwise).  The sets replay as in ``predict_sets_lppd``; the matrix stays on the device unless asked for, under
+        the byte budget of ``predict_sets_hpd``'s stack (NpbnnError E_NOMEM names the rows that fit)."""
+        from .loo import check_samples
+        who = "predict_sets_loo"
+        if lik_kind not in (capi.LIK_CATEGORICAL, capi.LIK_GAUSS):
+            raise ValueError("%s: lik_kind must be LIK_CATEGORICAL or LIK_GAUSS (predicted-sigma regression and the count likelihoods "
+                             "are out of scope), got %r" % (who, lik_kind))
+        packed, ap, n_sets = self._pack_sets(weight_sets, act_prm_sets, who)
+        check_samples(n_sets, who)
+        n_rows = self.n_rows[which]
+        if n_rows < 1:
+            raise ValueError("%s: the matrix has no rows" % who)
+        sig = None
+        if lik_kind == capi.LIK_GAUSS:
+            if sigma_sets is None:
+                raise ValueError("%s: the Gaussian likelihood needs sigma_sets" % who)
+            sig = sigma_matrix(sigma_sets, n_sets, self.n_out, who)
+        elif sigma_sets is not None:
+            raise ValueError("%s: sigma_sets goes with LIK_GAUSS only" % who)
+        elpd, lppd, k = (np.empty(n_rows, dtype=np.float64) for _ in range(3))
+        trace = np.empty(n_sets, dtype=np.float64)
+        matrix = np.empty((n_sets, n_rows), dtype=np.float64) if log_lik else None
+        self._chk(self._lib.npbnn_predict_sets_loo(self._ctx, capi.dptr(packed), capi.dptr(ap), n_sets, which, int(lik_kind), capi.dptr(sig),
+                                                   capi.dptr(elpd), capi.dptr(lppd), capi.dptr(k), capi.dptr(trace), capi.dptr(matrix)))
+        return dict(elpd_loo_i=elpd, lppd_i=lppd, pareto_k=k, log_lik_sample=trace, log_lik=matrix)
+
     def predict_sets_uncertainty(self, weight_sets, act_prm_sets=None, which=capi.TRAIN, pointwise=True):
         """Uncertainty decomposition of several weight sets' predictions on the resident matrix (npbnn_predict_sets_uncertainty); the
         kind follows the architecture's output function, and no labels or targets are read.  Softmax: a dict with ``mean_prob``

@@ -968,6 +968,7 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     if (what == NPBNN_INFO_REPLAY_PASSES) { *out = ctx->replay_passes; return NPBNN_OK; }
     if (what == NPBNN_INFO_REPLAY_MAX_GROUP) { *out = ctx->replay_max_group; return NPBNN_OK; }
     if (what == NPBNN_INFO_CALIBRATION_FINAL_NS) { *out = ctx->calibration_ns; return NPBNN_OK; }
+    if (what == NPBNN_INFO_LOO_FINAL_NS) { *out = ctx->loo_ns; return NPBNN_OK; }
     if (what >= NPBNN_INFO_PERMUTE_NS && what <= NPBNN_INFO_CONVERGENCE_FINAL_NS) { *out = ctx->fi_ns[what - NPBNN_INFO_PERMUTE_NS]; return NPBNN_OK; }
     if (ctx->arch_set && ctx->wide && (what == NPBNN_INFO_WAVES_PER_BLOCK || what == NPBNN_INFO_MAX_CANDIDATES || what == NPBNN_INFO_FAST_TAILS)) {
         *out = what == NPBNN_INFO_WAVES_PER_BLOCK ? 4 : what == NPBNN_INFO_MAX_CANDIDATES ? 1 : 0;      // (group passes: one chain per pass; what a replay of stored sets carried: NPBNN_INFO_REPLAY_MAX_GROUP)

@@ -243,6 +243,7 @@ struct npbnn_ctx : npbnn_ctx_streams {
                                    // npbnn_predict_sets_lppd's, npbnn_predict_sets_uncertainty's and npbnn_predict_sets_convergence's final kernels (NPBNN_INFO_PERMUTE_NS ...;
                                    // every entry that goes through replay_sets, npbnn_sets.hip.h, leaves its passes and sinks in [1], [2])
     int calibration_ns = 0;        // NPBNN_FI_TIMING: the last npbnn_predict_sets_calibration's final kernel (NPBNN_INFO_CALIBRATION_FINAL_NS; fi_ns is full)
+    int loo_ns = 0;                // NPBNN_FI_TIMING: the last npbnn_predict_sets_loo's psis_kernel (NPBNN_INFO_LOO_FINAL_NS)
     int replay_passes = 0, replay_max_group = 0;  // the last replay_sets: passes over X (float32 repeats included), most sets in one (NPBNN_INFO_REPLAY_*)
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     int ale_route = 0;             // route of the last npbnn_predict_ale: 1 both edges from one read of X, 2 per edge; 0 none, or refused (NPBNN_INFO_ALE_ROUTE)

@@ -26,13 +26,13 @@ void load_group_slopes(npbnn_ctx* ctx, const double* act_prm_sets, int n_act, in
         for (int l = 0; l < n_act; ++l) ctx->net.act_prm[l] = (float)act_prm_sets[(size_t)s0 * n_act + l];
 }
 
-static int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_rows, int C) {
-    size_t budget = 1ull << 30;        // default budget of a float32 device stack [n_sets][n_rows][out_dim]
+int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_rows, int C, size_t elem_bytes, const char* type) {
+    size_t budget = 1ull << 30;        // default budget of a device stack [n_sets][n_rows][out_dim]
     if (const char* e = getenv("NPBNN_HPD_STACK_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-    const size_t row_bytes = (size_t)n_sets * C * sizeof(float);
+    const size_t row_bytes = (size_t)n_sets * C * elem_bytes;
     if ((size_t)n_rows * row_bytes > budget)
-        return fail(ctx, NPBNN_E_NOMEM, "%s: the [%d][%lld][%d] float32 stack takes %zu bytes, over the budget of %zu "
-                    "(NPBNN_HPD_STACK_BYTES); at most %zu rows fit", who, n_sets, n_rows, C, (size_t)n_rows * row_bytes, budget,
+        return fail(ctx, NPBNN_E_NOMEM, "%s: the [%d][%lld][%d] %s stack takes %zu bytes, over the budget of %zu "
+                    "(NPBNN_HPD_STACK_BYTES); at most %zu rows fit", who, n_sets, n_rows, C, type, (size_t)n_rows * row_bytes, budget,
                     budget / row_bytes);
     return NPBNN_OK;
 }

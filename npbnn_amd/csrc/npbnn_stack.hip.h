@@ -76,6 +76,11 @@ struct StackInput {
     DevBuf<double> buf;
 };
 
+// NPBNN_E_NOMEM through fail(ctx, ...) when a device array [n_sets][n_rows][C] of elem_bytes-wide `type` values is over the byte
+// budget of a stack (1 GiB, or NPBNN_HPD_STACK_BYTES from the environment); the message names the largest row count that fits.
+int check_stack_budget(npbnn_ctx* ctx, const char* who, int n_sets, long long n_rows, int C, size_t elem_bytes = sizeof(float),
+                       const char* type = "float32");
+
 // The sets replayed (replay_sets) into *stack, [n_sets][t.n_rows][outputs] float32 on the device, allocated here.  NPBNN_E_NOMEM
 // through fail(ctx, ...) before anything is allocated when the stack is over its byte budget (check_stack_budget, npbnn_sets.hip:
 // 1 GiB, or NPBNN_HPD_STACK_BYTES from the environment); the message names the largest row count that fits.

@@ -262,3 +262,24 @@ def convergence(values, n_chains=1):
     lib, dev = _lib()
     _chk(lib, lib.npbnn_op_convergence(dev, v.ctypes.data, kind, int(n_chains), n_draws, n_cols, n_cols, capi.dptr(rhat), capi.dptr(ess)))
     return rhat, ess
+
+
+def psis(log_lik):
+    """npbnn_op_psis on a [S, n_cols] array of log-likelihoods: (elpd_loo_i, lppd_i, pareto_k) as float64 [n_cols]
+    (npbnn_amd/loo.py has the definition).  float32 stays float32 on its way to the device, anything else is taken as float64; the
+    arithmetic is float64 either way."""
+    from .loo import check_samples
+    a = np.asarray(log_lik)
+    if a.ndim != 2:
+        raise ValueError("psis: log_lik must be [samples, columns], got shape %s" % (a.shape,))
+    v, kind = capi.value_array(a)
+    check_samples(v.shape[0], "psis")
+    if not np.all(np.isfinite(v)):
+        raise ValueError("psis: log_lik holds NaN or infinite values")
+    n_cols = v.shape[1]
+    elpd, lppd, k = np.empty(n_cols), np.empty(n_cols), np.empty(n_cols)
+    if n_cols == 0:
+        return elpd, lppd, k
+    lib, dev = _lib()
+    _chk(lib, lib.npbnn_op_psis(dev, v.ctypes.data, kind, v.shape[0], n_cols, n_cols, capi.dptr(elpd), capi.dptr(lppd), capi.dptr(k)))
+    return elpd, lppd, k

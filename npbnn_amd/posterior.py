@@ -140,6 +140,37 @@ class _SamplePredictor:
             ctx.set_targets(labels)
         return ctx.predict_sets_lppd(self._packed, lik_kind, sigma_sets=sigma_sets, act_prm_sets=self._slopes, pointwise=pointwise)
 
+    def loo(self, features, labels, lik_kind, sigma_sets=None, log_lik=False, block_rows=None):
+        """``posterior_loo``'s dict, with ``log_lik_sample`` [S] and (``log_lik``) the matrix ``log_lik`` [S, N] beside it, for the
+        stored samples on ``features`` against ``labels`` (class indices, LIK_CATEGORICAL) or targets (LIK_GAUSS, ``sigma_sets`` per
+        sample): the log-likelihood matrix stays on the device (npbnn_predict_sets_loo).  ``block_rows``: the most rows a device
+        matrix may hold.  A table of more rows is uploaded whole - the scales of the first layer's half-precision split are the
+        whole table's - and served block by block as the context's second table, labels or targets set per block; a row's
+        results do not depend on the blocks, and the totals are formed from the concatenated arrays.  A custom output callable has
+        no device route: its stack is built on the host and goes through ``posterior_loo``."""
+        from .loo import check_samples, loo_totals, posterior_loo
+        check_samples(len(self._packed), "loo")
+        if self.custom_output:
+            from .lppd import log_lik_of_stack
+            ll = log_lik_of_stack(self.predict(features), labels, lik_kind, sigma_sets)
+            return dict(posterior_loo(ll), log_lik_sample=np.sum(ll, axis=1), log_lik=ll if log_lik else None)
+        ctx = self._load(features)
+        kw = dict(sigma_sets=sigma_sets, act_prm_sets=self._slopes, log_lik=log_lik)
+        set_y = ctx.set_labels if lik_kind == capi.LIK_CATEGORICAL else ctx.set_targets
+        if block_rows is None or block_rows >= len(features):
+            set_y(labels)
+            parts = [ctx.predict_sets_loo(self._packed, lik_kind, **kw)]
+        else:
+            parts = []
+            for r in range(0, len(features), block_rows):
+                ctx.set_data(features[r:r + block_rows], capi.TEST)
+                set_y(labels[r:r + block_rows], capi.TEST)
+                parts.append(ctx.predict_sets_loo(self._packed, lik_kind, which=capi.TEST, **kw))
+        res = loo_totals(*(np.concatenate([p[k] for p in parts]) for k in ("elpd_loo_i", "lppd_i", "pareto_k")), len(self._packed))
+        res["log_lik_sample"] = np.sum([p["log_lik_sample"] for p in parts], axis=0)
+        res["log_lik"] = np.concatenate([p["log_lik"] for p in parts], axis=1) if log_lik else None
+        return res
+
     def uncertainty(self, features, kind, sigma_sets=None, pointwise=True):
         """``posterior_uncertainty``'s dict (without the counts) for the stored samples on ``features``, ``kind``
         ``"classification"``, ``"regression"`` (``sigma_sets`` per sample: the device returns mean and epistemic variance, and the
