@@ -212,7 +212,10 @@ enum { NPBNN_INFO_L0_F16 = 1, NPBNN_INFO_WAVES_PER_BLOCK = 2, NPBNN_INFO_N_CU = 
        NPBNN_INFO_SHAPLEY_ROUTE = 29, NPBNN_INFO_SHAPLEY_WALK_NS = 30,
        /* with NPBNN_FI_TIMING=1 the device time in nanoseconds of the last npbnn_predict_sets_loo's final kernel (0 otherwise, and
         * after a call refused before any launch); its passes and its log-likelihood launches are in NPBNN_INFO_SUMMARY_PASS_NS / _ACC_NS */
-       NPBNN_INFO_LOO_FINAL_NS = 31 };
+       NPBNN_INFO_LOO_FINAL_NS = 31,
+       /* with NPBNN_FI_TIMING=1 the device time in nanoseconds of the last npbnn_loglik_grad's phase 1 (one thread per row) and of its
+        * phase 2 (the products over the rows and the reduce kernel), over every chunk (0 otherwise, and after a refused call) */
+       NPBNN_INFO_GRAD_ROWS_NS = 32, NPBNN_INFO_GRAD_FOLD_NS = 33 };
 int npbnn_set_option(npbnn_ctx* ctx, int option, int value);
 int npbnn_get_info(npbnn_ctx* ctx, int what, int* out);
 
@@ -308,6 +311,52 @@ int npbnn_predict_ale(npbnn_ctx* ctx, const double* W_sets, const double* act_pr
  * npbnn_set_arch or without data on `which`. */
 int npbnn_predict_saliency(npbnn_ctx* ctx, const double* W_sets, const double* act_prm_sets, int32_t n_sets, const double* col_override, int which,
                            int apply_out_fn, double* out_mean, double* out_abs, double* out_sq);
+
+/* ---- the log-likelihood and its gradient with respect to the WEIGHTS.  np_bnn has no counterpart: it takes a starting point trained
+ * elsewhere (get_weights_from_tensorflow_model, np_bnn/BNN_lib.py:601-624); npbnn_amd/gradient.py builds map_estimate on this entry.
+ * Arguments as npbnn_eval's.  With z the last layer's values of row i of the resident matrix `which` after col_override (after the
+ * activation where arch.final_act is set),
+ *   out->loglik = sum_i l_i        out_grad [n_weights] = sum_i d l_i / d W
+ * out_grad in packed-weight order: the layer matrices concatenated, each row-major, the bias in column 0 where the layer has one.
+ *   NPBNN_LIK_CATEGORICAL      l_i = lik_temp w_i log softmax(z)_{y_i};  d l_i / d z_c = lik_temp w_i (delta(c, y_i) - p_c).  w_i: the
+ *                              instance weight times the class weight of y_i, each 1 where npbnn_set_row_weights gave none, as
+ *                              npbnn_eval applies them: on the training table only.
+ *   NPBNN_LIK_GAUSS            l_i = lik_temp sum_t norm.logpdf(y_it, z_t, sigma_t);  d l_i / d z_t = lik_temp (y_it - z_t) / sigma_t^2.
+ *                              sigma (k values) is required: NULL, the empirical sigma, is NPBNN_E_ARG.  out->sigma, sum_r and sum_r2
+ *                              are filled as npbnn_eval fills them.
+ *   NPBNN_LIK_GAUSS_PRED_SIGMA mu = z[:k], s = softplus(z[k:]), l_i = lik_temp sum_t norm.logpdf(y_it, mu_t, s_t);
+ *                              d l / d z_t = lik_temp (y - mu) / s^2,  d l / d z_{k+t} = lik_temp ((y - mu)^2 / s^3 - 1 / s) sigmoid(z_{k+t}).
+ * The count likelihoods and NPBNN_LIK_NONE are refused with NPBNN_E_ARG.  Below the outputs the chain rule is npbnn_predict_saliency's:
+ * every activation's derivative on the branch the forward pass takes, the last layer's where arch.final_act is set, the slopes from
+ * act_prm.  With delta_l the derivative with respect to layer l's pre-activation and h_(l-1) that layer's input (the row of X for
+ * l = 0), d l_i / d W_l = delta_l h_(l-1)^T; a bias column receives sum_i delta_l; a column of layer 0 whose feature col_override
+ * replaces by the constant c_j receives c_j times layer 0's bias sum - the derivative of what the forward pass computes.  The
+ * derivative with respect to the slopes is not returned.
+ * One route, every network the library takes at runtime widths, in two phases over a chunk of rows.  Phase 1, one thread per row:
+ * forward from the float32 blocks of npbnn_predict_saliency's route 2, the row's log-likelihood term, and the backward pass of that
+ * scalar down to layer 0; every layer's values and deltas stay in a device scratch, layer 0's delta row-major.  Phase 2: the products
+ * whose reduction dimension is the rows - layer 0's [H0 x rows] [rows x in_dim] against X itself on v_mfma_f32_32x32x2_f32, a wave
+ * per slot of rows, 32 hidden units and up to 128 features; the later layers in a plain kernel.  Sums over rows run in float32
+ * inside one slot of 256 rows (kGradSlotRows), from there on as float64 partials in device memory that a reduce kernel adds in a
+ * fixed order; lik_temp multiplies the float64 totals.  No floating-point atomics: the same input gives the same bits on every
+ * call.  It reads the float32 matrix only: NPBNN_OPT_L0_PRECISION plays no part and there is no fp16-range repeat.  Scratch and
+ * partials have a byte budget (128 MiB; NPBNN_GRAD_SCRATCH_BYTES in the environment overrides it): a larger table runs in chunks
+ * of rows (npbnn_attrib_grad_of).  With NPBNN_FI_TIMING=1 the device time of phase 1 goes to NPBNN_INFO_GRAD_ROWS_NS and that of
+ * phase 2, the reduce kernel included, to NPBNN_INFO_GRAD_FOLD_NS (0 otherwise, and after a refused call).  The context keeps the
+ * call's device buffers - up to the scratch budget, and the float32 blocks - for the next call; npbnn_set_data and npbnn_share_data
+ * free them, npbnn_destroy too.  Measured on an MI355X (tools/time_grad.py; the entry and, in a run of their own, the two phases
+ * as medians of 200 calls, in two fresh processes):
+ * 100k x 256, [32, 8], 10 classes 0.64-0.65 ms a call (phase 1 0.34, phase 2 0.17), 1M x 64, [16, 4], 2 Gaussian targets
+ * 1.18-1.20 ms (0.56, 0.56); npbnn_eval of the same weights 0.08-0.09 and 0.10-0.11 ms, the definition in numpy 80-82 and 320-341 ms.  Against float64
+ * (tests/test_hip_grad.py): the largest error is 0.23 of a bar of 16 times the larger of a float32 restatement's distance and
+ * 2^-24 sum_i |delta_i| |h_i|, per layer; the log-likelihood within a relative 3.3e-8.
+ * NPBNN_E_ARG before any launch: a null W_packed, out or out_grad, `which` not 0 or 1, a table without rows, a likelihood other
+ * than the three, NPBNN_LIK_GAUSS without sigma, NPBNN_LIK_GAUSS_PRED_SIGMA with out_dim other than 2 k, targets of another width;
+ * after the launches: a label outside [0, out_dim).  NPBNN_E_STATE: no npbnn_set_arch, no data, labels or targets on `which`, or a
+ * row-sharded context (npbnn_set_row_shard).  A refused call leaves out and out_grad untouched.  Non-finite results are returned
+ * as they are. */
+int npbnn_loglik_grad(npbnn_ctx* ctx, const double* W_packed, const double* act_prm, const double* col_override, double lik_temp,
+                      const double* sigma, int which, npbnn_eval_out* out, double* out_grad);
 
 /* Permutation-sampling Shapley attributions of single rows, per stored weight set; np_bnn has no counterpart.  f_s is the network of set s
  * (through the output function with apply_out_fn = 1, the last layer's values with 0), x_e row rows[e] of the resident matrix `which`, b row

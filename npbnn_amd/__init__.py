@@ -36,6 +36,7 @@ from .pdp import get_feature_summary, get_pdp, make_pdp_features, pdp  # noqa: F
 from .ale import ale, get_ale, make_ale_edges  # noqa: F401
 from .saliency import get_saliency, saliency  # noqa: F401
 from .shapley import get_shapley, shapley  # noqa: F401
+from .gradient import log_posterior_grad, loglik_grad, map_estimate  # noqa: F401
 from .hpd import calcHPD, get_posterior_hpd, posterior_hpd  # noqa: F401
 from .lppd import get_posterior_lppd, posterior_lppd  # noqa: F401
 from .loo import get_posterior_loo, loo_compare, posterior_loo  # noqa: F401

@@ -45,6 +45,7 @@ INFO_SALIENCY_FOLD_NS = 28
 INFO_SHAPLEY_ROUTE = 29
 INFO_SHAPLEY_WALK_NS = 30
 INFO_LOO_FINAL_NS = 31
+INFO_GRAD_ROWS_NS, INFO_GRAD_FOLD_NS = 32, 33
 VALUE_F64, VALUE_F32 = 0, 1
 E_ARG = -1
 E_STATE = -2
@@ -155,6 +156,7 @@ SIGNATURES = {
                                     C.c_int, _DP]),
     "npbnn_predict_ale": (C.c_int, [_P, _DP, _DP, C.c_int32, C.c_int32, _DP, C.c_int32, _DP, C.c_int, C.c_int, C.POINTER(C.c_int64), _DP]),
     "npbnn_predict_saliency": (C.c_int, [_P, _DP, _DP, C.c_int32, _DP, C.c_int, C.c_int, _DP, _DP, _DP]),
+    "npbnn_loglik_grad": (C.c_int, [_P, _DP, _DP, _DP, C.c_double, _DP, C.c_int, C.POINTER(EvalOut), _DP]),
     "npbnn_predict_shapley": (C.c_int, [_P, _DP, _DP, C.c_int32, _DP, C.c_int, C.POINTER(C.c_int64), C.c_int32, C.c_int, C.POINTER(C.c_int64),
                                         C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int, _DP, _DP, _DP,
                                         _DP, _DP, _DP]),

@@ -272,6 +272,28 @@ class HipContext:
         return dict(loglik=out.loglik, sigma=np.array(out.sigma[:k]), sum_r=np.array(out.sum_r[:k]),
                     sum_r2=np.array(out.sum_r2[:k]), n_rows=out.n_rows, confusion=conf)
 
+    def loglik_grad(self, weights, act_prm=None, col_override=None, lik_temp=1.0, sigma=None, which=capi.TRAIN):
+        """``(eval dict, [gradient per layer])``: the log-likelihood as :meth:`eval` returns it (no confusion counts) and its
+        gradient with respect to every weight, shaped like ``weights`` (npbnn_loglik_grad).  ``weights``: the per-layer matrices.
+        Categorical, Gaussian with ``sigma`` given, and predicted-sigma likelihoods."""
+        shapes = [np.shape(x) for x in weights]
+        w = one_vector(list(weights))
+        ap = None if act_prm is None else capi.as_f64(act_prm)
+        co = None if col_override is None else capi.as_f64(col_override)
+        sg = None if sigma is None else capi.as_f64(np.broadcast_to(sigma, (self.arch.n_targets,)))
+        out = capi.EvalOut()
+        grad = np.zeros(w.size, dtype=np.float64)
+        self._chk(self._lib.npbnn_loglik_grad(self._ctx, capi.dptr(w), capi.dptr(ap), capi.dptr(co), float(lik_temp), capi.dptr(sg), which,
+                                              C.byref(out), capi.dptr(grad)))
+        k = self.arch.n_targets
+        layers, at = [], 0
+        for sh in shapes:
+            n = int(np.prod(sh))
+            layers.append(grad[at:at + n].reshape(sh))
+            at += n
+        return (dict(loglik=out.loglik, sigma=np.array(out.sigma[:k]), sum_r=np.array(out.sum_r[:k]), sum_r2=np.array(out.sum_r2[:k]),
+                     n_rows=out.n_rows, confusion=None), layers)
+
     def predict(self, weights, act_prm=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         w = one_vector(weights)
         ap = None if act_prm is None else capi.as_f64(act_prm)

@@ -3,7 +3,8 @@
  * npbnn_predict_shapley) as arithmetic on plain numbers: route 1's envelope and block shapes (npbnn_attrib_route_of), and per entry
  * how a job is cut into groups of prepared sets, launches of sets and chunks of rows, outputs or grid points under its byte budgets,
  * with the element count of every device buffer that cut needs (npbnn_attrib_sal_of, npbnn_attrib_shap_of, npbnn_attrib_pdp_g_chunk,
- * npbnn_attrib_ale_of).  Nothing here touches the GPU, the environment or a context: the entries read those, fill a request, allocate
+ * npbnn_attrib_ale_of), and the cut of npbnn_loglik_grad's table into chunks of rows (npbnn_attrib_grad_of: it runs on saliency's
+ * route-2 blocks; tests/test_host_grad_plan.py).  Nothing here touches the GPU, the environment or a context: the entries read those, fill a request, allocate
  * by the plan's counts and loop by the plan's numbers.  Plain C, so that the host library (npbnn_host.c) exports the same rule the HIP
  * library runs by, for the CPU tests of it (tests/test_host_attrib_plan.py).
  */
@@ -159,6 +160,54 @@ static inline void npbnn_attrib_sal_of(const npbnn_attrib_sal_req* s, npbnn_attr
     p->n_act = r->route == 1 ? 0 : rows_cap * r->sum_w;
     p->n_g = r->route == 1 ? 0 : rows_cap * 2 * r->max_w;
     p->lds_bytes = r->lds_bytes;
+}
+
+/* ---- weight gradient of the log-likelihood (npbnn_loglik_grad) ------------------------------------------------------------- */
+
+static const int kGradSlotRows = 256;                  /* rows whose products are added in float32: a workgroup of phase 1, a wave of phase 2 */
+static const int kGradLikTerms = 1 + 2 * NPBNN_MAX_TARGETS;   /* per slot: the log-likelihood terms, then every target's sum_r and sum_r2 */
+
+typedef struct npbnn_attrib_grad_req {
+    const npbnn_attrib_route* r;   /* the plan of saliency's route 2: one set, one bias point */
+    int n_weights;
+    long long n_rows;
+    long long scratch_bytes;       /* phase 1's scratches and the partials */
+} npbnn_attrib_grad_req;
+
+typedef struct npbnn_attrib_grad {
+    int rows_cap;        /* rows of a chunk: a multiple of kGradSlotRows */
+    int n_slot_cap;      /* slots of a chunk */
+    int n_chunks;
+    int n_tot;           /* doubles of a slot's partials: the packed weights, layer 0's H0P bias sums, kGradLikTerms */
+    int bsum_off, lik_off;         /* where the last two start in a slot's partials */
+    int a_off[NPBNN_MAX_LAYERS];   /* layer l's first unit in the scratches [unit][row] */
+    long long row_bytes;           /* scratch bytes per row of a chunk, its share of a slot's partials included */
+    long long n_act, n_fac, n_dl, n_D0, n_part, n_acc;   /* elements of the buffers (act, fac, dl, D0 float; part, acc double) */
+} npbnn_attrib_grad;
+
+static inline void npbnn_attrib_grad_of(const npbnn_attrib_grad_req* s, npbnn_attrib_grad* p) {
+    const npbnn_attrib_route* r = s->r;
+    const int L = r->q.n_layers;
+    long long rows_cap;
+    const long long rows_all = (s->n_rows + kGradSlotRows - 1) / kGradSlotRows * kGradSlotRows;
+    p->bsum_off = s->n_weights;
+    p->lik_off = s->n_weights + r->H0P;
+    p->n_tot = p->lik_off + kGradLikTerms;
+    /* per row: every unit's value, derivative factor and delta, layer 0's delta once more row-major, and 1 / 256 of a slot's partials */
+    p->row_bytes = ((long long)3 * r->sum_w + r->H0P) * 4 + ((long long)p->n_tot * 8 + kGradSlotRows - 1) / kGradSlotRows;
+    rows_cap = s->scratch_bytes / p->row_bytes / kGradSlotRows * kGradSlotRows;
+    rows_cap = attrib_min(attrib_min(attrib_max(rows_cap, kGradSlotRows), rows_all), 1ll << 24);   /* (a chunk's row indices are ints) */
+    p->rows_cap = (int)rows_cap;
+    p->n_slot_cap = (int)(rows_cap / kGradSlotRows);
+    p->n_chunks = (int)((s->n_rows + rows_cap - 1) / rows_cap);
+    for (int l = 0, off = 0; l < L; ++l) {
+        p->a_off[l] = off;
+        off += l == 0 ? r->q.H0 : r->q.l_out[l];
+    }
+    p->n_act = p->n_fac = p->n_dl = rows_cap * r->sum_w;
+    p->n_D0 = rows_cap * r->H0P;
+    p->n_part = (long long)p->n_slot_cap * p->n_tot;
+    p->n_acc = p->n_tot;
 }
 
 /* ---- Shapley ------------------------------------------------------------------------------------------------------------- */

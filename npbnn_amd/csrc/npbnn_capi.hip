@@ -23,6 +23,7 @@ int fail(npbnn_ctx* ctx, int code, const char* fmt, ...) {
 
 // What a context keeps for a table (labels, targets, weights, permuted columns) belongs to the matrix it came with, and goes with it.
 void forget_rows(npbnn_ctx* ctx, int which) {
+    ctx->grad_work.reset();      // (npbnn_loglik_grad's buffers were sized for the table that goes: the next call allocates for the new one)
     ctx->ds[which] = Dataset();
     ctx->ds[which].m = &ctx->store->table[which];
 }
@@ -969,6 +970,7 @@ int npbnn_get_info(npbnn_ctx* ctx, int what, int* out) {
     if (what == NPBNN_INFO_REPLAY_MAX_GROUP) { *out = ctx->replay_max_group; return NPBNN_OK; }
     if (what == NPBNN_INFO_CALIBRATION_FINAL_NS) { *out = ctx->calibration_ns; return NPBNN_OK; }
     if (what == NPBNN_INFO_LOO_FINAL_NS) { *out = ctx->loo_ns; return NPBNN_OK; }
+    if (what == NPBNN_INFO_GRAD_ROWS_NS || what == NPBNN_INFO_GRAD_FOLD_NS) { *out = ctx->grad_ns[what - NPBNN_INFO_GRAD_ROWS_NS]; return NPBNN_OK; }
     if (what >= NPBNN_INFO_PERMUTE_NS && what <= NPBNN_INFO_CONVERGENCE_FINAL_NS) { *out = ctx->fi_ns[what - NPBNN_INFO_PERMUTE_NS]; return NPBNN_OK; }
     if (ctx->arch_set && ctx->wide && (what == NPBNN_INFO_WAVES_PER_BLOCK || what == NPBNN_INFO_MAX_CANDIDATES || what == NPBNN_INFO_FAST_TAILS)) {
         *out = what == NPBNN_INFO_WAVES_PER_BLOCK ? 4 : what == NPBNN_INFO_MAX_CANDIDATES ? 1 : 0;      // (group passes: one chain per pass; what a replay of stored sets carried: NPBNN_INFO_REPLAY_MAX_GROUP)

@@ -244,6 +244,9 @@ struct npbnn_ctx : npbnn_ctx_streams {
                                    // every entry that goes through replay_sets, npbnn_sets.hip.h, leaves its passes and sinks in [1], [2])
     int calibration_ns = 0;        // NPBNN_FI_TIMING: the last npbnn_predict_sets_calibration's final kernel (NPBNN_INFO_CALIBRATION_FINAL_NS; fi_ns is full)
     int loo_ns = 0;                // NPBNN_FI_TIMING: the last npbnn_predict_sets_loo's psis_kernel (NPBNN_INFO_LOO_FINAL_NS)
+    std::shared_ptr<void> grad_work; // npbnn_loglik_grad's device buffers, kept between calls (GradWork, npbnn_grad.hip); freed when a table
+                                     // is replaced (forget_rows) and with the context
+    int grad_ns[2] = {0, 0};       // NPBNN_FI_TIMING: the last npbnn_loglik_grad's phase 1 and phase 2 (NPBNN_INFO_GRAD_ROWS_NS, NPBNN_INFO_GRAD_FOLD_NS)
     int replay_passes = 0, replay_max_group = 0;  // the last replay_sets: passes over X (float32 repeats included), most sets in one (NPBNN_INFO_REPLAY_*)
     int pdp_route = 0;             // route of the last npbnn_predict_pdp: 1 grid-batched kernel, 2 per grid point (NPBNN_INFO_PDP_ROUTE)
     int ale_route = 0;             // route of the last npbnn_predict_ale: 1 both edges from one read of X, 2 per edge; 0 none, or refused (NPBNN_INFO_ALE_ROUTE)

@@ -777,6 +777,12 @@ int npbnn_host_attrib_shapley(const npbnn_attrib_route* r, const int64_t* req, n
                                      req[8], req[9], req[10]};
     return npbnn_attrib_shap_of(&s, out);
 }
+int npbnn_host_attrib_grad(const npbnn_attrib_route* r, const int64_t* req, npbnn_attrib_grad* out) {
+    if (!r || !req || !out) return -1;
+    const npbnn_attrib_grad_req s = {r, (int)req[0], req[1], req[2]};
+    npbnn_attrib_grad_of(&s, out);
+    return 0;
+}
 int npbnn_host_attrib_pdp_g_chunk(int n_grid, int64_t n_rows, int C, int64_t acc_bytes) { return npbnn_attrib_pdp_g_chunk(n_grid, n_rows, C, acc_bytes); }
 int npbnn_host_attrib_ale(const npbnn_attrib_route* r, int K, int C, int64_t n_rows, int64_t part_bytes, npbnn_attrib_ale* out) {
     if (!r || !out) return -1;

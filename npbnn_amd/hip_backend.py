@@ -133,6 +133,11 @@ class HipBackend:
         return self.ctx.eval(weights, act_prm=slopes, col_override=col_override, lik_temp=lik_temp, sigma=sigma,
                              which=which, want_confusion=want_confusion)
 
+    def loglik_grad(self, weights, slopes=None, col_override=None, lik_temp=1.0, sigma=None, which=capi.TRAIN):
+        """The log-likelihood and its gradient per layer; see HipContext.loglik_grad."""
+        self._configure(weights)
+        return self.ctx.loglik_grad(weights, act_prm=slopes, col_override=col_override, lik_temp=lik_temp, sigma=sigma, which=which)
+
     def predict(self, weights, slopes=None, col_override=None, which=capi.TRAIN, apply_out_fn=True):
         self._configure(weights)
         return self.ctx.predict(weights, act_prm=slopes, col_override=col_override, which=which,
